@@ -11,6 +11,8 @@ full training step (frozen encoders fwd, fusion BiLSTM fwd/bwd, CTC, Adam) with 
 RNG and one loss read-back, exactly K of them between barrier+sync pairs; value = all ranks' frames / max time.
 The multi-process rendezvous (RCCL unique id) is a plain TCP exchange on MASTER_ADDR:MASTER_PORT+101; torch is not imported.
 
+    python bench.py --steps 20 --dump-outputs DIR   # + DIR/<name>.npy: loss, updated trainable weights and gradients of the
+                                                    # last timed step (same arguments, same inputs: two builds compare array by array)
     python bench.py --gpus 2 --comm host      # world > 1 WITHOUT RCCL: gradients are summed on the host (parallel.HostComm);
                                               # ranks may then share one GPU (per-rank batch is divided so that every rank's
                                               # persistent scans stay co-resident) - a functional check of the data-parallel
@@ -164,7 +166,12 @@ def main():
                     help="NCCL_MAX_NCHANNELS for the gradient all-reduce unless the environment sets it (0: RCCL's default)")
     ap.add_argument("--watchdog", type=float, default=120.0, help="seconds without progress after which a rank exits with code 3 (0: off)")
     ap.add_argument("--stall-at-step", type=int, default=-1, help=argparse.SUPPRESS)   # test hook: stop making progress there
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed (loss, updated trainable weights, their gradients) "
+                         "as DIR/<name>.npy - rank 0, before the f32 leg")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -276,6 +283,8 @@ def main():
         n, ms = dev.prof_get(i)
         fam[name] = {"launches": n, "ms": round(ms, 3)}
     dev.prof_enable(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, losses[-1])
     import ctypes
     n_persist, n_serial = ctypes.c_int(), ctypes.c_int()
     dev.call("mgr_persist_stats", ctypes.byref(n_persist), ctypes.byref(n_serial))
@@ -416,6 +425,24 @@ def main():
         comm.barrier()   # nobody tears its communicator down while a peer is still in a collective
         comm.close()
     return out
+
+
+def dump_outputs(out_dir, eng, loss):
+    """What the last timed step handed its caller, for comparing two builds output for output: the step's loss (float64), the
+    trainable weights after its Adam update and the gradients it computed (float32, Keras layouts; about 11 MB at config F).
+    Inputs, weights and the device-side noise / dropout seeds are fixed by the arguments, so equal arguments give equal inputs."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.asarray([loss], np.float64)}
+    w = eng.get_weights()
+    for name, g in eng.get_grads().items():
+        key = name.replace("/", ".")
+        arrays["weights." + key] = np.ascontiguousarray(w[name], np.float32)
+        arrays["grads." + key] = np.ascontiguousarray(g, np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (more than 64 MB)" % total)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def loss_parity(spec, dev, T_full, tuned=None):

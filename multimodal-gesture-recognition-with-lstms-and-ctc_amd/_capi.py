@@ -197,10 +197,6 @@ def load_library(build_if_missing=True):
     global _lib
     if _lib is not None:
         return _lib
-    # The HIP runtime multiplexes streams onto 4 hardware queues by default; a context here has 8 streams, and two logically
-    # independent streams that share a hardware queue serialise (measured: the host->device batch copy queued behind a whole
-    # training step and took the encoder stream with it, 51 instead of 42 ms/step).  Must be set before the runtime starts.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     if not os.path.exists(LIB_PATH) and build_if_missing:
         from . import _build
         _build.build(verbose=False)

@@ -12,6 +12,73 @@ int mgr_fail(int code, const char* fmt, ...) {
   return code;
 }
 
+namespace {
+// Stream placement.  The HIP runtime multiplexes a process's streams onto a capped number of in-order hardware queues (as few as 2)
+// and does not say which stream lands on which.  A residency wait (mgr_stream_wait_*resident*) spins on one stream until a
+// persistent launch on another stream is on the chip: if the two share a hardware queue, the launch sits behind the wait and the
+// wait runs into its bound.  Every such pair in this project is one even and one odd stream index, so a context keeps the rule
+// "no even stream shares a hardware queue with an odd one", testing each new stream with the two kernels below.
+__global__ void k_queue_probe_wait(unsigned* w, unsigned timeout_us) {
+  const unsigned long long t0 = wall_clock64();   // 100 MHz
+  while (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+    if (wall_clock64() - t0 > 100ull * timeout_us) {   // the setter never ran beside it: same hardware queue
+      w[1] = 1u;
+      return;
+    }
+    __builtin_amdgcn_s_sleep(8);
+  }
+}
+__global__ void k_queue_probe_set(unsigned* w) { __hip_atomic_store(w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+constexpr unsigned kProbeBoundUs = 1000;
+constexpr int kPlaceAttempts = 8;
+
+// *shared = 1 when work on `b` cannot start while `a` is busy (their kernels share a hardware queue)
+int queue_shared(hipStream_t a, hipStream_t b, unsigned* w, int* shared) {
+  unsigned r[2] = {0u, 0u};
+  MGR_HIP(hipMemset(w, 0, 2 * sizeof(unsigned)));
+  hipLaunchKernelGGL(k_queue_probe_wait, dim3(1), dim3(1), 0, a, w, kProbeBoundUs);
+  MGR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_queue_probe_set, dim3(1), dim3(1), 0, b, w);
+  MGR_LAUNCH_CHECK();
+  MGR_HIP(hipStreamSynchronize(a));
+  MGR_HIP(hipStreamSynchronize(b));
+  MGR_HIP(hipMemcpy(r, w, sizeof(r), hipMemcpyDeviceToHost));
+  *shared = r[1] != 0u;
+  return 0;
+}
+
+// A new stream for slot `idx` (priority `prio`, or the default with use_prio == 0) that shares no hardware queue with a stream of
+// the other parity among slots [0, n) other than idx.  A stream that does is kept aside while the next one is created (the runtime
+// then counts its queue as busier) and destroyed at the end; after kPlaceAttempts the last stream is taken as it is - placement
+// only, never a correctness dependency.
+int place_stream(mgr_ctx* c, int idx, int n, int use_prio, int prio, hipStream_t* out) {
+  unsigned* w = nullptr;
+  MGR_HIP(hipMalloc(&w, 2 * sizeof(unsigned)));
+  hipStream_t rejected[kPlaceAttempts];
+  int nrej = 0, rc = 0;
+  hipStream_t s = nullptr;
+  for (;;) {
+    hipError_t e = use_prio ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio) : hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+      s = nullptr;
+      rc = mgr_fail(-3, "hipStreamCreate: %s", hipGetErrorString(e));
+      break;
+    }
+    int clash = 0;
+    for (int j = 0; j < n && !clash && rc == 0; ++j)
+      if (j != idx && ((j ^ idx) & 1)) rc = queue_shared(c->streams[j], s, w, &clash);
+    if (rc != 0 || !clash || nrej == kPlaceAttempts) break;
+    rejected[nrej++] = s;
+  }
+  for (int i = 0; i < nrej; ++i) hipStreamDestroy(rejected[i]);
+  hipFree(w);
+  if (rc != 0 && s) hipStreamDestroy(s);
+  if (rc == 0) *out = s;
+  return rc;
+}
+}  // namespace
+
 extern "C" {
 
 int mgr_version(void) { return 100; }
@@ -41,7 +108,10 @@ int mgr_ctx_create(int device, mgr_ctx** out) {
   c->cu_count = prop.multiProcessorCount;
   c->hbm_bytes = prop.totalGlobalMem;
   snprintf(c->name, sizeof(c->name), "%s/%s", prop.name, prop.gcnArchName);
-  for (int i = 0; i < MGR_NUM_STREAMS; ++i) MGR_HIP(hipStreamCreateWithFlags(&c->streams[i], hipStreamNonBlocking));
+  for (int i = 0; i < MGR_NUM_STREAMS; ++i) {
+    const int rc = place_stream(c, i, i, 0, 0, &c->streams[i]);
+    if (rc != 0) return rc;
+  }
   for (int i = 0; i < MGR_NUM_EVENTS; ++i) MGR_HIP(hipEventCreate(&c->events[i]));
   for (int i = 0; i < 64; ++i) MGR_HIP(hipEventCreateWithFlags(&c->xev[i], hipEventDisableTiming));
   MGR_HIP(hipHostMalloc(&c->h_small_pinned, MGR_SMALL_D2H, hipHostMallocDefault));
@@ -217,7 +287,8 @@ int mgr_stream_set_priority(mgr_ctx* c, int idx, int level) {
   const int prio = level > 0 ? greatest : level < 0 ? least : (least + greatest) / 2;
   MGR_HIP(hipStreamSynchronize(c->streams[idx]));
   hipStream_t s;
-  MGR_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio));
+  const int rc = place_stream(c, idx, MGR_NUM_STREAMS, 1, prio, &s);
+  if (rc != 0) return rc;
   MGR_HIP(hipStreamDestroy(c->streams[idx]));
   c->streams[idx] = s;
   return 0;

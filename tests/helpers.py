@@ -20,3 +20,9 @@ def rel_err(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
     return float(np.abs(a - b).max() / max(1e-30, np.abs(b).max()))
+
+
+def many_keras_layers(rng, n):
+    """n Keras-style (layer name, [(weight name, array)]) entries, 0 - 2 small float32 weights each (h5lite writer tests)."""
+    return [("layer_%03d" % i, [("layer_%03d/w_%d:0" % (i, j), rng.standard_normal((3, 2 + j)).astype(np.float32))
+                                for j in range(i % 3)]) for i in range(n)]

@@ -13,7 +13,6 @@ class BwdJob(C.Structure):
 
 B, T = 64, int(os.environ.get("BPTT_PROBE_T", "1900"))
 HS = [int(h) for h in os.environ.get("BPTT_PROBE_H", "100").split(",")]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ref = {}
 for path in sys.argv[1:]:
     tune16 = 0

@@ -12,7 +12,6 @@ class ScanJob(C.Structure):
 
 B, T = 64, 1900
 HS = [tuple(int(h) for h in a.split("+")) for a in os.environ.get("SCAN_PROBE_H", "500+300,500").split(",")]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ref_out = {}
 for path in sys.argv[1:]:
     tunes = []
