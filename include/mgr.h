@@ -485,6 +485,26 @@ int mgr_ctc_beam_search(mgr_ctx* ctx, const float* P, const int32_t* input_len, 
                         int blank, int beam, float eps, int merge_repeated, int32_t* out, int32_t* out_len,
                         double* logp, void* ws, size_t ws_bytes);
 
+/* ---- K10: TimeDistributed CNN front-end of the RGB network (rgb_network/cnn_lstm.py: conv_1 / conv_3 / conv_5, each followed by
+ * MaxPooling2D) ------------------------------------------------------------------------------------------------------------------
+ * Per frame of N = B*T frames, channels-last: X [N][Hin][Win][Cin] -> valid Conv2D (W [ks][ks][Cin][Cout], b [Cout]) -> ReLU ->
+ * 2x2 / stride 2 max-pool with floor -> Y [N][Hp][Wp][Cout], Hp = (Hin - ks + 1) / 2, Wp likewise.  ks is 4 or 5, Cout a multiple of
+ * 4, W 16-byte aligned; a frame (Hin*Win*Cin floats) and a frame's pooled gradient (Hp*Wp*Cout floats + bytes) must fit 64 KiB.
+ * code [N][Hp][Wp][Cout] (uint8) routes the gradient through the pool: the window position dy*2+dx of the FIRST maximum in row-major
+ * window order, or MGR_CONV_NO_GRAD when the maximum is a ReLU zero (no position of that window gets a gradient).  Exact f32.
+ * mgr_conv_pool_bwd_data: dX [N][Hin][Win][Cin] (overwritten) from the pooled gradient dY through pool, ReLU and the transposed conv.
+ * mgr_conv_pool_bwd_weights: dW, db (overwritten), deterministic: fixed-order partial sums over frame chunks in ws
+ * (mgr_conv_pool_bwd_weights_ws_bytes), then a fixed-order pass over the chunks; no atomics.  The forward and data-gradient calls
+ * need no workspace. */
+#define MGR_CONV_NO_GRAD 0xFF
+int mgr_conv_pool_fwd(mgr_ctx* ctx, const float* X, int N, int Hin, int Win, int Cin, const float* W, const float* b, int ks, int Cout,
+                      float* Y, uint8_t* code);
+int mgr_conv_pool_bwd_data(mgr_ctx* ctx, const float* dY, const uint8_t* code, const float* W, int N, int Hin, int Win, int Cin, int ks,
+                           int Cout, float* dX);
+size_t mgr_conv_pool_bwd_weights_ws_bytes(int N, int Hin, int Win, int Cin, int ks, int Cout);
+int mgr_conv_pool_bwd_weights(mgr_ctx* ctx, const float* X, const float* dY, const uint8_t* code, int N, int Hin, int Win, int Cin, int ks,
+                              int Cout, float* dW, float* db, void* ws, size_t ws_bytes);
+
 /* ---- skeletal feature extraction (skeletal_network/skeletal_feature_extraction.py:24-215), fp64 like the original.
  * joints[n_frames][12] = lhX lhY rhX rhY leX leY reX reY hipX hipY shcX shcY of the WHOLE frame table in file order;
  * out[n_frames][23] = lh_v rh_v le_v re_v | lh_a rh_a le_a re_a | hands_d | lh,rh,le,re _hip_d | lh,rh,le,re _shc_d |

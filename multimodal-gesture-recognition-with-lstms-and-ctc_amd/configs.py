@@ -50,6 +50,20 @@ def early_fusion_spec(numfeats_speech=39, numfeats_skeletal=20, nb_classes=22, h
         optimizer={"lr": 1e-4, "decay": 1e-5, "clipvalue": 0.5, "maxnorm": 3.0}, name="early_multimodal")
 
 
+def rgb_spec(img_dim=60, nb_classes=22, h=512):
+    """rgb_network/cnn_lstm.py:251-375: TimeDistributed(Conv2D 16 5x5 -> MaxPool 2, Conv2D 32 5x5 -> MaxPool 2, Conv2D 48 4x4 ->
+    MaxPool 2, Flatten) -> 2x BiLSTM(h) + add -> Dense -> softmax -> CTC.  Every Dropout is 0 and there is no GaussianNoise."""
+    return NetworkSpec(
+        streams=[{"name": "the_input", "noise": 0.0, "residual": True, "trainable": True,
+                  "frontend": {"input_shape": [img_dim, img_dim, 1],
+                               "layers": [{"name": "conv_1", "filters": 16, "kernel_size": 5},
+                                          {"name": "conv_3", "filters": 32, "kernel_size": 5},
+                                          {"name": "conv_5", "filters": 48, "kernel_size": 4}]},
+                  "layers": [{"H": h, "dropout": 0.0, "name": "blstm_1"}, {"H": h, "dropout": 0.0, "name": "blstm_2"}]}],
+        fusion=None, head={"dropout": 0.0, "C": nb_classes, "dropout_name": "drop_4"},
+        optimizer={"lr": 1e-4, "decay": 0.0, "clipvalue": 0.5, "maxnorm": 3.0}, name="rgb_ctc_lstm")
+
+
 def baseline_config(key):
     """BASELINE.json configs[] as (spec, B, T, Lmax)."""
     if key == "A":   # audio plumbing: 2-layer BiLSTM(128), 21 labels + blank

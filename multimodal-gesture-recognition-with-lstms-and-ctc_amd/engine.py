@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import Device, DeviceArray
+from .spec import frontend_layers, input_width
 
 
 def _pad4(n):
@@ -299,9 +300,12 @@ class Engine:
         self._lab_user = [-1, -1]
         self._step_id = 0              # training steps enqueued so far
         self._synced_step = -1         # the host has seen the loss of this step (everything before its CTC is complete)
+        self.fe = {}       # stream name -> its CNN front-end: per conv layer (shape dict, pooled output, pool routing codes[, dX])
         for s in sp.streams:
             for ring in self._xin_ring:
-                ring[s["name"]] = dev.empty((B, T, s["F"]))
+                ring[s["name"]] = dev.empty((B, T, input_width(s)))
+            if s.get("frontend"):
+                self._build_frontend(s, train)
             if s["noise"] > 0:
                 self.X[s["name"]] = dev.empty((B, T, s["F"]))
             self.Xin = self._xin_ring[0]
@@ -371,6 +375,52 @@ class Engine:
             self.ws_dense = dev.bytes(self.lib.mgr_dense_bwd_ws_bytes(B, T, D, Cn))
             self.ws_head = dev.bytes(self.lib.mgr_head_ws_bytes(B, T, D, Cn, self.Lmax))
         self.dev.sync()
+
+    def _build_frontend(self, s, train):
+        """Buffers of a stream's CNN front-end: per conv layer the pooled output [B*T frames][Hp][Wp][Cout] (the last one is the
+        stream's LSTM input [B, T, F]) and its pool routing codes; for training the gradient w.r.t. each layer's input but the
+        first's (the data), the LSTM's dX into the last pooled map and the weight-gradient workspace."""
+        dev, N = self.mem, self.B * self.T
+        layers = []
+        for i, c in enumerate(frontend_layers(s["frontend"])):
+            lay = dict(c, Y=dev.empty((self.B, self.T, c["F"])), code=dev.empty((N * c["F"],), np.uint8), dX=None)
+            if train and s["trainable"] and i > 0:
+                lay["dX"] = dev.empty((N * c["Hin"] * c["Win"] * c["Cin"],))
+            layers.append(lay)
+        ws = None
+        if train and s["trainable"]:
+            ws = dev.bytes(max(self.lib.mgr_conv_pool_bwd_weights_ws_bytes(N, c["Hin"], c["Win"], c["Cin"], c["ks"], c["Cout"])
+                               for c in layers))
+        self.fe[s["name"]] = dict(layers=layers, ws=ws, dF=dev.empty((self.B, self.T, s["F"])) if ws is not None else None)
+
+    def _frontend_fwd(self, name, X):
+        """The front-end's forward on the current stream: conv + bias + ReLU + pool per layer (one launch each); returns the last
+        pooled map, the stream's LSTM input."""
+        N = self.B * self.T
+        self.fe[name]["X0"] = X           # (read again by the first layer's weight gradient)
+        for c in self.fe[name]["layers"]:
+            pre = "%s/%s/" % (name, c["name"])
+            self.dev.call("mgr_conv_pool_fwd", X, N, c["Hin"], c["Win"], c["Cin"], self._wview(pre + "W"), self._wview(pre + "b"),
+                          c["ks"], c["Cout"], c["Y"], c["code"])
+            X = c["Y"]
+        return X
+
+    def _frontend_bwd(self, name):
+        """The front-end's backward on the current stream, from the gradient the first LSTM layer left in fe["dF"]: per layer, last
+        first, dW / db and (but for the first layer) the gradient w.r.t. its input, which is the pooled map of the layer below."""
+        fe, N = self.fe[name], self.B * self.T
+        layers = fe["layers"]
+        dY = fe["dF"]
+        for i in range(len(layers) - 1, -1, -1):
+            c = layers[i]
+            X = layers[i - 1]["Y"] if i > 0 else fe["X0"]
+            pre = "%s/%s/" % (name, c["name"])
+            self.dev.call("mgr_conv_pool_bwd_weights", X, dY, c["code"], N, c["Hin"], c["Win"], c["Cin"], c["ks"], c["Cout"],
+                          self._gview(pre + "W"), self._gview(pre + "b"), fe["ws"], fe["ws"].nbytes)
+            if i > 0:
+                self.dev.call("mgr_conv_pool_bwd_data", dY, c["code"], self._wview(pre + "W"), N, c["Hin"], c["Win"], c["Cin"], c["ks"],
+                              c["Cout"], c["dX"])
+                dY = c["dX"]
 
     def _wview(self, name):
         if name in self.seg:
@@ -516,7 +566,7 @@ class Engine:
         if self._xin_user[slot] > self._synced_step:
             dev.wait_event(self.COPY_STREAM, self.EV_IN[slot])
         if self._xin_pin is None:   # page-locked staging, allocated at the first host batch (resident-input runs never need it)
-            self._xin_pin = [{s["name"]: dev.pinned((self.B, self.T, s["F"]), np.float32) for s in self.spec.streams}
+            self._xin_pin = [{s["name"]: dev.pinned((self.B, self.T, input_width(s)), np.float32) for s in self.spec.streams}
                              for _ in range(2)]
         # The page-locked staging set is refilled by the HOST: the copies enqueued out of it last time must be done.  (Round 6: a call
         # of the two-calls-ahead schedule that also runs its own encoder pass uploads THREE batches - its own, the next, the one after
@@ -526,7 +576,13 @@ class Engine:
             dev.event_sync(self.EV_XIN_COPIED[slot])
         for s in self.spec.streams:
             x = np.asarray(inputs[s["name"]])
-            if x.shape != (self.B, self.T, s["F"]):
+            if s.get("frontend"):
+                # (B, T, h, w, c) frames of a CNN front-end; they travel as rows of h * w * c
+                want = (self.B, self.T) + tuple(int(v) for v in s["frontend"]["input_shape"])
+                if x.shape != want:
+                    raise ValueError("input %s: expected %s got %s" % (s["name"], want, x.shape))
+                x = x.reshape(self.B, self.T, -1)
+            elif x.shape != (self.B, self.T, s["F"]):
                 raise ValueError("input %s: expected %s got %s" % (s["name"], (self.B, self.T, s["F"]), x.shape))
             stage = self._xin_pin[slot][s["name"]]
             np.copyto(stage, x, casting="unsafe")          # float64 batch -> float32 staging in one pass
@@ -668,6 +724,8 @@ class Engine:
                 dev.call("mgr_add_gaussian_noise", X, self.X[name], X.size, float(s["noise"]),
                          C.c_uint64(self._seed(900 + si)))
                 X = self.X[name]
+            if name in self.fe:
+                X = self._frontend_fwd(name, X)     # (where the other networks apply GaussianNoise: the CNN front-end)
             self._xcur[name] = X
         depth = max(len(s["layers"]) for s in sp.streams)
         feat_by_scans = True     # every stream's last layer writes FEAT (and its transposed copy) from its scan
@@ -1739,6 +1797,7 @@ class Engine:
         name = s["name"]
         nl = len(s["layers"])
         dout = self.dFEAT.view(col, (1,))
+        dF = self.fe[name]["dF"] if name in self.fe else None     # (the first layer's input gradient feeds the CNN front-end)
         if nl == 2:
             H1, H2 = s["layers"][0]["H"], s["layers"][1]["H"]
             if s["residual"]:
@@ -1750,11 +1809,13 @@ class Engine:
             if s["residual"]:
                 dev.call("mgr_add2d", self.dY1[name], 2 * H1, dout, W, self.dY1[name], 2 * H1, B * T, 2 * H1)
             self._bilstm_backward("%s/l0" % name, self.dY1[name], 2 * H1, self._xcur[name], s["F"], s["F"],
-                                  self.Y1[name], 2 * H1, None, 0)
+                                  self.Y1[name], 2 * H1, dF, s["F"] if dF is not None else 0)
         else:
             H1 = s["layers"][0]["H"]
             self._bilstm_backward("%s/l0" % name, dout, W, self._xcur[name], s["F"], s["F"],
-                                  self.FEAT.view(col, (1,)), W, None, 0)
+                                  self.FEAT.view(col, (1,)), W, dF, s["F"] if dF is not None else 0)
+        if dF is not None:
+            self._frontend_bwd(name)
 
     def apply_gradients(self):
         """all-reduce (if data parallel) -> clip -> Adam -> max-norm; identical on every replica."""

@@ -67,6 +67,8 @@ def _walk_keras_graph(cfg):
                    # auto-named wrapper ("bidirectional_N") is identified by its inner LSTM's name instead
                    name=inner.get("name", name) if name.startswith("bidirectional_") else name, wrapper=name,
                    trainable=bool(k.get("trainable", True)) and bool(inner.get("trainable", True)))
+        elif c == "TimeDistributed":
+            t = _time_distributed(k["layer"], ins, name)
         elif c == "Add":
             t = _T("add", ins)
         elif c in ("Concatenate", "Merge"):
@@ -89,6 +91,63 @@ def _walk_keras_graph(cfg):
     if pending:
         raise ValueError("unresolvable inbound nodes for layers %s" % [l.get("name") for l in pending])
     return out
+
+
+def _pair(v):
+    return tuple(int(x) for x in (v if isinstance(v, (list, tuple)) else (v, v)))
+
+
+def _time_distributed(layer, ins, name):
+    """TimeDistributed(Conv2D / MaxPooling2D / Flatten / Dropout) of the RGB network's CNN front-end (rgb_network/cnn_lstm.py) ->
+    a graph node; anything outside the form the device kernels implement (csrc/conv.hip) is refused."""
+    c, k = layer["class_name"], layer["config"]
+    if k.get("data_format", "channels_last") not in (None, "channels_last"):
+        raise ValueError("TimeDistributed %s (%s): only channels_last is implemented" % (c, name))
+    if c in ("Conv2D", "Convolution2D"):
+        ks = _pair(k["kernel_size"])
+        if ks[0] != ks[1] or ks[0] not in (4, 5):
+            raise ValueError("Conv2D %s: kernel %s (square 4x4 or 5x5 are implemented)" % (name, ks))
+        if k.get("activation") != "relu" or k.get("padding", "valid") != "valid" or _pair(k.get("strides", 1)) != (1, 1) \
+                or _pair(k.get("dilation_rate", 1)) != (1, 1) or not k.get("use_bias", True):
+            raise ValueError("Conv2D %s: only activation relu, padding valid, strides 1, dilation 1 with a bias are implemented" % name)
+        for con in ("kernel_constraint", "bias_constraint", "kernel_regularizer", "bias_regularizer", "activity_regularizer"):
+            if k.get(con) is not None:
+                raise ValueError("Conv2D %s: %s is not implemented" % (name, con))
+        return _T("conv", ins, name=name, filters=int(k["filters"]), ks=ks[0])
+    if c in ("MaxPooling2D", "MaxPool2D"):
+        pool = _pair(k.get("pool_size", 2))
+        strides = _pair(k.get("strides") or pool)
+        if pool != (2, 2) or strides != (2, 2) or k.get("padding", "valid") != "valid":
+            raise ValueError("MaxPooling2D %s: only pool 2x2, stride 2, padding valid is implemented" % name)
+        return _T("pool", ins, name=name)
+    if c == "Flatten":
+        return _T("flatten", ins, name=name)
+    if c == "Dropout":
+        rate = float(k.get("rate", k.get("p", 0.0)))
+        if rate != 0.0:
+            raise ValueError("TimeDistributed(Dropout) %s: rate %g (the front-end implements rate 0, the reference's)" % (name, rate))
+        return _T("td_identity", ins, name=name)
+    raise ValueError("TimeDistributed(%s) %s is not on the reference's RGB path" % (c, name))
+
+
+def _parse_frontend(t):
+    """flatten <- (pool <- conv [<- Dropout(0)])+ <- input (B, T, h, w, c) -> (input node, frontend dict)."""
+    if t.op != "flatten":
+        raise ValueError("a CNN front-end must end in TimeDistributed(Flatten)")
+    t = t.args[0]
+    layers = []
+    while t.op != "input":
+        if t.op != "pool" or t.args[0].op != "conv":
+            raise ValueError("the CNN front-end must be TimeDistributed Conv2D -> MaxPooling2D blocks (near %s)" % t.kw.get("name"))
+        conv = t.args[0]
+        layers.append({"name": conv.kw["name"], "filters": conv.kw["filters"], "kernel_size": conv.kw["ks"]})
+        t = conv.args[0]
+        while t.op == "td_identity":
+            t = t.args[0]
+    shape = t.kw["shape"]
+    if len(shape) != 5:
+        raise ValueError("the input of a CNN front-end must be (batch, time, h, w, c), got %s" % (shape,))
+    return t, {"input_shape": [int(v) for v in shape[2:]], "layers": layers[::-1]}
 
 
 def _kernel_maxnorm(inner, name):
@@ -137,7 +196,10 @@ def _parse_stream(t):
             return strip(x.args[0])
         return x
     base = strip(t)
-    if base.op == "concat":            # early fusion: concat of (noisy) inputs
+    if base.op == "flatten":           # TimeDistributed CNN front-end (rgb_network/cnn_lstm.py)
+        inp, fe = _parse_frontend(base)
+        s = {"name": inp.kw["name"], "frontend": fe}
+    elif base.op == "concat":            # early fusion: concat of (noisy) inputs
         members = [strip(m) for m in base.args]
         if any(m.op != "input" for m in members):
             raise ValueError("unsupported concat below the first LSTM")
@@ -184,7 +246,7 @@ def spec_from_keras_json(text):
     for x in g.values():
         if x.op == "input":
             sh = x.kw["shape"]
-            if len(sh) == 3:
+            if len(sh) in (3, 5):
                 maxlen = sh[1]
             elif x.kw["name"] == "the_labels":
                 Lmax = sh[1]
@@ -196,6 +258,14 @@ def keras_layer_order(spec):
     """[(keras layer name, [(variable name, our weight key)])] for every WEIGHTED layer, in Keras ``model.layers``
     order (depth-major: first BiLSTM of every stream, then the second, ..., fusion BiLSTM, Dense)."""
     out = []
+    for s in spec.streams:
+        # TimeDistributed(Conv2D) of a CNN front-end (rgb_network/cnn_lstm.py): the group is the wrapper's name (the reference names
+        # them conv_1 / conv_3 / conv_5); the variable names Keras 2.1.4 writes inside a TimeDistributed group are recalled as
+        # "<conv layer>/kernel:0", not pinned.  Loading matches groups by their arrays' shapes, in file order: a conv group has 2
+        # arrays like the Dense group and is told apart by its 4-d kernel (the Dense kernel is 2-d)
+        for c in (s.get("frontend") or {}).get("layers", []):
+            out.append((c["name"], [("%s/kernel:0" % c["name"], "%s/%s/W" % (s["name"], c["name"])),
+                                    ("%s/bias:0" % c["name"], "%s/%s/b" % (s["name"], c["name"]))]))
     n = 0
     depth = max(len(s["layers"]) for s in spec.streams)
     for k in range(depth):

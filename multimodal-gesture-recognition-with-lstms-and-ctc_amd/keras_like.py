@@ -231,6 +231,10 @@ class Model:
             for n in (s.get("inputs") or [s["name"]]):
                 L.append(Layer(n, "InputLayer", self))
         for s in sp.streams:
+            if s.get("frontend"):      # (rgb_network/cnn_lstm.py: TimeDistributed Conv2D / MaxPooling2D, no GaussianNoise)
+                for c in s["frontend"]["layers"]:
+                    L.append(Layer(c["name"], "TimeDistributed", self, "%s/%s" % (s["name"], c["name"]), s["trainable"], dict(c)))
+                continue
             L.append(Layer("gaussian_noise_" + s["name"], "GaussianNoise", self, config={"stddev": s["noise"]}))
             if s.get("inputs"):
                 L.append(Layer(s["name"], "Concatenate", self))
@@ -289,7 +293,7 @@ class Model:
         rng = np.random.RandomState(47)
         w = {}
         for name, shape, _, kind in self.spec.weight_table():
-            if kind in ("kernel", "dense"):
+            if kind in ("kernel", "dense", "conv"):
                 w[name] = rng.uniform(-0.05, 0.05, size=shape).astype(np.float32)
             elif kind == "recurrent":
                 H = shape[0]

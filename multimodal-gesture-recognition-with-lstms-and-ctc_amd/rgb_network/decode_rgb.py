@@ -1,0 +1,28 @@
+"""Decode for the RGB network (reference rgb_network/decode_rgb.py): plain best-path decoding of out[j, 2:] with repeats collapsed -
+the reference's confidence threshold is commented out, so none applies - over the 22 gesture names (index 21 = "sil", kept), and the
+MLF writer with the ten-file ignore list."""
+import numpy as np
+
+from ..decoding import confidence_filter_collapse, write_mlf
+from ..keras_like import Model
+from ..multimodal_fusion.sequence_decoding import ignore_list, map_gest  # noqa: F401  (the same 22 names and ignore list)
+from .cnn_lstm import load_model as _load_model
+
+
+def load_model(json_path="rgb_ctc_lstm_model.json", weights_path="rgb_ctc_lstm_weights_best.h5", device=0):
+    """The trained model and its softmax view (decode_rgb.py: Model(inputs=loaded.input, outputs=loaded.get_layer('softmax').output))."""
+    return prediction_model(_load_model(json_path, weights_path, device))
+
+
+def prediction_model(model):
+    return Model(inputs=model.input, outputs=model.get_layer('softmax').output)
+
+
+def decode_batch(pred_out, f_list, out_file="ctc_recout.mlf"):
+    """pred_out (N, T, C) posteriors -> per file the collapsed best-path gesture names of frames 2 ...; writes the MLF."""
+    P = np.asarray(pred_out)[:, 2:, :]
+    best = P.argmax(axis=2)           # (first index on ties, as mgr_frame_argmax)
+    ret = [[map_gest[int(i)] for i in confidence_filter_collapse(best[j], None, None)] for j in range(P.shape[0])]
+    nums = [int(str(f)[6:11]) if not isinstance(f, (int, np.integer)) else int(f) for f in f_list]
+    write_mlf(out_file, ret, nums, ignore_list, "Sample%05d")
+    return ret

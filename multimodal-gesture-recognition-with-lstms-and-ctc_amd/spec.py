@@ -19,6 +19,12 @@ class NetworkSpec:
                                "epsilon": 1e-7, "maxnorm": 3.0}, **(optimizer or {}))
         self.name = name
         for s in self.streams:
+            if s.get("frontend"):
+                fe = s["frontend"]
+                if s.get("noise", 0.0) or any(lay.get("dropout", 0.0) for lay in fe["layers"]):
+                    raise ValueError("stream %s: a CNN front-end takes no GaussianNoise and no Dropout before its convolutions"
+                                     % s["name"])
+                s["F"] = frontend_layers(fe)[-1]["F"]
             s.setdefault("noise", 0.0)
             s.setdefault("residual", len(s["layers"]) == 2)
             s.setdefault("trainable", True)
@@ -83,8 +89,13 @@ class NetworkSpec:
         return float(self.optimizer.get("maxnorm") or 0.0) if v is None else float(v)
 
     def weight_table(self):
-        """Ordered (name, keras_shape, trainable, kind) - Keras weight-list order: fwd W,U,b then bwd W,U,b."""
+        """Ordered (name, keras_shape, trainable, kind) - Keras weight-list order: a stream's CNN front-end (kernel (kh, kw, cin, cout),
+        bias) first, then per Bidirectional layer fwd W,U,b then bwd W,U,b."""
         out = []
+        for s in self.streams:
+            for c in frontend_layers(s.get("frontend")):
+                out.append(("%s/%s/W" % (s["name"], c["name"]), (c["ks"], c["ks"], c["Cin"], c["Cout"]), s["trainable"], "conv"))
+                out.append(("%s/%s/b" % (s["name"], c["name"]), (c["Cout"],), s["trainable"], "conv_bias"))
         for prefix, fin, H, _, tr in self.lstm_layers():
             for d in ("fwd", "bwd"):
                 out.append(("%s/%s/W" % (prefix, d), (fin, 4 * H), tr, "kernel"))
@@ -112,6 +123,13 @@ class NetworkSpec:
         (used from p >= 0.3 on, 16 <= F <= 2048) skip the products with dropped features, i.e. run the (1 - p) share of
         their K loops; the skipped terms are exact zeros, the result is the dense one."""
         mac = 0
+        fe_streams = set()
+        for s in self.streams:
+            for i, c in enumerate(frontend_layers(s.get("frontend"))):
+                conv = 4 * c["Hp"] * c["Wp"] if executed else c["Ho"] * c["Wo"]   # (the device forms the pooled windows only)
+                conv *= c["ks"] * c["ks"] * c["Cin"] * c["Cout"]
+                mac += conv * (1 + (2 if s["trainable"] and i > 0 else 1 if s["trainable"] else 0))   # fwd, dW [, dX]
+                fe_streams.add(s["name"])
         for prefix, fin, H, p, tr in self.lstm_layers():
             keep = (1.0 - p) if (executed and p >= 0.3 and 16 <= fin <= 2048) else 1.0
             proj = fin * 4 * H
@@ -120,6 +138,8 @@ class NetworkSpec:
             if tr:
                 bwd = 2 * (proj * keep + 2 * H * 4 * H)  # dW + (dh_rec, dU)
                 first = prefix.endswith("/l0")
+                if first and prefix.rsplit("/l", 1)[0] in fe_streams:
+                    bwd += 2 * fin * 4 * H  # dX to the CNN front-end
                 if not first and prefix != "fusion":
                     bwd += 2 * fin * 4 * H  # dX to a trainable layer below
                 elif prefix == "fusion" and any(s["trainable"] for s in self.streams):
@@ -127,3 +147,32 @@ class NetworkSpec:
                 mac += bwd
         mac += self.head_width * self.head["C"] * 3
         return 2 * mac if executed else int(2 * mac)
+
+
+def frontend_layers(frontend):
+    """Shapes of a stream's TimeDistributed CNN front-end (rgb_network/cnn_lstm.py): per layer a valid Conv2D (bias, ReLU) and a 2x2 /
+    stride 2 floor max-pool, channels-last.  frontend = {"input_shape": [h, w, c], "layers": [{"name", "filters", "kernel_size"}]};
+    returns per layer dict(name, Hin, Win, Cin, ks, Cout, Ho, Wo, Hp, Wp, F) with F = Hp * Wp * Cout, the flattened width of its
+    pooled output (channels-last flatten, f = (i * Wp + j) * Cout + c)."""
+    if not frontend:
+        return []
+    h, w, c = (int(v) for v in frontend["input_shape"])
+    out = []
+    for lay in frontend["layers"]:
+        ks, co = int(lay["kernel_size"]), int(lay["filters"])
+        ho, wo = h - ks + 1, w - ks + 1
+        hp, wp = ho // 2, wo // 2
+        if hp < 1 or wp < 1:
+            raise ValueError("front-end layer %s: input %dx%d too small for a %dx%d kernel and a 2x2 pool" % (lay["name"], h, w, ks, ks))
+        out.append(dict(name=lay["name"], Hin=h, Win=w, Cin=c, ks=ks, Cout=co, Ho=ho, Wo=wo, Hp=hp, Wp=wp, F=hp * wp * co))
+        h, w, c = hp, wp, co
+    return out
+
+
+def input_width(s):
+    """Per-frame width of a stream's raw input: F, or h * w * c of its front-end's frames."""
+    fe = s.get("frontend")
+    if not fe:
+        return s["F"]
+    h, w, c = (int(v) for v in fe["input_shape"])
+    return h * w * c
