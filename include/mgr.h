@@ -513,6 +513,21 @@ int mgr_conv_pool_bwd_weights(mgr_ctx* ctx, const float* X, const float* dY, con
 #define MGR_SKELETAL_FEATURE_COLS 23
 int mgr_skeletal_features(mgr_ctx* ctx, const double* joints, size_t n_frames, double* out);
 
+/* ---- HTK HCopy-compatible MFCC_0[_D[_A]] front-end of the audio network (README.md: 13 MFCCs + deltas + accelerations, made with
+ * HTK's HCopy from config_HCopy; algorithm restated in DESIGN 9c).  A batch of n_utts ragged utterances: samples (raw int16, no
+ * scaling) of utterance u are [sample_offsets[u], sample_offsets[u + 1]); it has (N - frameSize) / frameRate + 1 frames when
+ * N >= frameSize, else 0, and n_frames is their sum over the batch.  fftN is a power of two in [256, 2048] with frameSize <= fftN;
+ * numChans <= 128, numCeps <= min(numChans, 63); cepLifter 0 disables the lifter; accs needs deltas.  loChan (int32) / loWt (fp64)
+ * [fftN / 2] are HTK's filterbank table per bin (bin 0 = DC; loChan -1 = unused bin).  Each output row holds numCeps + 1 statics
+ * (C1..C_numCeps, C0), then as many deltas if deltas, then as many accelerations if accs, as f32.  Utterance u's rows are
+ * [out_offsets[u], out_offsets[u + 1]) (out_offsets has n_utts + 1 entries): row r holds frame r * out_stride, or zeros past the
+ * utterance's last frame, so the rows can be packed or a padded (B, T, cols) batch.  fp64 arithmetic; deterministic (no atomics).
+ * ws >= mgr_mfcc_ws_bytes(n_utts, n_frames, frameSize, fftN, numChans, numCeps). */
+size_t mgr_mfcc_ws_bytes(int n_utts, long long n_frames, int frameSize, int fftN, int numChans, int numCeps);
+int mgr_mfcc(mgr_ctx* ctx, const int16_t* samples, const int64_t* sample_offsets, int n_utts, long long n_frames, int frameSize,
+             int frameRate, int fftN, int numChans, int numCeps, int cepLifter, double preemph, int deltas, int accs, int out_stride,
+             const int32_t* loChan, const double* loWt, float* out, const int64_t* out_offsets, void* ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,13 +20,15 @@ class DataGenerator(BaseDataGenerator):
 
     def __init__(self, minibatch_size, numfeats, maxlen, nb_classes, dataset, val_split=0.2,
                  absolute_max_sequence_len=150, data_root='../data', synthetic_files=None, seed=20131901,
-                 word_level=True, rank=0, world=1):
+                 word_level=True, rank=0, world=1, store=None):
         self.numfeats = numfeats
         self.word_level = word_level
         names = {'train': ('train_audio', 'training_oov.csv'), 'val': ('val_audio', 'validation.csv'),
                  'final': ('final_audio', 'validation.csv')}[dataset]
         self.in_audio_dir = os.path.join(data_root, names[0])
-        if synthetic_files is None and os.path.isdir(self.in_audio_dir):
+        if store is not None:      # e.g. a datagen.WavStore: features extracted from the WAV files
+            pass
+        elif synthetic_files is None and os.path.isdir(self.in_audio_dir):
             store = CsvStore(self.in_audio_dir, None, os.path.join(data_root, names[1]))
         else:
             n = synthetic_files if synthetic_files is not None else 470

@@ -5,7 +5,9 @@ Two sample stores provide per-file feature matrices and label rows:
   * SyntheticStore - seeded ChaLearn-shaped sequences (no dataset exists in the build / GPU images),
   * CsvStore       - the reference's on-disk layout (per-file ``audio_<id>.csv``, one skeletal CSV with a
                      ``file_number`` column, a label CSV with ``Id`` / ``Sequence``), read once and cached instead of
-                     one ``pd.read_csv`` per file per step.
+                     one ``pd.read_csv`` per file per step,
+  * WavStore       - CsvStore's layout with the audio features computed from the WAV files on the GPU
+                     (audio_network/feature_extraction.py) instead of read from HTK-made CSVs.
 The batch contract (dict keys, float64 arrays, np.ones initialisation, post-padding with zeros, labels padded with
 -1, the blank substitution for empty label rows, input_length = maxlen - 2) is the reference's.
 """
@@ -113,6 +115,38 @@ class CsvStore:
 
     def labels(self, file_id):
         return self.labs.get(int(file_id), np.zeros((0,), np.float32))
+
+
+class WavStore(CsvStore):
+    """CsvStore with the audio features extracted from ``wav_dir`` on the GPU: the files whose names match ``pattern`` (its group is
+    the file number) go through the HTK MFCC_0_D_A front-end in batched launches, every ``audio_stride``-th frame is kept (100 fps
+    -> 20 fps) and the result is float64, as CsvStore returns for the CSVs feature_extraction.write_audio_csv writes of the same
+    features (equal after rounding to f32: pandas' default float parser may differ in the last bit of a 17-digit decimal).
+    ``config`` is passed to feature_extraction.mfcc (None: the reference's config_HCopy)."""
+
+    def __init__(self, wav_dir, skeletal_csv=None, label_csv=None, pattern=r'Sample(\d+)_audio\.wav', audio_stride=5, config=None,
+                 dev=None):
+        from .audio_network import feature_extraction as fe
+        CsvStore.__init__(self, None, skeletal_csv, label_csv)
+        by_rate = {}
+        for name in sorted(os.listdir(wav_dir)):
+            m = re.fullmatch(pattern, name)
+            if not m:
+                continue
+            samples, rate = fe.read_wav(os.path.join(wav_dir, name))
+            by_rate.setdefault(rate, []).append((int(m.group(1)), samples))
+        for rate, files in sorted(by_rate.items()):
+            start = 0
+            while start < len(files):      # batches of at most MAX_SAMPLES / MAX_UTTS_PER_LAUNCH (at least one file)
+                end, total = start, 0
+                while end < len(files) and end - start < fe.MAX_UTTS_PER_LAUNCH and \
+                        (end == start or total + files[end][1].size <= fe.MAX_SAMPLES_PER_LAUNCH):
+                    total += files[end][1].size
+                    end += 1
+                feats = fe.mfcc([s for _, s in files[start:end]], rate, config=config, dev=dev, stride=audio_stride)
+                for (fid, _), f in zip(files[start:end], feats):
+                    self.audio[fid] = f.astype(np.float64)
+                start = end
 
 
 class BaseDataGenerator(Callback):

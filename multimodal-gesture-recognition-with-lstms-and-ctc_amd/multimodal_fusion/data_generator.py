@@ -10,7 +10,8 @@ class DataGenerator(BaseDataGenerator):
     model_weights_name = "multimodal_ctc_blstm_weights.h5"
 
     def __init__(self, minibatch_size, numfeats_skeletal, numfeats_speech, maxlen, nb_classes, dataset, val_split=0.2,
-                 absolute_max_sequence_len=35, data_root='../data', synthetic_files=None, seed=20131900, rank=0, world=1):
+                 absolute_max_sequence_len=35, data_root='../data', synthetic_files=None, seed=20131900, rank=0, world=1,
+                 store=None):
         self.numfeats_speech = numfeats_speech
         self.numfeats_skeletal = numfeats_skeletal
         names = {'train': ('train_audio', 'Training_set_skeletal.csv', 'training_oov.csv'),
@@ -19,7 +20,9 @@ class DataGenerator(BaseDataGenerator):
         self.in_audio_dir = os.path.join(data_root, names[0])
         self.in_file_skeletal = os.path.join(data_root, names[1])
         label_csv = os.path.join(data_root, names[2])
-        if synthetic_files is None and os.path.isdir(self.in_audio_dir) and os.path.isfile(self.in_file_skeletal):
+        if store is not None:      # e.g. a datagen.WavStore: features extracted from the WAV files
+            pass
+        elif synthetic_files is None and os.path.isdir(self.in_audio_dir) and os.path.isfile(self.in_file_skeletal):
             store = CsvStore(self.in_audio_dir, self.in_file_skeletal, label_csv)
         else:
             n = synthetic_files if synthetic_files is not None else 470
