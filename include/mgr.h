@@ -528,6 +528,17 @@ int mgr_mfcc(mgr_ctx* ctx, const int16_t* samples, const int64_t* sample_offsets
              int frameRate, int fftN, int numChans, int numCeps, int cepLifter, double preemph, int deltas, int accs, int out_stride,
              const int32_t* loChan, const double* loWt, float* out, const int64_t* out_offsets, void* ws, size_t ws_bytes);
 
+/* ---- upper-body crops of the RGB network's frames (rgb_network/roi_extraction.py:18-80 of the reference).  frames are
+ * n BGR uint8 frames (n, H, W, 3), 4-byte aligned, 3 W a multiple of 4, W <= 4096; boxes int32 (n, 4) = [y0, y1, x0, x1) with
+ * 0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W (the host has applied the reference's clamps, slicing and fallback; a frame whose box is
+ * outside these bounds gets zeros); 1 <= img_dim <= 64.  out (n, img_dim, img_dim) uint8, 4-byte aligned: OpenCV's 8-bit BGR2GRAY
+ * Y = (1868 B + 9617 G + 4899 R + 8192) >> 14 of the crop, resized with OpenCV's generic fixed-point INTER_CUBIC path: per axis
+ * scale = 1 / (img_dim / size) (double), fx = (float)((d + 0.5) scale - 0.5), sx = floor(fx), fx -= sx, cubic weights (A = -0.75)
+ * in float32, the fourth 1 - c0 - c1 - c2, each rounded half to even to c * 2048; taps sx - 1 .. sx + 2 clamped to the crop;
+ * int32 horizontal sums, int32 vertical sums of 4 taps x 4 weights, (v + 2^21) >> 22 saturated to 0..255.  Bit-exact contract;
+ * deterministic (no atomics). */
+int mgr_roi_crop(mgr_ctx* ctx, const uint8_t* frames, int n, int H, int W, const int32_t* boxes, int img_dim, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,7 @@ SIGNATURES = {
     "mgr_conv_pool_bwd_data": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mgr_conv_pool_bwd_weights_ws_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
     "mgr_conv_pool_bwd_weights": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz]),
+    "mgr_roi_crop": (i32, [vp, vp, i32, i32, i32, vp, i32, vp]),
 }
 
 SCAN_GAVE_UP, SCAN_NONFINITE = 1, 8   # enum in include/mgr.h (mgr_scan_status)

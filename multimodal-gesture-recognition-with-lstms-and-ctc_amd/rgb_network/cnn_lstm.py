@@ -26,10 +26,12 @@ class DataGenerator(K.Callback):
     blank label (nb_classes - 1) with label_length 1; the batch is then normalised with ``X -= 128; X /= 255``; input_length is
     maxlen - 2; the train / validation split shuffles the sorted directory listing after ``random.seed(10)`` and both lists are
     cut to a multiple of the batch size; on_epoch_end shuffles both again.
-    synthetic_files=n: n generated files (Sample00000 ...; every fifth has no label row) instead of a directory."""
+    synthetic_files=n: n generated files (Sample00000 ...; every fifth has no label row) instead of a directory.
+    store=roi_extraction.RoiStore: the file list and the frames come from the store (the crops of a colour-video directory, made on
+    the GPU on first use) instead of data_path; the labels still come from lab_file."""
 
     def __init__(self, minibatch_size, img_dim, maxlen, val_split, nb_classes=22, data_path=None, lab_file=None,
-                 absolute_max_sequence_len=28, synthetic_files=None, seed=20131903):
+                 absolute_max_sequence_len=28, synthetic_files=None, seed=20131903, store=None):
         super().__init__()
         self.minibatch_size = minibatch_size
         self.maxlen = maxlen
@@ -44,6 +46,9 @@ class DataGenerator(K.Callback):
         self.blank_label = np.array([self.nb_classes - 1])
         self.synthetic_files = synthetic_files
         self.seed = seed
+        self.store = store
+        if store is not None and synthetic_files is not None:
+            raise ValueError("store and synthetic_files are exclusive")
         self.load_dataset()
 
     # ---- data sources ------------------------------------------------------------------------
@@ -64,7 +69,7 @@ class DataGenerator(K.Callback):
             with open(self.lab_file) as f:
                 for row in csv.DictReader(f):
                     self.labs.setdefault(int(row["Id"]), row["Sequence"])
-            file_list = sorted(os.listdir(self.data_path))
+            file_list = self.store.names() if self.store is not None else sorted(os.listdir(self.data_path))
         random.seed(10)
         random.shuffle(file_list)
         split_point = int(len(file_list) * (1 - self.val_split))
@@ -84,6 +89,8 @@ class DataGenerator(K.Callback):
             rng = np.random.RandomState(self.seed + 7 * num + 1)
             n = rng.randint(self.maxlen // 2, self.maxlen + self.maxlen // 4 + 1)
             return rng.randint(0, 256, (n, self.img_dim, self.img_dim, 1)).astype(np.float64)
+        if self.store is not None:
+            return self.store.frames(file).astype(float)
         return np.load(os.path.join(self.data_path, file)).astype(float)
 
     def get_size(self, train):
