@@ -113,7 +113,7 @@ int mgr_lstm_input_proj_pair(mgr_ctx* ctx, const float* X, int ldx, const float*
  * holds the actual factors, 0 or 1/(1-p)): from drop_rate >= 0.3 on (and 16 <= F <= 2048) the K loop runs per gate
  * over the kept features only (gemm.hip, k_gemm_nn_sparse) - the same sums with the zero terms left out, i.e. equal to
  * mgr_lstm_input_proj up to fp32 summation order.  ws from mgr_lstm_input_proj_dropout_ws_bytes (index lists, rebuilt by
- * every call).  tune key 9 = 1 keeps the dense kernel. */
+ * every call).  MGR_TUNE_PROJ_DENSE = 1 keeps the dense kernel. */
 size_t mgr_lstm_input_proj_dropout_ws_bytes(int B, int F, int H);
 int mgr_lstm_input_proj_dropout(mgr_ctx* ctx, const float* X, int ldx, const float* mask4, float drop_rate,
                                 const float* Wp, const float* bp, float* Z, int B, int T, int F, int H, void* ws,
@@ -131,10 +131,10 @@ int mgr_lstm_input_proj_dropout(mgr_ctx* ctx, const float* X, int ldx, const flo
  *   x_absmax < 0: |x_absmax| is a bound the PRODUCER of XT guarantees by construction - the transposed copies the scans of this
  *     library write (mgr_scan_job.YT) hold h = o * tanh(c), |h| <= 1, or the sum of two of them (residual input), <= 2 - and no
  *     check is made.  This is what the engine passes for the buffers its own scans fill.
- *   0, or tune key 15 = 1: v_mfma_f32_32x32x2_f32.
+ *   0, or MGR_TUNE_GEMM_F32 = 1: v_mfma_f32_32x32x2_f32.
  * mask4 may be NULL (no dropout: inference): with a bound the plain dense projection on the f16 pipe (k_gemm_nn_dense16: one
- * K loop over all features, the A tile staged once for the four gates; tune key 10 = 2 takes it with a mask as well, the mask
- * factors folded into the weight tiles), without one the f32 kernel over all features. */
+ * K loop over all features, the A tile staged once for the four gates; MGR_TUNE_PROJ_DENSE16_MASKED = 2 takes it with a mask as
+ * well, the mask factors folded into the weight tiles), without one the f32 kernel over all features. */
 int mgr_lstm_input_proj_dropout_wants_transposed(mgr_ctx* ctx, float drop_rate, int F);
 int mgr_lstm_input_proj_dropout_t(mgr_ctx* ctx, const float* XT, int ldt, const float* mask4, float drop_rate,
                                   const float* Wp, const float* bp, float* Z, int B, int T, int F, int H, void* ws,
@@ -203,16 +203,18 @@ int mgr_lstm_scan_fwd_multi(mgr_ctx* ctx, int njobs, const mgr_scan_job* jobs, v
 /* Explicit launch options of the two multi-scan calls (round 6; the same calls, with the choices a scheduler makes PER CALL passed
  * as arguments instead of through context-wide tune keys, and with the launch number handed back).
  *   struct_size  sizeof(mgr_scan_launch_opts) of the CALLER's header: members beyond it are taken as zero, so the struct can grow.
- *   form         forward call: MGR_SCAN_FORM_*; backward call: MGR_BPTT_FORM_*.  AUTO (0) = what tune keys 4 / 16 say.
+ *   form         forward call: MGR_SCAN_FORM_*; backward call: MGR_BPTT_FORM_*.  AUTO (0) = what MGR_TUNE_SCAN_FORM /
+ *                MGR_TUNE_BPTT_FORM say.
  *   seq_out      host word (ordinary or page-locked memory; NULL: not wanted) that receives, BEFORE the call returns, the launch
  *                number of the persistent multi-CU launch this call enqueued - what mgr_stream_wait_resident takes - or MGR_SEQ_NONE
  *                when the call enqueued no launch that enters the residency ledger (single-CU kernels, fallbacks).  With a word from
  *                mgr_host_alloc this is the hand-over for a wait that was enqueued BEFORE the launch it waits for
  *                (mgr_stream_wait_resident_word). */
-enum { MGR_SCAN_FORM_AUTO = 0, MGR_SCAN_FORM_PLAIN = 1, MGR_SCAN_FORM_PAIR = 2, MGR_SCAN_FORM_FUSED = 3,
+enum { MGR_SCAN_FORM_AUTO = 0, MGR_SCAN_FORM_PLAIN = 1, MGR_SCAN_FORM_FUSED = 3,
        MGR_SCAN_FORM_FUSED_ANY = 4 };   /* FUSED: launches that do not fit one workgroup per CU as they are; FUSED_ANY: every launch the
-                                         * fused kernel can run (a narrow layer then holds ceil(G / 2) whole CUs per cluster) */
-enum { MGR_BPTT_FORM_AUTO = 0, MGR_BPTT_FORM_TRIMMED = 1, MGR_BPTT_FORM_YIELDING = 2, MGR_BPTT_FORM_DIRECT = 3,   /* tune key 16 = 0 / 1 / 2 */
+                                         * fused kernel can run (a narrow layer then holds ceil(G / 2) whole CUs per cluster).  2 (the
+                                         * retired pair form) is refused. */
+enum { MGR_BPTT_FORM_AUTO = 0, MGR_BPTT_FORM_TRIMMED = 1, MGR_BPTT_FORM_YIELDING = 2, MGR_BPTT_FORM_DIRECT = 3,   /* MGR_TUNE_BPTT_FORM = 0 / 1 / 2 */
        /* round 6, narrow layers (16 < H <= 128) with an exchange: 8-wave workgroups that run TWO unit groups of their cluster, a CU each
         * (H = 100: 32 workgroups instead of 56), with the trimmed step / the direct gather inside; the same bits as every other form.  A
         * launch that does not qualify takes the trimmed / direct form. */
@@ -238,43 +240,62 @@ int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* ctx, int njobs, const mgr_scan_job* jobs
  * MGR_ABI_REVISION. */
 #define MGR_ABI_REVISION 7
 int mgr_abi_struct_sizes(unsigned out[4]);
-/* Tuning / test hooks.  key 0 (MGR_TUNE_SCAN_PATH): 0 auto, 1 force the L2-streaming fallback kernels,
- * 2 force one workgroup per batch group (no inter-CU exchange) where it fits, 3 force clusters with 4 tiles per
- * workgroup, 4 same with 8 tiles per workgroup.  key 1: !=0 makes scan_fwd check the give-up word synchronously.
- * key 2: print the scan plan.  key 3: 1 = K-split scan launches keep contiguous cluster ids and write-through publishes (no
- *        XCD-local exchange).
- * key 4: 2 = split-f16 K-split scan launches take the PAIR form (two 16-sample groups per workgroup, one workgroup per CU) whenever
- *        they qualify; bit-identical to the default (two workgroups per CU) and slower: kept as a measured alternative.
- *        3 = launches that do not fit ONE workgroup per CU as they are (config F's encoder depths: 408 workgroups) take the FUSED form:
- *        8-wave workgroups that run two unit groups of their cluster, a CU each (208), bit-identical; the CUs they leave free are what
- *        4-wave persistent launches of other streams get - the admission ledger then counts those by the CUs they need two to a CU,
- *        and their caller starts them once the fused launch is resident (mgr_stream_wait_resident) so that they do land there.
- * key 7: one-tile-per-wave clusters: 0 = K-split step (register-direct gather), 1 = LDS-image step.
- * key 8: 1 = the multi-CU BPTT keeps its 4-wave kernel instead of the split-role (4 compute + 4 gather waves) one, 2 = always split.
- * key 9: 1 = mgr_lstm_input_proj_dropout always takes the dense kernel.
- * key 10: 2 = mgr_lstm_input_proj_dropout_t with a bound on |XT| takes the dense-K split-f16 kernel with a mask as well.
- * key 12: mgr_lstm_input_proj_dropout_ts tile: 0 = the library's choice, 1 = 128 x 64 (4 waves, two workgroups per CU), 2 = 128 x 128 (8 waves).
- * key 13: 1 = mgr_dense_softmax_fwd / mgr_dense_bwd keep their LDS-tiled vector-ALU kernels where the matrix-core forms would run.
- * key 14: K-split scan step: 0 = recurrent product on the f16 matrix pipe with every f32 operand split into an f16 (hi, lo) pair and
- *        f32 accumulation (22+ significant bits per operand; lstm_cluster.hip cluster_run_k16), 1 = v_mfma_f32_16x16x4_f32.
- * key 15: 1 = the transposed-input projection / parameter-gradient GEMMs keep their f32 MFMA kernels whatever bound the caller states.
- * key 20 / 21: KiB of LDS the CTC recurrence kernel / the CTC per-frame kernels ask for at least (0: what they use).  A placement hint
- *         for callers that run mgr_ctc_loss_grad / mgr_head_fwd_bwd beside persistent scan launches of another stream: a workgroup that
- *         asks for more LDS than a scan workgroup leaves on its CU lands on a CU without one (engine.py sets 96 / 64 for such steps).
- * key 19: 1 = mgr_lstm_scan_bwd_multi[_ex] with form AUTO takes MGR_BPTT_FORM_SINGLE_CU where it qualifies (A/B of whole runs).
- * key 18: 1 = mgr_ctc_loss_grad runs one sample per workgroup (rounds 1 - 5); 0 = two (from B = 2 on: the alpha / beta chains of a
- *         workgroup's two samples on its four SIMDs - 32 workgroups for config F's 64 samples, which the 48 CUs beside fused encoder scans
- *         hold one per CU); the same bits.
- * key 17: 1 = the two halves of a FUSED scan workgroup each fetch and verify the whole h image of the step themselves (round 5's
- *         k_scan_cluster_k16f); 0 = they share ONE gather through LDS (k_scan_cluster_k16fs: half the L2 traffic); the same bits.
- * key 16: 1 = the BPTT of narrow layers (H <= 128) launched next runs BESIDE persistent scans of another stream: it takes the form that
- *         yields to them (two barriers, partial sums through LDS) instead of the one trimmed along its dependent chain, which is faster
- *         alone (H = 100: 1.77 against 2.29 us per step) and costs the step beside them; same results bit for bit.  The engine sets it
- *         from its schedule (a deterministic choice: it never depends on what happens to be running).
- *         2 = the direct gather: every wave fetches the words of its own cells from all sources, no partial sums through LDS, one barrier
- *         per step - the fastest form alone (1.58 us per step), 4.7 x the texture-path traffic: for launches that have CUs of their own
- *         (beside fused encoder scans).  All three forms give the same bits. */
-enum { MGR_TUNE_SCAN_PATH = 0, MGR_TUNE_COUNT = 24 };
+/* Tuning / test hooks: context-wide keys set with mgr_tune, 0 by default.  Keys 5, 6, 17, 22 and 23 are unused; mgr_tune refuses
+ * the settings of retired forms (key 4 = 2, key 17 != 0) rather than run the default under their name. */
+enum {
+  /* 0 auto, 1 force the L2-streaming fallback kernels, 2 force one workgroup per batch group (no inter-CU exchange) where it fits,
+   * 3 force clusters with 4 tiles per workgroup, 4 same with 8 tiles per workgroup. */
+  MGR_TUNE_SCAN_PATH = 0,
+  MGR_TUNE_SCAN_SYNC_CHECK = 1,     /* != 0: the multi-scan calls check the give-up word synchronously */
+  MGR_TUNE_SCAN_PRINT_PLAN = 2,     /* != 0: print the forward scan plan */
+  /* 1 = K-split scan launches keep contiguous cluster ids and write-through publishes (no XCD-local exchange). */
+  MGR_TUNE_SCAN_NO_XCD_LOCAL = 3,
+  /* form of the split-f16 K-split scan launches (mgr_lstm_scan_fwd_multi[_ex] with form AUTO): 3 = launches that do not fit ONE
+   * workgroup per CU as they are (config F's encoder depths: 408 workgroups) take the FUSED form: 8-wave workgroups that run two unit
+   * groups of their cluster, a CU each (208), bit-identical; the CUs they leave free are what 4-wave persistent launches of other
+   * streams get - the admission ledger then counts those by the CUs they need two to a CU, and their caller starts them once the
+   * fused launch is resident (mgr_stream_wait_resident) so that they do land there.  Any other value: the plain form. */
+  MGR_TUNE_SCAN_FORM = 4,
+  MGR_TUNE_SCAN_LDS_IMAGE = 7,      /* one-tile-per-wave clusters: 0 = K-split step (register-direct gather), 1 = LDS-image step */
+  /* 1 = the multi-CU BPTT keeps its 4-wave kernel instead of the split-role (4 compute + 4 gather waves) one, 2 = always split. */
+  MGR_TUNE_BPTT_SPLIT_ROLE = 8,
+  MGR_TUNE_PROJ_DENSE = 9,          /* 1 = mgr_lstm_input_proj_dropout always takes the dense kernel */
+  /* 2 = mgr_lstm_input_proj_dropout_t with a bound on |XT| takes the dense-K split-f16 kernel with a mask as well. */
+  MGR_TUNE_PROJ_DENSE16_MASKED = 10,
+  /* 2 = mgr_lstm_input_proj_dropout from row-major X takes 128-unit tiles instead of 64: faster alone, slower in the training step
+   * (its 512-thread workgroups need two free wave slots on all four SIMDs of a CU at once). */
+  MGR_TUNE_PROJ_WIDE_TILES = 11,
+  /* mgr_lstm_input_proj_dropout_ts tile: 0 = the library's choice, 1 = 128 x 64 (4 waves, two workgroups per CU), 2 = 128 x 128
+   * (8 waves). */
+  MGR_TUNE_PROJ_TS_TILE = 12,
+  /* 1 = mgr_dense_softmax_fwd / mgr_dense_bwd keep their LDS-tiled vector-ALU kernels where the matrix-core forms would run. */
+  MGR_TUNE_DENSE_VALU = 13,
+  /* K-split scan step: 0 = recurrent product on the f16 matrix pipe with every f32 operand split into an f16 (hi, lo) pair and f32
+   * accumulation (22+ significant bits per operand; lstm_cluster.hip cluster_run_k16), 1 = v_mfma_f32_16x16x4_f32. */
+  MGR_TUNE_SCAN_F32_MFMA = 14,
+  /* 1 = the transposed-input projection / parameter-gradient GEMMs keep their f32 MFMA kernels whatever bound the caller states. */
+  MGR_TUNE_GEMM_F32 = 15,
+  /* form of the narrow-layer (H <= 128) BPTT with form AUTO.  1 = the BPTT launched next runs BESIDE persistent scans of another
+   * stream: it takes the form that yields to them (two barriers, partial sums through LDS) instead of the one trimmed along its
+   * dependent chain, which is faster alone (H = 100: 1.77 against 2.29 us per step) and costs the step beside them; same results bit
+   * for bit.  The engine sets it from its schedule (a deterministic choice: it never depends on what happens to be running).
+   * 2 = the direct gather: every wave fetches the words of its own cells from all sources, no partial sums through LDS, one barrier
+   * per step - the fastest form alone (1.58 us per step), 4.7 x the texture-path traffic: for launches that have CUs of their own
+   * (beside fused encoder scans).  All three forms give the same bits. */
+  MGR_TUNE_BPTT_FORM = 16,
+  /* 1 = mgr_ctc_loss_grad runs one sample per workgroup (rounds 1 - 5); 0 = two (from B = 2 on: the alpha / beta chains of a
+   * workgroup's two samples on its four SIMDs - 32 workgroups for config F's 64 samples, which the 48 CUs beside fused encoder scans
+   * hold one per CU); the same bits. */
+  MGR_TUNE_CTC_ONE_SAMPLE = 18,
+  /* 1 = mgr_lstm_scan_bwd_multi[_ex] with form AUTO takes MGR_BPTT_FORM_SINGLE_CU where it qualifies (A/B of whole runs). */
+  MGR_TUNE_BPTT_SINGLE_CU = 19,
+  /* KiB of LDS the CTC recurrence kernel (20) / the CTC per-frame kernels (21) ask for at least (0: what they use).  A placement hint
+   * for callers that run mgr_ctc_loss_grad / mgr_head_fwd_bwd beside persistent scan launches of another stream: a workgroup that
+   * asks for more LDS than a scan workgroup leaves on its CU lands on a CU without one (engine.py sets 96 / 64 for such steps). */
+  MGR_TUNE_CTC_CHAIN_LDS_KIB = 20,
+  MGR_TUNE_CTC_FRAME_LDS_KIB = 21,
+  MGR_TUNE_COUNT = 24
+};
 int mgr_tune(mgr_ctx* ctx, int key, int value);
 int mgr_tune_get(mgr_ctx* ctx, int key, int* value);   /* what a key is set to (a host of the library that lays out buffers by it) */
 /* Health of the persistent multi-CU scans launched on this context since the last mgr_scan_status_clear: *out receives the OR
@@ -391,7 +412,7 @@ int mgr_lstm_param_grads_dropout(mgr_ctx* ctx, const float* X, int ldx, const fl
  * f16 matrix pipe with split-f16 (hi, lo) operands and f32 accumulation (k_gemm_tn_sparse16; dZ is scaled per (sample, gate
  * column) by its own largest magnitude, so its dynamic range costs nothing); then equal to mgr_lstm_param_grads_dropout to the
  * f32 tolerance instead of bit for bit.  > 0: checked on the device, f32 MFMA kernel if violated; < 0: guaranteed by the producer of
- * XT, unchecked; 0, or tune key 15 = 1: the f32 MFMA kernel. */
+ * XT, unchecked; 0, or MGR_TUNE_GEMM_F32 = 1: the f32 MFMA kernel. */
 int mgr_lstm_param_grads_dropout_wants_transposed(mgr_ctx* ctx, float drop_rate, int F);
 size_t mgr_lstm_param_grads_dropout_t_ws_bytes(int B, int T, int F, int H, int ldt);
 int mgr_lstm_param_grads_dropout_t(mgr_ctx* ctx, const float* XT, int ldt, const float* mask4, float drop_rate,

@@ -155,10 +155,31 @@ class ScanLaunchOpts(C.Structure):
 
 
 # enums of include/mgr.h (mgr_scan_launch_opts.form)
-SCAN_FORM_AUTO, SCAN_FORM_PLAIN, SCAN_FORM_PAIR, SCAN_FORM_FUSED, SCAN_FORM_FUSED_ANY = range(5)
+SCAN_FORM_AUTO, SCAN_FORM_PLAIN, SCAN_FORM_FUSED, SCAN_FORM_FUSED_ANY = 0, 1, 3, 4
 BPTT_FORM_AUTO, BPTT_FORM_TRIMMED, BPTT_FORM_YIELDING, BPTT_FORM_DIRECT, BPTT_FORM_FUSED, BPTT_FORM_FUSED_DIRECT, BPTT_FORM_SINGLE_CU = range(7)
 SEQ_NONE = 0xFFFFFFFF
 ABI_REVISION = 7
+# tune keys of include/mgr.h (mgr_tune / mgr_tune_get)
+TUNE_SCAN_PATH = 0
+TUNE_SCAN_SYNC_CHECK = 1
+TUNE_SCAN_PRINT_PLAN = 2
+TUNE_SCAN_NO_XCD_LOCAL = 3
+TUNE_SCAN_FORM = 4
+TUNE_SCAN_LDS_IMAGE = 7
+TUNE_BPTT_SPLIT_ROLE = 8
+TUNE_PROJ_DENSE = 9
+TUNE_PROJ_DENSE16_MASKED = 10
+TUNE_PROJ_WIDE_TILES = 11
+TUNE_PROJ_TS_TILE = 12
+TUNE_DENSE_VALU = 13
+TUNE_SCAN_F32_MFMA = 14
+TUNE_GEMM_F32 = 15
+TUNE_BPTT_FORM = 16
+TUNE_CTC_ONE_SAMPLE = 18
+TUNE_BPTT_SINGLE_CU = 19
+TUNE_CTC_CHAIN_LDS_KIB = 20
+TUNE_CTC_FRAME_LDS_KIB = 21
+TUNE_COUNT = 24
 
 
 def make_launch_opts(form=0, seq_out=0):

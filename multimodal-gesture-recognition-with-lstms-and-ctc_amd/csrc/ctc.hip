@@ -499,18 +499,19 @@ int mgr_ctc_loss_grad(mgr_ctx* c, const float* P, const int32_t* labels, const i
   float* LY = reinterpret_cast<float*>(ws);
   float* AL = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + ly);
   float* BE = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + ly + ab);
-  // two samples per workgroup (one chain per SIMD) from B = 2 on; tune key 18 = 1: one sample per workgroup (rounds 1 - 5)
-  const int spw = (B >= 2 && c->tune[18] == 0) ? 2 : 1;
+  // two samples per workgroup (one chain per SIMD) from B = 2 on; MGR_TUNE_CTC_ONE_SAMPLE = 1: one sample per workgroup (rounds 1 - 5)
+  const int spw = (B >= 2 && c->tune[MGR_TUNE_CTC_ONE_SAMPLE] == 0) ? 2 : 1;
   size_t lds_grad = (size_t)256 * (C + 1) * sizeof(float) + (size_t)(Lmax + 1) * sizeof(int);
   size_t lds_chains = (size_t)spw * (Lmax + 1) * sizeof(int) + 16, lds_emis = 0;
   MGR_REQUIRE(lds_grad <= 160 * 1024, "C=%d too large for the LDS occupancy tile", C);
-  // tune keys 20 / 21 = KiB of LDS the recurrence / the per-frame kernels ask for at least.  Placement: a workgroup that asks for more
-  // than a persistent scan workgroup leaves on its CU can only land on a CU without one (the engine sets them for the steps of its
-  // fused schedule, where this call runs beside 208 whole-CU scan workgroups: 96 KiB = the 32 recurrence workgroups on a CU each)
-  if (c->tune[20] > 0 && lds_chains < (size_t)c->tune[20] * 1024) lds_chains = (size_t)c->tune[20] * 1024;
-  if (c->tune[21] > 0) {
-    if (lds_grad < (size_t)c->tune[21] * 1024) lds_grad = (size_t)c->tune[21] * 1024;
-    lds_emis = (size_t)c->tune[21] * 1024;
+  // KiB of LDS the recurrence / the per-frame kernels ask for at least.  Placement: a workgroup that asks for more than a persistent
+  // scan workgroup leaves on its CU can only land on a CU without one (the engine sets them for the steps of its fused schedule,
+  // where this call runs beside 208 whole-CU scan workgroups: 96 KiB = the 32 recurrence workgroups on a CU each)
+  const int chain_kib = c->tune[MGR_TUNE_CTC_CHAIN_LDS_KIB], frame_kib = c->tune[MGR_TUNE_CTC_FRAME_LDS_KIB];
+  if (chain_kib > 0 && lds_chains < (size_t)chain_kib * 1024) lds_chains = (size_t)chain_kib * 1024;
+  if (frame_kib > 0) {
+    if (lds_grad < (size_t)frame_kib * 1024) lds_grad = (size_t)frame_kib * 1024;
+    lds_emis = (size_t)frame_kib * 1024;
   }
   if (!(c->attr_done & 128u)) {
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_emissions), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

@@ -356,8 +356,8 @@ __global__ __launch_bounds__(256, KS > 6 ? 4 : 6) void k_dense_bwd_mfma(const fl
 // any width - 1024 covers the unimodal heads, D = 600 / 1000), C <= 24, rows readable as float4, 32-bit element offsets
 static bool dense_mfma_ok(const mgr_ctx* c, const float* A, int lda, int ldo, int D, int C, size_t nframes, int maxD = 256, int maxC = 24) {
   const size_t ld = (size_t)(lda > ldo ? lda : ldo);
-  return c->tune[13] == 0 && D <= maxD && D % 4 == 0 && C <= maxC && lda % 4 == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 &&
-         nframes * (ld > (size_t)D ? ld : (size_t)D) < ((size_t)1 << 31);
+  return c->tune[MGR_TUNE_DENSE_VALU] == 0 && D <= maxD && D % 4 == 0 && C <= maxC && lda % 4 == 0 &&
+         (reinterpret_cast<uintptr_t>(A) & 15) == 0 && nframes * (ld > (size_t)D ? ld : (size_t)D) < ((size_t)1 << 31);
 }
 
 // both reductions of the backward pass in one launch (each launch of the step queues behind the resident scans)

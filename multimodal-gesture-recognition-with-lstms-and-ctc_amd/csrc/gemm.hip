@@ -1447,7 +1447,7 @@ size_t mgr_lstm_input_proj_dropout_ws_bytes(int B, int F, int H) {
 static bool sparse_proj_shape(const mgr_ctx* c, float drop_rate, int F) {
   // the per-gate K loops pay when enough features are dropped; at small F (depth-1 layers, F = 39 / 20) the GEMM is bound
   // by the Z stores and the float4 epilogue of this kernel is what helps (0.39 / 0.18 ms against 0.47 / 0.24)
-  return drop_rate >= 0.3f && F >= 16 && F <= SP_MAXF && c->tune[9] == 0;
+  return drop_rate >= 0.3f && F >= 16 && F <= SP_MAXF && c->tune[MGR_TUNE_PROJ_DENSE] == 0;
 }
 
 int mgr_lstm_input_proj_dropout_wants_transposed(mgr_ctx* c, float drop_rate, int F) {
@@ -1471,11 +1471,11 @@ static int input_proj_dropout_impl(mgr_ctx* c, const float* X, int ldx, bool tra
   // the PRODUCER of XT guarantees (mgr.h): no check
   const bool trusted = x_absmax < 0.f;
   const float xb = fabsf(x_absmax);
-  // split-f16 kernel (tune key 15 = 1: never): transposed input with a bound on |X|, a drop rate that bounds the mask factor
-  const bool f16 = transposed && xb > 0.f && xb < 1.0e30f && drop_rate < 0.99f && c->tune[15] == 0;
-  // dense K loop with the mask as a factor (k_gemm_nn_dense16): where there is no mask (inference); tune key 10 = 2: always.  With a
-  // mask the per-gate K loops over the kept features are faster (audio depth 2: 1.99 against 2.28 ms)
-  const bool dense = f16 && (!mask4 || c->tune[10] == 2);
+  // split-f16 kernel (MGR_TUNE_GEMM_F32 = 1: never): transposed input with a bound on |X|, a drop rate that bounds the mask factor
+  const bool f16 = transposed && xb > 0.f && xb < 1.0e30f && drop_rate < 0.99f && c->tune[MGR_TUNE_GEMM_F32] == 0;
+  // dense K loop with the mask as a factor (k_gemm_nn_dense16): where there is no mask (inference); MGR_TUNE_PROJ_DENSE16_MASKED = 2:
+  // always.  With a mask the per-gate K loops over the kept features are faster (audio depth 2: 1.99 against 2.28 ms)
+  const bool dense = f16 && (!mask4 || c->tune[MGR_TUNE_PROJ_DENSE16_MASKED] == 2);
   MGR_REQUIRE(mask4 || transposed, "a projection without a dropout mask is only handled from the transposed copy");
   unsigned* gate = (f16 && !trusted) ? wmax + 1 : nullptr;
   const bool lists = !dense || gate;   // the kept-feature lists: what every kernel but the dense one walks (no mask: all features)
@@ -1491,10 +1491,10 @@ static int input_proj_dropout_impl(mgr_ctx* c, const float* X, int ldx, bool tra
     const int wgs = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     hipLaunchKernelGGL(k_gate_major, dim3(wgs), dim3(256), 0, s, Wp, Wg, F, H, wmax);
   }
-  // 128-unit tiles (tune key 11 = 2) are faster alone (audio L2 2.77 against 3.03 ms) but slower in the training step
+  // 128-unit tiles (MGR_TUNE_PROJ_WIDE_TILES = 2) are faster alone (audio L2 2.77 against 3.03 ms) but slower in the training step
   // (39.7 against 38.5 ms/step): a 512-thread workgroup needs two free wave slots on all four SIMDs of a CU at once and
   // gets in the way of the BPTT scan and the small kernels of the other stream
-  const bool wide = c->tune[11] == 2 && !transposed;
+  const bool wide = c->tune[MGR_TUNE_PROJ_WIDE_TILES] == 2 && !transposed;
   const int tu = wide ? 128 : 64;
   const int ntiles = ((H + tu - 1) / tu) * ((((T + SP_TM - 1) / SP_TM) * B + 7) / 8) * 8;   // (row tiles padded to the 8 XCDs)
   if (f16) {
@@ -1692,11 +1692,11 @@ static int param_grads_dropout_impl(mgr_ctx* c, const float* X, int ldx, const f
     if (XT) {
       float* dZT = reinterpret_cast<float*>(w);   // [B][4H][ldt]
       w += mgr_align_up((size_t)B * 4 * H * ldt * sizeof(float), 256);
-      // split-f16 kernel (tune key 15 = 1: never): a bound on |X| (stated: checked on the device, f32 kernel if violated; negative:
+      // split-f16 kernel (MGR_TUNE_GEMM_F32 = 1: never): a bound on |X| (stated: checked on the device, f32 kernel if violated; negative:
       // guaranteed by the producer of XT), whole stages of 32 time steps in the padded rows
       const bool trusted = x_absmax < 0.f;
       const float xb = fabsf(x_absmax);
-      const bool f16 = xb > 0.f && xb < 1.0e30f && c->tune[15] == 0 && ldt >= (T + 31) / 32 * 32;
+      const bool f16 = xb > 0.f && xb < 1.0e30f && c->tune[MGR_TUNE_GEMM_F32] == 0 && ldt >= (T + 31) / 32 * 32;
       unsigned* zmax = reinterpret_cast<unsigned*>(w);   // [B][4H] largest |dZ| of a (sample, gate column), + the gate word
       unsigned* gate = (f16 && !trusted) ? zmax + (size_t)B * 4 * H : nullptr;
       if (f16) MGR_HIP(hipMemsetAsync(zmax, 0, ((size_t)B * 4 * H + 1) * sizeof(unsigned), s));
@@ -1728,7 +1728,7 @@ static int param_grads_dropout_impl(mgr_ctx* c, const float* X, int ldx, const f
 }
 
 static bool sparse_dw_shape(mgr_ctx* c, const float* mask4, float drop_rate, int F) {
-  return mask4 && drop_rate >= 0.3f && F >= 128 && c->tune[9] == 0;
+  return mask4 && drop_rate >= 0.3f && F >= 128 && c->tune[MGR_TUNE_PROJ_DENSE] == 0;
 }
 
 int mgr_lstm_param_grads_dropout(mgr_ctx* c, const float* X, int ldx, const float* mask4, float drop_rate, const float* Hs,
@@ -1744,7 +1744,7 @@ int mgr_lstm_param_grads_dropout(mgr_ctx* c, const float* X, int ldx, const floa
 }
 
 int mgr_lstm_param_grads_dropout_wants_transposed(mgr_ctx* c, float drop_rate, int F) {
-  return (c && drop_rate >= 0.3f && F >= 128 && c->tune[9] == 0) ? 1 : 0;
+  return (c && drop_rate >= 0.3f && F >= 128 && c->tune[MGR_TUNE_PROJ_DENSE] == 0) ? 1 : 0;
 }
 
 size_t mgr_lstm_param_grads_dropout_t_ws_bytes(int B, int T, int F, int H, int ldt) {

@@ -699,9 +699,10 @@ int mgr_lstm_input_proj_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const f
       c->planes[free_slot] = mgr_ctx::PlaneEntry{Wp, ws, F, H};
     }
   }
-  // 128-unit tiles (8 waves, one workgroup per CU) where they waste little of their width; tune key 12: 1 = always 64, 2 = always 128
+  // 128-unit tiles (8 waves, one workgroup per CU) where they waste little of their width; MGR_TUNE_PROJ_TS_TILE: 1 = always 64,
+  // 2 = always 128
   const int waste128 = (H + 127) / 128 * 128 - H, waste64 = (H + 63) / 64 * 64 - H;
-  const bool wide = c->tune[12] == 2 || (c->tune[12] == 0 && waste128 - waste64 <= H / 8);
+  const bool wide = c->tune[MGR_TUNE_PROJ_TS_TILE] == 2 || (c->tune[MGR_TUNE_PROJ_TS_TILE] == 0 && waste128 - waste64 <= H / 8);
   const int tu = wide ? 128 : 64;
   const int ntiles = ((H + tu - 1) / tu) * ((((T + PS_TM - 1) / PS_TM) * B + 7) / 8) * 8;
   if (wide)
@@ -800,7 +801,7 @@ int mgr_lstm_param_grads_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const 
     const int grid2 = 8 * ((B + 7) / 8) * 4 * ((Hp32 + DW_BM - 1) / DW_BM) * ((H + DW_BN - 1) / DW_BN);
     MGR_HIP(hipMemsetAsync(words2, 0, 2 * sizeof(unsigned), s));
     hipLaunchKernelGGL(k_lists32, dim3(4 * B), dim3(64), 0, s, (const float*)nullptr, H, Hp32, lists2, kcnt2, kpos2, words2 + 1);
-    if (c->tune[12] == 1)
+    if (c->tune[MGR_TUNE_PROJ_TS_TILE] == 1)
       hipLaunchKernelGGL(k_dw_split<4>, dim3(grid2), dim3(256), 3 * DW_STAGE, s, reinterpret_cast<const char*>(HsT), ldt, lists2, kcnt2, words2 + 1,
                          reinterpret_cast<const char*>(dZS), zmax, P2, B, T, Hp32, H, H);
     else
@@ -810,8 +811,9 @@ int mgr_lstm_param_grads_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const 
     hipLaunchKernelGGL(k_dw_gather32, dim3((int)((n2 + 255) / 256 < 4096 ? (n2 + 255) / 256 : 4096)), dim3(256), 0, s, P2, kpos2, dUp, B, H, Hp32, H);
   }
   const int grid = 8 * ((B + 7) / 8) * 4 * ((Fp32 + DW_BM - 1) / DW_BM) * ((H + DW_BN - 1) / DW_BN);
-  // tune key 12 (the tile switch of the projection): 1 = the 4-wave form, which fits on a CU beside a workgroup of a persistent scan
-  if (c->tune[12] == 1)
+  // MGR_TUNE_PROJ_TS_TILE (the tile switch of the projection): 1 = the 4-wave form, which fits on a CU beside a workgroup of a
+  // persistent scan
+  if (c->tune[MGR_TUNE_PROJ_TS_TILE] == 1)
     hipLaunchKernelGGL(k_dw_split<4>, dim3(grid), dim3(256), 3 * DW_STAGE, s, reinterpret_cast<const char*>(XS), ldt, lists, kcnt, words + 1,
                        reinterpret_cast<const char*>(dZS), zmax, P, B, T, Fp32, F, H);
   else

@@ -170,7 +170,7 @@ static int layout_classes(int njobs, const bool* use, SameFn same, SizeFn G_of, 
 }
 
 static int check_launch_status(mgr_ctx* c, unsigned* status, const char* what) {
-  unsigned st = 0;   // tune key 1: synchronous give-up check (tests)
+  unsigned st = 0;   // MGR_TUNE_SCAN_SYNC_CHECK: synchronous give-up check (tests)
   MGR_HIP(hipMemcpyAsync(&st, status, sizeof(st), hipMemcpyDeviceToHost, mgr_stream(c)));
   MGR_HIP(hipStreamSynchronize(mgr_stream(c)));
   MGR_REQUIRE(st == 0, "%s: a bounded spin gave up (status %u)", what, st);
@@ -181,6 +181,8 @@ extern "C" {
 
 int mgr_tune(mgr_ctx* c, int key, int value) {
   MGR_REQUIRE(c && key >= 0 && key < MGR_TUNE_COUNT, "bad tune key");
+  MGR_REQUIRE(!(key == MGR_TUNE_SCAN_FORM && value == 2), "tune key %d = 2: the pair form of the scan is retired", key);
+  MGR_REQUIRE(key != 17 || value == 0, "tune key 17 = %d: the fused scan form whose halves gather alone is retired", value);
   c->tune[key] = value;
   return 0;
 }
@@ -253,9 +255,10 @@ int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, 
   unsigned* seq_out;
   read_opts(opts, &form, &seq_out);
   MGR_REQUIRE(form >= MGR_SCAN_FORM_AUTO && form <= MGR_SCAN_FORM_FUSED_ANY, "unknown scan form %d", form);
+  MGR_REQUIRE(form != 2, "scan form 2 (the pair form) is retired");
   if (seq_out) *seq_out = MGR_SEQ_NONE;   // (until a launch of this call enters the residency ledger)
-  // the form of the split-f16 K-split launches: the caller's, or tune key 4 (0 plain, 2 pair, 3 fused)
-  const int key4 = form == MGR_SCAN_FORM_AUTO ? c->tune[4] : form == MGR_SCAN_FORM_PLAIN ? 0 : form == MGR_SCAN_FORM_FUSED_ANY ? 3 : form;
+  // the form of the split-f16 K-split launches: the caller's, or MGR_TUNE_SCAN_FORM (3 fused, anything else plain)
+  const bool want_fused = form == MGR_SCAN_FORM_AUTO ? c->tune[MGR_TUNE_SCAN_FORM] == MGR_SCAN_FORM_FUSED : form >= MGR_SCAN_FORM_FUSED;
   const bool fused_any = form == MGR_SCAN_FORM_FUSED_ANY;
   for (int i = 0; i < njobs; ++i) {
     const mgr_scan_job& j = jobs[i];
@@ -288,41 +291,19 @@ int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, 
     char* base = w;
     w += kScanHdrBytes;
     // K-split launches (every job a 4-wave, one-tile-per-wave cluster with an exchange) lay their clusters out XCD-locally
-    // (tune key 3 = 1 turns that off); the table of workgroup XCD ids lives in the launch header
+    // (MGR_TUNE_SCAN_NO_XCD_LOCAL = 1 turns that off); the table of workgroup XCD ids lives in the launch header
     // the K-split step addresses Z and the residual input with 32-bit byte offsets per lane (LDS-DMA prefetch): launches with a
     // larger tensor take the LDS-image step
-    bool ks_ok = c->tune[7] == 0;
+    bool ks_ok = c->tune[MGR_TUNE_SCAN_LDS_IMAGE] == 0;
     for (int i = 0; i < njobs && ks_ok; ++i) {
       if (!P.cluster[i]) continue;
       const mgr_scan_job& j = jobs[i];
       const size_t zb = (size_t)j.B * j.T * 4 * j.H * sizeof(float), rb = j.R ? (size_t)j.B * j.T * j.ldr * sizeof(float) : 0;
       ks_ok = zb < ((size_t)1 << 32) && rb < ((size_t)1 << 32);
     }
-    // Pair form of the split-f16 K-split step (lstm_cluster.hip, cluster_run_k16p): two 16-sample groups per workgroup, ONE workgroup
-    // per CU (config F's encoder depths: 204 workgroups instead of 408).  Bit-identical, tested - and NOT the default: measured 3.5 us
-    // per pair of steps against 2.2 for the two-workgroups-per-CU launch (one wave runs both groups' instruction streams one after the
-    // other; two waves per SIMD interleave them), 30.9 against 21.5 ms per training step (profiles/r05_scan_probes.txt).
-    // tune key 4: 2 = take it whenever the launch qualifies.
-    int nbg16[MGR_MAX_SCAN_JOBS];
-    for (int i = 0; i < njobs; ++i) nbg16[i] = P.cluster[i] ? P.nbg[i] : 0;
-    bool pair = ks_ok && P.exchange && c->tune[14] == 0 && key4 == 2;
-    {
-      int unpaired = 0, most = 0;
-      for (int i = 0; i < njobs && pair; ++i) {
-        if (!P.cluster[i]) continue;
-        pair = P.cfg[i].nw == 4 && P.cfg[i].tpw == 1 && P.G[i] > 1 && mgr_cluster_ks_supported(jobs[i].H / 4);
-        unpaired += P.G[i] * P.nbg[i];
-        most = P.nbg[i] > most ? P.nbg[i] : most;
-      }
-      pair = pair && most >= 2;
-      (void)unpaired;
-      if (pair)
-        for (int i = 0; i < njobs; ++i)
-          if (P.cluster[i]) P.nbg[i] = (P.nbg[i] + 1) / 2;     // clusters of the job from here on
-    }
-    // Fused form (lstm_cluster.hip, k_scan_cluster_k16f): 8-wave workgroups that run TWO unit groups of their cluster, one workgroup
-    // per CU (config F's encoder depths: 208 workgroups on 208 CUs, 48 CUs left to the other stream).  tune key 4: 3.
-    bool fused = !pair && ks_ok && P.exchange && c->tune[14] == 0 && key4 == 3 && c->tune[3] == 0;
+    // Fused form (lstm_cluster.hip, k_scan_cluster_k16fs): 8-wave workgroups that run TWO unit groups of their cluster, one workgroup
+    // per CU (config F's encoder depths: 208 workgroups on 208 CUs, 48 CUs left to the other stream).
+    bool fused = ks_ok && P.exchange && c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0 && want_fused && c->tune[MGR_TUNE_SCAN_NO_XCD_LOCAL] == 0;
     for (int i = 0; i < njobs && fused; ++i) {
       if (!P.cluster[i]) continue;
       fused = P.cfg[i].nw == 4 && P.cfg[i].tpw == 1 && P.G[i] > 1 && mgr_cluster_ks_supported(jobs[i].H / 4);
@@ -334,7 +315,7 @@ int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, 
       fused = fused && (fused_any || unf > c->cu_count);
     }
     auto members = [&](int i) { return fused ? (P.G[i] + 1) / 2 : P.G[i]; };   // workgroups per cluster
-    bool xcd = c->tune[3] == 0 && ks_ok && P.exchange;
+    bool xcd = c->tune[MGR_TUNE_SCAN_NO_XCD_LOCAL] == 0 && ks_ok && P.exchange;
     {
       int tot = 0, live_x = 0;
       for (int i = 0; i < njobs && xcd; ++i) {
@@ -356,7 +337,7 @@ int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, 
           tot += members(i) * ((clusters + 7) / 8 * 8);
           live_x += members(i) * clusters;
         }
-        xcd = live_x <= ((pair || fused) ? 1 : 2) * c->cu_count && tot <= 2 * c->cu_count && (size_t)tot * sizeof(unsigned) <= kScanHdrBytes - 256;
+        xcd = live_x <= (fused ? 1 : 2) * c->cu_count && tot <= 2 * c->cu_count && (size_t)tot * sizeof(unsigned) <= kScanHdrBytes - 256;
       }
     }
     int cb[MGR_MAX_SCAN_JOBS], cn[MGR_MAX_SCAN_JOBS], c0[MGR_MAX_SCAN_JOBS], cr[MGR_MAX_SCAN_JOBS];
@@ -380,17 +361,15 @@ int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, 
       cj.Z = j.Z; cj.Up = j.Up; cj.Y = j.Y; cj.R = j.R; cj.G = j.gates; cj.Cs = j.cs;
       cj.ldy = j.ldy; cj.ldr = j.ldr; cj.B = j.B; cj.T = j.T; cj.H = j.H; cj.reverse = j.reverse;
       cj.ks = ks; cj.tpw = P.cfg[i].tpw; cj.nw = P.cfg[i].nw;
-      cj.G_ = P.G[i]; cj.nbg = P.nbg[i]; cj.nbg16 = nbg16[i];
+      cj.G_ = P.G[i]; cj.nbg = P.nbg[i];
       cj.cls_begin = cb[i]; cj.cls_nclusters = cn[i]; cj.cls_cluster0 = c0[i]; cj.cls_rot = cr[i];
       cj.xbuf = reinterpret_cast<float*>(w);
-      w += mgr_align_up((size_t)nbg16[i] * 2 * img * sizeof(float), 256);
+      w += mgr_align_up((size_t)P.nbg[i] * 2 * img * sizeof(float), 256);
     }
-    L.pair = pair ? 1 : 0;
     L.fused = fused ? 1 : 0;
     L.live_wgs = live;
-    // tune key 7: 0 = K-split step for one-tile-per-wave clusters, 1 = LDS-image step for every cluster
     L.ksplit = ks_ok ? 1 : 0;
-    L.split16 = c->tune[14] == 0;   // tune key 14: 1 = f32 MFMA in the K-split step
+    L.split16 = c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0;
     // transposed outputs: the K-split kernel writes them itself; everything else gets a transpose behind the scans (below)
     if (mgr_cluster_uses_ks(L, P.exchange)) {
       int k = 0;
@@ -401,7 +380,7 @@ int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, 
         yt_done[i] = jobs[i].YT != nullptr;
       }
     }
-    if (c->tune[2]) {  // tune key 2: print the plan
+    if (c->tune[MGR_TUNE_SCAN_PRINT_PLAN]) {
       for (int i = 0; i < L.njobs; ++i)
         fprintf(stderr, "[mgr scan plan] job %d: H=%d ks=%d nw=%d tpw=%d G=%d nbg=%d wg_begin=%d\n", i, L.job[i].H,
                 L.job[i].ks, L.job[i].nw, L.job[i].tpw, L.job[i].G_, L.job[i].nbg, L.job[i].cls_begin);
@@ -443,7 +422,7 @@ int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, 
   }
   r = mgr_prof_end(c, family);
   if (r) return r;
-  if (status && c->tune[1]) return check_launch_status(c, status, "cluster scan");
+  if (status && c->tune[MGR_TUNE_SCAN_SYNC_CHECK]) return check_launch_status(c, status, "cluster scan");
   return 0;
 }
 
@@ -470,7 +449,7 @@ int mgr_lstm_scan_bwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jo
   if (seq_out) *seq_out = MGR_SEQ_NONE;
   const bool want_fused = form == MGR_BPTT_FORM_FUSED || form == MGR_BPTT_FORM_FUSED_DIRECT;
   // 0 trimmed, 1 yielding, 2 direct gather (the fused forms: the trimmed step / the direct gather)
-  const int key16 = form == MGR_BPTT_FORM_AUTO ? c->tune[16]
+  const int key16 = form == MGR_BPTT_FORM_AUTO ? c->tune[MGR_TUNE_BPTT_FORM]
                     : (form == MGR_BPTT_FORM_FUSED || form == MGR_BPTT_FORM_SINGLE_CU) ? 0 : form == MGR_BPTT_FORM_FUSED_DIRECT ? 2 : form - 1;
   MGR_REQUIRE(ws && ws_bytes >= mgr_lstm_scan_bwd_multi_ws_bytes(njobs, jobs), "workspace too small");
   for (int i = 0; i < njobs; ++i) {
@@ -482,9 +461,11 @@ int mgr_lstm_scan_bwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jo
   int r = mgr_prof_begin(c, MGR_K_SCAN_BWD);
   if (r) return r;
   const int path = c->tune[MGR_TUNE_SCAN_PATH];
-  // The single-CU split-f16 form (lstm_cu_bwd.hip): asked for by the caller (or tune key 19 = 1), taken when the jobs are the directions
-  // of ONE narrow layer (same shape, 16 < H <= 128) and the f16 matrix pipe is in use; no inter-CU exchange, no ledger entry
-  if ((form == MGR_BPTT_FORM_SINGLE_CU || (form == MGR_BPTT_FORM_AUTO && c->tune[19] == 1)) && c->tune[14] == 0 && (path == 0 || path == 3)) {
+  // The single-CU split-f16 form (lstm_cu_bwd.hip): asked for by the caller (or MGR_TUNE_BPTT_SINGLE_CU = 1), taken when the jobs are
+  // the directions of ONE narrow layer (same shape, 16 < H <= 128) and the f16 matrix pipe is in use; no inter-CU exchange, no ledger
+  // entry
+  if ((form == MGR_BPTT_FORM_SINGLE_CU || (form == MGR_BPTT_FORM_AUTO && c->tune[MGR_TUNE_BPTT_SINGLE_CU] == 1)) &&
+      c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0 && (path == 0 || path == 3)) {
     r = mgr_scan_bwd_cu16_multi(c, njobs, jobs);
     if (r < 0) return r;
     if (r == 1) {
@@ -524,8 +505,9 @@ int mgr_lstm_scan_bwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jo
   int cb[MGR_MAX_SCAN_JOBS], cn[MGR_MAX_SCAN_JOBS], c0[MGR_MAX_SCAN_JOBS], cr[MGR_MAX_SCAN_JOBS];
   auto same_h = [&](int a, int b) { return jobs[a].H == jobs[b].H; };
   auto g_of = [&](int a) { return (jobs[a].H + 15) / 16; };
-  // XCD-local layout (octets of clusters) where the padded grid still fits the chip and the header's table; tune key 3 = 1: off
-  bool xcd = c->tune[3] == 0;
+  // XCD-local layout (octets of clusters) where the padded grid still fits the chip and the header's table
+  // (MGR_TUNE_SCAN_NO_XCD_LOCAL = 1: off)
+  bool xcd = c->tune[MGR_TUNE_SCAN_NO_XCD_LOCAL] == 0;
   int grid = layout_classes(njobs, use_cluster, same_h, g_of, nbg, cb, cn, c0, xcd, cr);
   if (xcd && (grid > 2 * c->cu_count || (size_t)grid * sizeof(unsigned) > kScanHdrBytes - 256)) {
     xcd = false;
@@ -534,7 +516,8 @@ int mgr_lstm_scan_bwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jo
   // Fused form (lstm_cluster_bwd.hip, k_scan_cluster_bwd16_f): asked for by the caller, taken when every job of the launch qualifies -
   // the same clusters with ceil(G / 2) eight-wave members, a CU each
   bool fused = want_fused && xcd;
-  for (int i = 0; i < njobs && fused; ++i) fused = use_cluster[i] && jobs[i].H > 16 && jobs[i].H <= 128 && c->tune[14] == 0;
+  for (int i = 0; i < njobs && fused; ++i)
+    fused = use_cluster[i] && jobs[i].H > 16 && jobs[i].H <= 128 && c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0;
   if (fused) {
     auto gr_of = [&](int a) { return (g_of(a) + 1) / 2; };
     const int gridf = layout_classes(njobs, use_cluster, same_h, gr_of, nbg, cb, cn, c0, true, cr);
@@ -612,7 +595,7 @@ int mgr_lstm_scan_bwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jo
   }
   r = mgr_prof_end(c, MGR_K_SCAN_BWD);
   if (r) return r;
-  if (L.njobs > 0 && c->tune[1]) return check_launch_status(c, status, "cluster BPTT");
+  if (L.njobs > 0 && c->tune[MGR_TUNE_SCAN_SYNC_CHECK]) return check_launch_status(c, status, "cluster BPTT");
   return 0;
 }
 

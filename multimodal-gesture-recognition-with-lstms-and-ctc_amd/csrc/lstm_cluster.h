@@ -44,8 +44,7 @@ struct ClusterJob {
   int ldy, ldr, B, T, H, reverse;
   int ks, tpw, nw;  // k-steps (H/4), tiles per wave, active waves per workgroup
   int G_;           // workgroups per cluster (one cluster = one 16-sample batch group)
-  int nbg;          // clusters of this job: 16-sample batch groups, or (ClusterLaunch::pair) pairs of them
-  int nbg16;        // 16-sample batch groups
+  int nbg;          // clusters of this job: 16-sample batch groups
   // jobs with identical geometry form a CLASS that shares one contiguous workgroup range: cluster `cl` of the class
   // owns workgroups [cls_begin + cl*G_, +G_); a job's batch group bg is cluster cls_cluster0 + bg
   int cls_begin, cls_nclusters, cls_cluster0;
@@ -56,11 +55,11 @@ struct ClusterLaunch {
   ClusterCommon cm;
   int njobs;
   int ksplit;        // one-tile-per-wave clusters use the K-split step (cluster_run_ks: register-direct gather); 0 = LDS-image step
-  int split16;       // K-split launches: f16 (hi, lo) operands on the f16 matrix pipe (cluster_run_k16; tune key 14 = 1: f32 MFMA step)
+  int split16;       // K-split launches: f16 (hi, lo) operands on the f16 matrix pipe (cluster_run_k16; MGR_TUNE_SCAN_F32_MFMA = 1:
+                     // f32 MFMA step)
   int live_wgs;      // workgroups of the grid that run a cluster (the others are empty ids of the octet layout)
-  int pair;          // split16 K-split launches: every workgroup runs TWO 16-sample groups (cluster_run_k16p: one workgroup per CU)
   int fused;         // split16 K-split launches: every workgroup (8 waves, a CU of its own) runs TWO unit groups of its cluster; the job
-                     // table's cls_* fields then count ceil(G_ / 2) members per cluster (k_scan_cluster_k16f)
+                     // table's cls_* fields then count ceil(G_ / 2) members per cluster (k_scan_cluster_k16fs)
   int xcd_local;     // K-split launches: clusters are laid out on workgroup ids congruent mod 8 (one XCD under the dispatcher's
                      // round-robin); a cluster that FINDS all its members on one XCD publishes with plain stores into that L2
   ClusterJob job[MGR_MAX_SCAN_JOBS];
@@ -100,7 +99,8 @@ bool mgr_cluster_bwd_supported(int H);
 bool mgr_cluster_bwd_fusable(const mgr_ctx* c, const ClusterBwdLaunch& L);   // L.xcd_local, the jobs' H / G_ filled in
 size_t mgr_cluster_bwd_img_floats(int H);
 void mgr_cluster_bwd_geometry(const mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs, int* waves, int* per_cu);
-int mgr_cluster_bwd_launch(mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs, int form16);   // form16: 0 trimmed, 1 yielding, 2 direct (mgr.h, tune key 16)
+// form16: 0 trimmed, 1 yielding, 2 direct (mgr.h, MGR_TUNE_BPTT_FORM)
+int mgr_cluster_bwd_launch(mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs, int form16);
 
 // ---- admission of persistent launches (lstm.hip): co-residency by construction across the streams of a context
 int mgr_persist_admit(mgr_ctx* c, int wgs, int waves_per_wg, int per_cu, int fused, unsigned* seq_out);

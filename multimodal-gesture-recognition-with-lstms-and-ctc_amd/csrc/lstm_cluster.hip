@@ -586,7 +586,7 @@ __device__ __forceinline__ void cluster_run_ks(const ClusterJob& jb, const Clust
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Split-f16 variant of the K-split step (round 4; the default - tune key 14 = 1 keeps the f32 MFMA step above).
+// Split-f16 variant of the K-split step (round 4; the default - MGR_TUNE_SCAN_F32_MFMA = 1 keeps the f32 MFMA step above).
 //
 // The recurrence h_{t-1} U is an f32 product; v_mfma_f32_16x16x4_f32 delivers it at 64 FLOP per cycle and SIMD, the f16 form
 // v_mfma_f32_16x16x32_f16 at 1024.  Here every f32 operand x travels as TWO f16 values, x*s = hi + lo (s a power of two, hi =
@@ -652,25 +652,22 @@ extern "C" int mgr_debug_stamps(unsigned long long* out) {
 #else
 #define KSTAMP(i, dep) do { } while (0)
 #endif
-// FUSED (round 5, k_scan_cluster_k16f): the workgroup has 512 threads and runs TWO unit groups of one cluster - threads 0..255 the
-// member 2 j, threads 256..511 the member 2 j + 1 - each through this function with its own half of the LDS; they share the CU and
-// the barriers (the same count in both: one in the prologue, one per step), nothing else.
-// SHARE_TG >= 0 (round 6, k_scan_cluster_k16fs; FUSED only): the two halves of the workgroup belong to the SAME cluster, so wave w of
-// half 0 and wave w of half 1 need the same K-blocks of the same h image - and used to fetch and verify them twice, 64 KiB per CU and
-// step through the L2.  Now half 0 fetches and verifies the first ceil(NBW / 2) K-blocks of the wave's range, half 1 the rest; both
-// leave what they verified in a shared LDS image (xs: [wave][K-block][hi | lo][64 lanes] 16 bytes), ONE more workgroup barrier, and
-// each reads the other's blocks from there: half the L2 gather traffic and half the verification chain per wave.  Same operands, same
-// MFMA order: bit-identical.  The image is single-buffered: a wave writes step s + 1's blocks behind the step-s barrier, which its
-// partner reaches only after its MFMAs consumed step s's.  A unit group beyond G (odd G) runs as a member WITHOUT valid cells - it
-// still owes its partner half of the image.
-template <int NBW, bool FUSED = false, int SHARE_TG = -1>   // K-blocks (of 32 units) per wave: H <= 128 * NBW
+// HALF >= 0 (the fused form, k_scan_cluster_k16fs): the workgroup has 512 threads and runs TWO unit groups of one cluster - threads
+// 0..255 (HALF 0) the member 2 j, threads 256..511 (HALF 1) the member 2 j + 1 - each through this function with its own half of the
+// LDS; they share the CU and the barriers (the same count in both halves).  Wave w of half 0 and wave w
+// of half 1 need the same K-blocks of the same h image, so they share ONE gather: half 0 fetches and verifies the first ceil(NBW / 2)
+// K-blocks of the wave's range, half 1 the rest; both leave what they verified in a shared LDS image (xs: [wave][K-block][hi | lo]
+// [64 lanes] 16 bytes), ONE more workgroup barrier, and each reads the other's blocks from there: half the L2 gather traffic and half
+// the verification chain per wave.  Same operands, same MFMA order as the 4-wave form (HALF < 0): bit-identical.  The image is
+// single-buffered: a wave writes step s + 1's blocks behind the step-s barrier, which its partner reaches only after its MFMAs
+// consumed step s's.  A unit group beyond G (odd G) runs as a member WITHOUT valid cells - it still owes its partner half of the image.
+template <int NBW, int HALF = -1>   // K-blocks (of 32 units) per wave: H <= 128 * NBW
 __device__ __forceinline__ void cluster_run_k16(const ClusterJob& jb, const ClusterCommon& cm, int bg, int ug, float* smem, bool fast,
                                                 float* xs = nullptr) {
   static_assert(NBW >= 1 && NBW <= 4, "1..4 K-blocks per wave (H <= 512)");
-  static_assert(SHARE_TG < 0 || FUSED, "the shared gather is a property of the fused form");
-  constexpr bool SHARE = SHARE_TG >= 0;
+  constexpr bool FUSED = HALF >= 0;
   constexpr int NA = (NBW + 1) / 2;                       // K-blocks half 0 fetches; half 1: the other NBW - NA
-  constexpr int MLO = !SHARE ? 0 : (SHARE_TG == 0 ? 0 : NA), MHI = !SHARE ? NBW : (SHARE_TG == 0 ? NA : NBW);   // this wave fetches [MLO, MHI)
+  constexpr int MLO = !FUSED ? 0 : (HALF == 0 ? 0 : NA), MHI = !FUSED ? NBW : (HALF == 0 ? NA : NBW);   // this wave fetches [MLO, MHI)
   unsigned* status = cm.status;
   const int tid = FUSED ? (int)(threadIdx.x & 255u) : (int)threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0..3
@@ -835,7 +832,7 @@ __device__ __forceinline__ void cluster_run_k16(const ClusterJob& jb, const Clus
         if (failed) break;
       }
     }
-    if constexpr (SHARE) {
+    if constexpr (FUSED) {
       if (step > 0) {   // (workgroup-uniform: every wave of both halves takes the barrier, whatever its own gather did)
         u32x4* ximg = reinterpret_cast<u32x4*>(xs) + wave * (NBW * 2 * 64) + lane;
 #pragma unroll
@@ -957,302 +954,6 @@ __device__ __forceinline__ void cluster_run_k16(const ClusterJob& jb, const Clus
     mgr_mark_sample(cm, b);
   }
   if (ytrow) ks_zero_tail(ytrow, T, jb.ldt, yt_split);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// PAIR form of the split-f16 K-split step (round 5): ONE workgroup per CU.  A workgroup holds its 16 hidden units' slice of U once and
-// runs TWO 16-sample batch groups through it (cluster `bg` of a paired job owns the groups 2 bg and 2 bg + 1; an odd group count
-// leaves the last cluster with one).  Same exchange images (one per 16-sample group), same layouts, same arithmetic and summation order
-// as cluster_run_k16 - bit-identical results - but per step ONE round of gathers for both groups (one L2 round trip), one barrier,
-// and half the workgroups: the encoder launch of config F is 204 workgroups instead of 408, no CU holds two of them (the pace of a
-// cluster was set by its members that shared their CU with a workgroup of another cluster - uneven by construction), 52 CUs stay free
-// and every scan CU keeps one wave slot per SIMD and ~50 KiB of LDS for the other stream's kernels.
-constexpr int K16P_PER_S = 4 * K16_TILE + 4 * KS_STG * 64 + 4 * 2 * 256 + 4 * 2 * 64;
-constexpr int K16P_LDS_FLOATS = 2 * K16P_PER_S + 16;
-
-template <int NBW>
-__device__ __forceinline__ void cluster_run_k16p(const ClusterJob& jb, const ClusterCommon& cm, int bg, int ug, float* smem, bool fast) {
-  static_assert(NBW >= 1 && NBW <= 4, "1..4 K-blocks per wave (H <= 512)");
-  unsigned* status = cm.status;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0..3
-  const int H = jb.H, N = 4 * H, G = jb.G_;
-  const int NKB = (H + 31) >> 5;
-  const int IMGB = NKB * 2048;            // bytes of one exchange slot of one 16-sample group
-  const int B = jb.B, T = jb.T, reverse = jb.reverse;
-  const int om = lane & 15, okg = lane >> 4;
-  const int fn = 4 * wave + (lane >> 4), fu = lane & 15;
-  const int ns = (2 * bg + 1 < jb.nbg16) ? 2 : 1;     // 16-sample groups of this cluster (the same on every member)
-  int b[2];
-  bool bvalid[2];
-  int bc[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    b[s] = (2 * bg + s) * 16 + fn;
-    bvalid[s] = s < ns && b[s] < B;
-    bc[s] = bvalid[s] ? b[s] : B - 1;
-  }
-  const int unit = 16 * ug + fu;
-  const bool cvalid = unit < H;
-  const float* __restrict__ Z = jb.Z;
-  const float* __restrict__ Up = jb.Up;
-  const float* Rp = jb.R;
-  float *Yp = jb.Y, *Gp = jb.G, *Csp = jb.Cs;
-  int ldr = jb.ldr, ldy = jb.ldy;
-  asm volatile("" : "+s"(Rp), "+s"(Yp), "+s"(Gp), "+s"(Csp), "+s"(ldr), "+s"(ldy));   // (see cluster_run_ks)
-
-  const int qb = wave * NBW;
-  int nb = NKB - qb;
-  nb = nb < 0 ? 0 : (nb > NBW ? NBW : nb);
-  nb = __builtin_amdgcn_readfirstlane(nb);
-
-  // LDS of sample group s at smem + s K16P_PER_S: partial sums [tile] K16_TILE | staging [4 waves][KS_STG][64] | Z rings | R rings
-  float *red[2], *stg[2], *zring[2], *rring[2];
-  unsigned zring_lds[2], rring_lds[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    float* base = smem + s * K16P_PER_S;
-    red[s] = base;
-    stg[s] = base + 4 * K16_TILE + wave * (KS_STG * 64);
-    zring[s] = base + 4 * K16_TILE + 4 * KS_STG * 64 + wave * (2 * 256);
-    rring[s] = base + 4 * K16_TILE + 4 * KS_STG * 64 + 4 * 2 * 256 + wave * (2 * 64);
-    zring_lds[s] = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_float*)zring[s]);
-    rring_lds[s] = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_float*)rring[s]);
-  }
-  float* wmax = smem + 2 * K16P_PER_S;
-
-  // ---- weights (as cluster_run_k16)
-  auto uval = [&](int tt, int i, int e) -> float {
-    const int k = 32 * (qb + i) + 8 * okg + e, uu = 16 * ug + 4 * tt + (om >> 2);
-    return (k < H && uu < H) ? Up[(size_t)k * N + uu * 4 + (om & 3)] : 0.f;
-  };
-  float umax = 0.f;
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-    for (int i = 0; i < NBW; ++i)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) umax = fmaxf(umax, fabsf(uval(tt, i, e)));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) umax = fmaxf(umax, __shfl_xor(umax, o));
-  if (lane == 0) wmax[wave] = umax;
-  __syncthreads();
-  umax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-  int ex = 0;
-  if (umax > 0.f && umax < 3.0e38f) (void)frexpf(umax, &ex);
-  ex = ex < -60 ? -60 : ex;
-  const float sU = ldexpf(1.f, 15 - ex);
-  const float inv = ldexpf(1.f, ex - 30);
-  f16x8 ah[4][NBW], al[4][NBW];
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-    for (int i = 0; i < NBW; ++i)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float x = uval(tt, i, e) * sU;
-        asm volatile("" : "+v"(x));
-        const _Float16 hi = (_Float16)x;
-        ah[tt][i][e] = hi;
-        al[tt][i][e] = (_Float16)(x - (float)hi);
-      }
-
-  float* ytrow[2] = {nullptr, nullptr};
-  const bool yt_split = jb.yt_split != 0;
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-    if (jb.YT && cvalid && bvalid[s]) {
-      ytrow[s] = jb.YT + (size_t)b[s] * jb.ytb + (size_t)unit * jb.ldt;
-#pragma unroll
-      for (int i = 0; i < KS_STG; ++i) stg[s][i * 64 + lane] = 0.f;
-    }
-  // the exchange slots of the two groups are neighbours in the job's buffer: [group][slot][IMGB]
-  char* xb = reinterpret_cast<char*>(jb.xbuf) + (size_t)(2 * bg) * 2 * IMGB;
-  __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(xb, 0, ns * 2 * IMGB, 0x00020000);
-  unsigned goff[NBW];
-#pragma unroll
-  for (int i = 0; i < NBW; ++i) {
-    const int kb = qb + (i < nb ? i : 0);
-    const int half = (2 * kb + (okg >> 1) < G) ? (okg >> 1) : 0;
-    goff[i] = (unsigned)(kb * 2048 + half * 512 + (om >> 2) * 128 + (om & 3) * 32 + (okg & 1) * 16);
-  }
-  const unsigned poff = (unsigned)((ug >> 1) * 2048 + (lane & 1) * 1024 + (ug & 1) * 512 + wave * 128 + (lane >> 4) * 32 + (fu >> 1) * 4);
-
-  const int zunit = cvalid ? unit : 0;
-  unsigned zvoff[2], rvoff[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    zvoff[s] = (unsigned)(((size_t)bc[s] * T * N + (size_t)zunit * 4) * sizeof(float));
-    rvoff[s] = Rp ? (unsigned)(((size_t)bc[s] * T * ldr + zunit) * sizeof(float)) : 0u;
-  }
-  {   // Z / R of step 0 of both groups
-    const int t0 = reverse ? T - 1 : 0;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-      if (s < ns) {
-        mgr_dma_b128(Z + (size_t)t0 * N, zvoff[s], zring_lds[s]);
-        if (Rp) mgr_dma_b32(Rp + (size_t)t0 * ldr, rvoff[s], rring_lds[s]);
-      }
-  }
-  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the weight loads are retired before the time loop (see cluster_run_ks)
-
-  const int wslot = k16_wslot(om, okg);
-  const int rslot = k16_rslot(fu, fn);
-
-  float c[2] = {0.f, 0.f};
-  bool nonfinite[2] = {false, false};
-  bool failed = false;
-  unsigned rounds = 0;
-  auto tick = [&]() {
-    ++rounds;
-    if ((rounds & 255u) == 0) {
-      unsigned st;
-      asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(st) : "v"(status) : "memory");
-      if (__builtin_amdgcn_readfirstlane(st) != 0u) failed = true;
-    }
-    if (rounds > KS_ROUND_LIMIT) {
-      failed = true;
-      if (lane == 0) __hip_atomic_store(status, MGR_ST_GAVE_UP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  };
-
-  // One time step of ONE group: gather its h_{t-1} blocks, the matrix products, partial sums through LDS, barrier, cell, publish.
-  // The two groups alternate: while the peers' publishes of group s travel (publish -> L2 -> visible: the hand-off latency that a
-  // single chain waits for), this workgroup works on the other group - two barriers per pair of steps, and the partial-sum buffer of
-  // a group needs no second copy (a wave re-writes it only behind the OTHER group's barrier, which every wave reaches after it has
-  // read this one).
-  auto half_step = [&](auto sc, int step) {
-    constexpr int s = decltype(sc)::value;
-    const int t = reverse ? T - 1 - step : step;
-    f32x4 acc[4];
-    u32x4 v[2 * NBW];
-    const bool gather = step > 0 && nb > 0 && !failed;
-    if (gather) {
-      const unsigned sbase = (unsigned)(s * 2 * IMGB + ((step - 1) & 1) * IMGB);
-      const unsigned par = ((((unsigned)(step - 1)) >> 1) & 1u) ^ 1u;
-      for (;;) {
-#pragma unroll
-        for (int i = 0; i < NBW; ++i) {
-          v[2 * i] = __builtin_amdgcn_raw_buffer_load_b128(rs, goff[i], sbase, 16);              // sc1
-          v[2 * i + 1] = __builtin_amdgcn_raw_buffer_load_b128(rs, goff[i] + 1024u, sbase, 16);   // sc1
-        }
-        unsigned a_and = 0xFFFFFFFFu, a_or = 0u;
-#pragma unroll
-        for (int i = 0; i < 2 * NBW; ++i) {
-          a_and &= v[i].x & v[i].y & v[i].z & v[i].w;
-          a_or |= v[i].x | v[i].y | v[i].z | v[i].w;
-        }
-        const bool lane_fresh = par ? (a_and & 1u) != 0u : (a_or & 1u) == 0u;
-        if (__all(lane_fresh) || failed) break;
-        tick();
-        if (failed) break;
-      }
-    }
-    auto prefetch_s = [&](int st) {
-      if (st < T) {
-        const int tt2 = reverse ? T - 1 - st : st;
-        mgr_dma_b128(Z + (size_t)tt2 * N, zvoff[s], zring_lds[s] + (st & 1) * 1024);
-        if (Rp) mgr_dma_b32(Rp + (size_t)tt2 * ldr, rvoff[s], rring_lds[s] + (st & 1) * 256);
-      }
-    };
-    if (gather && !failed) {
-#pragma unroll
-      for (int i = 0; i < NBW; ++i) {
-        if (i == (NBW > 1 ? 1 : 0)) prefetch_s(step + 1);
-        const f16x8 bh = __builtin_bit_cast(f16x8, v[2 * i]), bl = __builtin_bit_cast(f16x8, v[2 * i + 1]);
-        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[tt][i], bh, i == 0 ? zero : acc[tt], 0, 0, 0);
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[tt][i], bh, acc[tt], 0, 0, 0);
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[tt][i], bl, acc[tt], 0, 0, 0);
-      }
-    } else {
-      prefetch_s(step + 1);
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) acc[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    float* rbuf = red[s];
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) *reinterpret_cast<f32x4*>(rbuf + tt * K16_TILE + (wave * 64 + wslot) * 4) = acc[tt];
-    // (Z_t / R_t of this group were fetched a pair of steps ago; what this wave may still have in flight are the DMAs just issued)
-    if (Rp)
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    const f32x4 zt = *reinterpret_cast<const f32x4*>(zring[s] + (step & 1) * 256 + lane * 4);
-    const float rt = Rp ? rring[s][(step & 1) * 64 + lane] : 0.f;
-    __syncthreads();
-    const unsigned par = (((unsigned)step >> 1) & 1u) ^ 1u;
-    unsigned packed = par | (par << 16);
-    float h = 0.f, yv = 0.f;
-    float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (cvalid) {
-      const float* mine = rbuf + rslot * 4;
-      f32x4 sum = *reinterpret_cast<const f32x4*>(mine);
-#pragma unroll
-      for (int src = 1; src < 4; ++src) sum += *reinterpret_cast<const f32x4*>(mine + src * 64 * 4);
-      f32x4 tot;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) tot[g] = fmaf(sum[g], inv, zt[g]);
-      h = mgr_cell_fwd(tot[0], tot[1], tot[2], tot[3], c[s], g4);
-      if (!(fabsf(h) < 2.f) && !nonfinite[s]) {
-        __hip_atomic_fetch_or(cm.sticky, MGR_ST_NONFINITE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        nonfinite[s] = true;
-      }
-      if (nonfinite[s]) {
-        h = 0.f;
-        c[s] = 0.f;
-      }
-      yv = nonfinite[s] ? __uint_as_float(0x7FC00000u) : h;
-      float hs = h * 32768.f;   // (the flag bits: cluster_run_k16)
-      asm volatile("" : "+v"(hs));
-      unsigned hib = (unsigned)__builtin_bit_cast(unsigned short, (_Float16)hs);
-      hib = k16_with_lsb(hib, par, hs, ~lane & 1u);
-      const float hif = (float)__builtin_bit_cast(_Float16, (unsigned short)hib);
-      float ls = hs - hif;
-      asm volatile("" : "+v"(ls));
-      unsigned lob = (unsigned)__builtin_bit_cast(unsigned short, (_Float16)ls);
-      lob = k16_with_lsb(lob, par, ls, ~lane & 1u);
-      packed = hib | (lob << 16);
-    }
-    if (step + 1 < T) {
-      const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)packed, 0xB1, 0xF, 0xF, true);
-      const unsigned w = (lane & 1) ? ((other >> 16) | (packed & 0xFFFF0000u)) : ((packed & 0xFFFFu) | (other << 16));
-      const unsigned so = (unsigned)(s * 2 * IMGB + (step & 1) * IMGB);
-      if (fast)
-        __builtin_amdgcn_raw_buffer_store_b32(w, rs, poff, so, 0);
-      else
-        __builtin_amdgcn_raw_buffer_store_b32(w, rs, poff, so, 16);  // sc1
-    }
-    if (cvalid && bvalid[s]) {
-      size_t row = (size_t)b[s] * T + t;
-      const float yo = yv + rt;
-      typedef __attribute__((address_space(1))) float gfloat;
-      typedef __attribute__((address_space(1))) f32x4 gf32x4;
-      ((gfloat*)Yp)[row * ldy + unit] = yo;
-      if (Gp) *(gf32x4*)(Gp + (row * H + unit) * 4) = (f32x4){g4.x, g4.y, g4.z, g4.w};
-      if (Csp) ((gfloat*)Csp)[row * H + unit] = c[s];
-      if (ytrow[s]) {
-        stg[s][(t & (KS_STG - 1)) * 64 + lane] = yo;
-        if (reverse ? (t & (KS_STG - 1)) == 0 : ((t & (KS_STG - 1)) == KS_STG - 1 || t == T - 1)) {
-          ks_flush_chunk(stg[s], lane, ytrow[s], t & ~(KS_STG - 1), jb.ldt, yt_split);
-#pragma unroll
-          for (int i = 0; i < KS_STG; ++i) stg[s][i * 64 + lane] = 0.f;
-        }
-      }
-    }
-  };
-  for (int step = 0; step < T; ++step) {
-    half_step(std::integral_constant<int, 0>{}, step);
-    if (ns == 2) half_step(std::integral_constant<int, 1>{}, step);   // (uniform over the cluster)
-  }
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    if (nonfinite[s]) mgr_mark_sample(cm, b[s]);
-    if (ytrow[s]) ks_zero_tail(ytrow[s], T, jb.ldt, yt_split);
-  }
 }
 
 #define CLKS_FOREACH(X) X(125) X(75) X(32) X(25)
@@ -1382,72 +1083,9 @@ __global__ __launch_bounds__(256, 2) void k_scan_cluster_k16_s(ClusterLaunch L) 
   scan_cluster_k16_body<true>(L, smem);
 }
 
-// the pair form (cluster_run_k16p): one workgroup per CU, two 16-sample groups per workgroup; same launch layout, `bg` counts pairs
-__global__ __launch_bounds__(256, 1) void k_scan_cluster_k16p(ClusterLaunch L) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  mgr_cluster_enter(L.cm);
-#define K16P_RUN(NBW) \
-  if (nbw == NBW) { cluster_run_k16p<NBW>(jb, L.cm, bg, ug, smem, same); return mgr_cluster_exit(L.cm); }
-#define K16P_DISPATCH                                    \
-  {                                                      \
-    const int nbw = (((jb.H + 31) >> 5) + 3) >> 2;       \
-    K16P_RUN(1) K16P_RUN(2) K16P_RUN(3) K16P_RUN(4)      \
-    return;                                              \
-  }
-  if (L.xcd_local) {
-    for (int k_ = 0; k_ < L.njobs; ++k_) {
-      const ClusterJob& jb = L.job[k_];
-      const int w_ = (int)blockIdx.x - jb.cls_begin, G = jb.G_;
-      if (w_ < 0 || w_ >= (jb.cls_nclusters + 7) / 8 * 8 * G) continue;
-      int cl, ug;
-      const bool same = mgr_cluster_octet(L.cm, jb.cls_begin, G, jb.cls_rot, w_, cl, ug);
-      const int bg = cl - jb.cls_cluster0;
-      if (cl >= jb.cls_nclusters || bg < 0 || bg >= jb.nbg) continue;
-      K16P_DISPATCH
-    }
-    return;
-  }
-  MGR_FOR_MY_JOB(L, jb, bg, ug) {
-    const bool same = false;
-    K16P_DISPATCH
-  }
-#undef K16P_DISPATCH
-#undef K16P_RUN
-}
-
-// the fused form: one 8-wave workgroup per CU = two unit groups (2 j, 2 j + 1) of one cluster; the launch lays out ceil(G / 2) members
-// per cluster (XCD-local octets as above); a unit group beyond G (odd G) only keeps the barrier count
-__global__ __launch_bounds__(512, 1) void k_scan_cluster_k16f(ClusterLaunch L) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  mgr_cluster_enter(L.cm);
-  const int tg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-  for (int k_ = 0; k_ < L.njobs; ++k_) {
-    const ClusterJob& jb = L.job[k_];
-    const int G = jb.G_, Gr = (G + 1) / 2;
-    const int w_ = (int)blockIdx.x - jb.cls_begin;
-    if (w_ < 0 || w_ >= (jb.cls_nclusters + 7) / 8 * 8 * Gr) continue;
-    int cl, ugr;
-    const bool same = mgr_cluster_octet(L.cm, jb.cls_begin, Gr, jb.cls_rot, w_, cl, ugr);
-    const int bg = cl - jb.cls_cluster0;
-    if (cl >= jb.cls_nclusters || bg < 0 || bg >= jb.nbg) continue;
-    const int ug = 2 * ugr + tg;
-    float* sm = smem + tg * K16_LDS_FLOATS;
-    if (ug >= G) {   // (odd G: the last workgroup's second half)
-      __syncthreads();
-      for (int step = 0; step < jb.T; ++step) __syncthreads();
-      return mgr_cluster_exit(L.cm);
-    }
-    const int nbw = (((jb.H + 31) >> 5) + 3) >> 2;
-    if (nbw == 1) cluster_run_k16<1, true>(jb, L.cm, bg, ug, sm, same);
-    else if (nbw == 2) cluster_run_k16<2, true>(jb, L.cm, bg, ug, sm, same);
-    else if (nbw == 3) cluster_run_k16<3, true>(jb, L.cm, bg, ug, sm, same);
-    else cluster_run_k16<4, true>(jb, L.cm, bg, ug, sm, same);
-    return mgr_cluster_exit(L.cm);
-  }
-}
-
-// the fused form with the SHARED gather (cluster_run_k16<.., true, half>): as k_scan_cluster_k16f, plus 2 KiB of LDS per wave and K-block
-// for the image the two halves exchange; a unit group beyond G (odd G) runs as a member without valid cells
+// the fused form: one 8-wave workgroup per CU = two unit groups (2 j, 2 j + 1) of one cluster that share one gather of the h image
+// (cluster_run_k16<NBW, half>), plus 2 KiB of LDS per wave and K-block for the image the two halves exchange; the launch lays out
+// ceil(G / 2) members per cluster (XCD-local octets as above); a unit group beyond G (odd G) runs as a member without valid cells
 __global__ __launch_bounds__(512, 1) void k_scan_cluster_k16fs(ClusterLaunch L) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   mgr_cluster_enter(L.cm);
@@ -1465,11 +1103,11 @@ __global__ __launch_bounds__(512, 1) void k_scan_cluster_k16fs(ClusterLaunch L) 
     float* sm = smem + tg * K16_LDS_FLOATS;
     float* xs = smem + 2 * K16_LDS_FLOATS;
     const int nbw = (((jb.H + 31) >> 5) + 3) >> 2;
-#define K16FS_RUN(NBW)                                                        \
-  if (nbw == NBW) {                                                           \
-    if (tg == 0) cluster_run_k16<NBW, true, 0>(jb, L.cm, bg, ug, sm, same, xs); \
-    else cluster_run_k16<NBW, true, 1>(jb, L.cm, bg, ug, sm, same, xs);       \
-    return mgr_cluster_exit(L.cm);                                            \
+#define K16FS_RUN(NBW)                                                    \
+  if (nbw == NBW) {                                                       \
+    if (tg == 0) cluster_run_k16<NBW, 0>(jb, L.cm, bg, ug, sm, same, xs); \
+    else cluster_run_k16<NBW, 1>(jb, L.cm, bg, ug, sm, same, xs);         \
+    return mgr_cluster_exit(L.cm);                                        \
   }
     K16FS_RUN(1) K16FS_RUN(2) K16FS_RUN(3) K16FS_RUN(4)
 #undef K16FS_RUN
@@ -1525,7 +1163,6 @@ void mgr_cluster_geometry(const ClusterLaunch& L, bool any_exchange, int* waves,
   *waves = maxnw <= 4 ? 4 : CL_WAVES;
   // 4-wave workgroups with <= 80 KiB of LDS fit two per CU (8 waves, <= 256 VGPRs each); anything else sits alone on its CU
   *per_cu = (*waves == 4 && (ks_eligible(L, any_exchange, *waves) || image_lds(L) <= 80 * 1024)) ? 2 : 1;
-  if (L.pair && L.split16 && ks_eligible(L, any_exchange, *waves)) *per_cu = 1;   // (the pair form's 101 KiB of LDS: alone among scans on its CU)
   if (L.fused && L.split16 && ks_eligible(L, any_exchange, *waves)) {              // (the fused form: 8 waves, 104 KiB, a CU of its own)
     *waves = 8;
     *per_cu = 1;
@@ -1557,33 +1194,22 @@ int mgr_cluster_launch(mgr_ctx* c, const ClusterLaunch& L, int total_wgs, bool a
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_ks_s), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_k16), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_k16_s), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_k16p), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     c->attr_done |= 1u;
   }
   const bool fused = L.fused && L.split16 && ks_eligible(L, any_exchange, 4);
   MGR_REQUIRE(!L.xcd_local || fused || ks_eligible(L, any_exchange, waves), "XCD-local layout is only understood by the K-split kernel");
   if (fused) {
     MGR_REQUIRE(L.xcd_local, "the fused form is laid out in octets");
-    if (!(c->attr_done & 4u)) {   // (per device, hence per context - like the block above)
-      MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_k16f), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      c->attr_done |= 4u;
-    }
-    if (!(c->attr_done & 64u)) {
+    if (!(c->attr_done & 64u)) {   // (per device, hence per context - like the block above)
       MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_k16fs), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       c->attr_done |= 64u;
     }
-    // tune key 17: 1 = the two halves of a fused workgroup each fetch the whole h image themselves (round 5's form)
-    if (c->tune[17] == 0)
-      hipLaunchKernelGGL(k_scan_cluster_k16fs, dim3(total_wgs), dim3(512), K16FS_LDS_BYTES, mgr_stream(c), L);
-    else
-      hipLaunchKernelGGL(k_scan_cluster_k16f, dim3(total_wgs), dim3(512), 2 * K16_LDS_FLOATS * sizeof(float), mgr_stream(c), L);
+    hipLaunchKernelGGL(k_scan_cluster_k16fs, dim3(total_wgs), dim3(512), K16FS_LDS_BYTES, mgr_stream(c), L);
   } else if (ks_eligible(L, any_exchange, waves)) {
     // partial-sum exchange, staging tiles of the transposed output, Z / R rings (no h image): 50 KiB, two workgroups per CU
     bool small = true;
     for (int i = 0; i < L.njobs; ++i) small = small && L.job[i].ks <= 32;
-    if (L.split16 && L.pair) {
-      hipLaunchKernelGGL(k_scan_cluster_k16p, dim3(total_wgs), dim3(256), K16P_LDS_FLOATS * sizeof(float), mgr_stream(c), L);
-    } else if (L.split16) {
+    if (L.split16) {
       if (small)
         hipLaunchKernelGGL(k_scan_cluster_k16_s, dim3(total_wgs), dim3(256), K16_LDS_FLOATS * sizeof(float), mgr_stream(c), L);
       else

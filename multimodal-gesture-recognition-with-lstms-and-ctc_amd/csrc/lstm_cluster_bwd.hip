@@ -473,7 +473,7 @@ __device__ __forceinline__ void cluster_bwd_run(const ClusterBwdJob& jb, int bg,
 // 16-byte element a source lane published; a workgroup's own tile travels through the exchange like the others) and sums them in the
 // same order - no partial sums through LDS, ONE barrier per step.  1.58 us per step alone at H = 100 (1.77 without), and 28 KiB per
 // workgroup and step through the texture path instead of 6: it lost 1 - 2 ms per step while encoder-scan workgroups shared its CUs,
-// and is the form the engine asks for (tune key 16 = 2) once the fused encoder scans leave the fusion layer CUs of its own.
+// and is the form the engine asks for (MGR_TUNE_BPTT_FORM = 2) once the fused encoder scans leave the fusion layer CUs of its own.
 // FUSED (round 6, k_scan_cluster_bwd16_f): the workgroup has 512 threads and runs TWO unit groups of one cluster - threads 0..255 the
 // member 2 j, threads 256..511 the member 2 j + 1 - each through this function with its own half of the LDS; they share the CU and
 // the barriers (the same count in both halves: two in the prologue, per step one in front of the reduction unless DIRECT, one behind the
@@ -883,7 +883,7 @@ __global__ __launch_bounds__(2 * BW_WAVES * 64) void k_scan_cluster_bwd_split(Cl
   scan_cluster_bwd_body<true>(L, smem);
 }
 
-// the same three with split-f16 operands (cluster_bwd_run<.., true>; tune key 14 = 1 keeps the f32 MFMA kernels above)
+// the same three with split-f16 operands (cluster_bwd_run<.., true>; MGR_TUNE_SCAN_F32_MFMA = 1 keeps the f32 MFMA kernels above)
 __global__ __launch_bounds__(BW_WAVES * 64) void k_scan_cluster_bwd16_s(ClusterBwdLaunch L) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   scan_cluster_bwd_body<false, true, true>(L, smem);
@@ -972,7 +972,7 @@ bool mgr_cluster_bwd_supported(int H) {
 // split roles (8 waves, > 80 KiB of LDS requested so that exactly one workgroup sits on a CU) whenever the launch fits one
 // workgroup per CU, has an exchange at all and the layers are wide: at H = 100 (7 workgroups per cluster, two 16-byte stores
 // per lane and step) the store acknowledgement is 0.35 of 2.2 us and the 8-wave workgroups cost config F 0.7 % end to end,
-// at H = 300 / 500 they save a third of the step (E: 60 -> 48 ms/step, S_ref 24 -> 21).  tune key 8: 1 = never, 2 = always.
+// at H = 300 / 500 they save a third of the step (E: 60 -> 48 ms/step, S_ref 24 -> 21).  MGR_TUNE_BPTT_SPLIT_ROLE: 1 = never, 2 = always.
 static bool bwd_split(const mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs) {
   int maxH = 0;
   bool exchange = false;
@@ -980,12 +980,13 @@ static bool bwd_split(const mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs
     maxH = L.job[i].H > maxH ? L.job[i].H : maxH;
     exchange = exchange || L.job[i].G_ > 1;
   }
-  return exchange && (maxH >= 200 || c->tune[8] == 2) && total_wgs <= c->cu_count && c->tune[8] != 1;
+  const int key = c->tune[MGR_TUNE_BPTT_SPLIT_ROLE];
+  return exchange && (maxH >= 200 || key == 2) && total_wgs <= c->cu_count && key != 1;
 }
 
 // the fused form runs narrow layers (16 < H <= 128) on the split-f16 path, laid out in XCD-local octets
 bool mgr_cluster_bwd_fusable(const mgr_ctx* c, const ClusterBwdLaunch& L) {
-  bool ok = c->tune[14] == 0 && L.xcd_local && L.njobs > 0;
+  bool ok = c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0 && L.xcd_local && L.njobs > 0;
   for (int i = 0; i < L.njobs; ++i) ok = ok && L.job[i].H > 16 && L.job[i].H <= 128 && L.job[i].G_ >= 2;
   return ok;
 }
@@ -1017,7 +1018,7 @@ int mgr_cluster_bwd_launch(mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs,
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_bwd16_fd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     c->attr_done |= 2u;
   }
-  const bool f16 = c->tune[14] == 0;   // split-f16 operands (tune key 14 = 1: f32 MFMA)
+  const bool f16 = c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0;   // split-f16 operands (MGR_TUNE_SCAN_F32_MFMA = 1: f32 MFMA)
   if (L.fused) {
     MGR_REQUIRE(mgr_cluster_bwd_fusable(c, L) && total_wgs <= c->cu_count, "the fused BPTT form needs narrow split-f16 layers in octets, one workgroup per CU");
     // (>= 84 KiB requested: the workgroup sits alone on its CU whatever its registers would allow)

@@ -95,10 +95,10 @@ class Schedule:
                         stream IN FRONT of the next batch's deepest scan - into gate pre-activation buffers of their own - and run while
                         that stream would wait for this step's fusion projections (a store-bound f32 GEMM beside a staging-bound one)
     bptt_yields_beside_scans  (round 5) a narrow layer's BPTT that the schedule puts beside the next batch's encoder scans takes the form
-                        that yields to them (mgr.h, tune key 16) instead of the one trimmed along its dependent chain (faster alone,
+                        that yields to them (mgr.h, MGR_TUNE_BPTT_FORM) instead of the one trimmed along its dependent chain (faster alone,
                         costs the step 0.1 - 0.2 ms there); bit-identical either way
     bptt_direct_when_alone  (round 5; measured, not the default) beside fused encoder scans the fusion layer's BPTT takes the direct-gather
-                        form (mgr.h, tune key 16 = 2: one barrier per step, the fastest form alone) - 16.64 - 16.72 against 16.60 - 16.61 ms
+                        form (mgr.h, MGR_TUNE_BPTT_FORM = 2: one barrier per step, the fastest form alone) - 16.64 - 16.72 against 16.60 - 16.61 ms
     fused_wide_tiles    (round 5) with fused encoder scans no GEMM shares a CU with a scan workgroup: the fusion layer's pre-split
                         products take the library's own tile choice instead of the 4-wave forms
     fused_encoder_scans (round 5; needs encoders_two_ahead) the encoder scans take the FUSED form (mgr.h, MGR_SCAN_FORM_FUSED: 8-wave
@@ -612,14 +612,14 @@ class Engine:
 
     def _split_rows_wanted(self):
         """The format new transposed activation copies are written in: split rows (f16 hi / lo pairs, mgr.h) for the pre-split
-        products on the f16 matrix pipe - unless tune key 15 keeps the GEMMs on their f32 MFMA kernels (bench.py's second leg)."""
+        products on the f16 matrix pipe - unless MGR_TUNE_GEMM_F32 keeps the GEMMs on their f32 MFMA kernels (bench.py's second leg)."""
         if not self.schedule.split_rows or self.inference_only or not self._fmt_train:
             # (learning phase 0 has no dropout mask: ONE dense K loop stages the A tile once for the four gates - k_gemm_nn_dense16 on
             #  f32 rows; the pre-split kernel would stage it once per gate: 20.3 against 19.4 ms per pipelined batch.  By PHASE, not by
             #  engine: predict on a training engine and on an inference engine give the same bits)
             return False
         v = C.c_int()
-        self.dev.call("mgr_tune_get", 15, C.byref(v))
+        self.dev.call("mgr_tune_get", _capi.TUNE_GEMM_F32, C.byref(v))
         return v.value == 0
 
     def _make_xt(self, X, ldx, XT, B, T, fin):
@@ -869,7 +869,7 @@ class Engine:
     _wide_ok = False          # probe: with fused encoder scans no GEMM shares a CU with a scan workgroup - the library's own tile choice
     _gate_words = (None, None)  # fused encoder scans: the host words through which the launches the fusion scan / the BPTT of the step
                                 # being enqueued wait for hand over their launch numbers
-    _enc_scan_form = _capi.SCAN_FORM_AUTO      # form of the encoder scan launches enqueued NOW (AUTO: the context's tune key 4)
+    _enc_scan_form = _capi.SCAN_FORM_AUTO      # form of the encoder scan launches enqueued NOW (AUTO: the context's MGR_TUNE_SCAN_FORM)
     _fusion_scan_form = _capi.SCAN_FORM_AUTO   # form of the fusion layer's scan launch
     _early_words = None      # seq_words dict of the generator in _early_gen
     _since_fresh = 0         # pipelined calls since the last one that started the next batch's pass itself (0 in such a call)
@@ -901,8 +901,8 @@ class Engine:
         return _Ctx()
 
     def _narrow_tiles(self, on):
-        """Context manager: the pre-split products enqueued inside take their 4-wave forms (tune key 12 = 1, mgr.h)."""
-        return self._tuned(on, {12: 1})
+        """Context manager: the pre-split products enqueued inside take their 4-wave forms (MGR_TUNE_PROJ_TS_TILE = 1, mgr.h)."""
+        return self._tuned(on, {_capi.TUNE_PROJ_TS_TILE: 1})
 
     def _new_seq_word(self):
         """Address of a zeroed page-locked word: a launch number on its way from the launch (mgr_scan_launch_opts.seq_out) to the
@@ -914,7 +914,7 @@ class Engine:
 
     def _scan_multi(self, jobs, wsname, form=_capi.SCAN_FORM_AUTO, seq_word=0):
         """One multi-scan call on the current stream; `wsname` keeps the encoder and fusion workspaces apart (they may
-        be in flight at the same time when steps are pipelined).  form: mgr.h MGR_SCAN_FORM_* (AUTO: the context's tune key 4);
+        be in flight at the same time when steps are pipelined).  form: mgr.h MGR_SCAN_FORM_* (AUTO: the context's MGR_TUNE_SCAN_FORM);
         seq_word: address of the host word that receives the launch number (0: not wanted)."""
         arr = _capi.make_scan_jobs(jobs)
         need = self.lib.mgr_lstm_scan_multi_ws_bytes(len(jobs), arr)
@@ -1528,9 +1528,11 @@ class Engine:
             dA, ldda = 0, D
         # the whole head in one call (mgr.h): Dropout / Dense / softmax, CTC loss + gradient, the mean loss, Dense backward
         # (a step of the fused schedule: the head runs beside the next batch's deepest encoder scan - 208 whole CUs.  The CTC kernels ask
-        #  for more LDS than a scan workgroup leaves on its CU - tune keys 20 / 21, mgr.h - so that the 32 recurrence workgroups get one of
-        #  the 48 other CUs each, and neither they nor the per-frame kernels share SIMDs with the scan, which is on the step's critical path)
-        with self._tuned(self._gate_words[0] is not None or self._gate_words[1] is not None, {20: 96, 21: 64}, keep_set=True):
+        #  for more LDS than a scan workgroup leaves on its CU - MGR_TUNE_CTC_CHAIN_LDS_KIB / _FRAME_LDS_KIB, mgr.h - so that the 32
+        #  recurrence workgroups get one of the 48 other CUs each, and neither they nor the per-frame kernels share SIMDs with the scan,
+        #  which is on the step's critical path)
+        ctc_lds = {_capi.TUNE_CTC_CHAIN_LDS_KIB: 96, _capi.TUNE_CTC_FRAME_LDS_KIB: 64}
+        with self._tuned(self._gate_words[0] is not None or self._gate_words[1] is not None, ctc_lds, keep_set=True):
             dev.call("mgr_head_fwd_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self._wview("dense/W"), self._wview("dense/b"),
                      self.labels_d, self.ilen_d, self.llen_d, B, T, D, Cn, self.Lmax, int(sp.ctc["skip"]), Cn - 1, float(sp.ctc["eps"]),
                      1.0 / B, self.P, self.loss_b, self.loss_mean, self.dLogits, self._gview("dense/W"), self._gview("dense/b"),
@@ -1717,7 +1719,7 @@ class Engine:
             self._ws_bwd_multi = self.mem.bytes(need)
         beside_scans = self._beside_scans     # (the deferred GEMMs run beside the next batch's encoder scans as well)
         wide_ok = self._wide_ok
-        # The form of the narrow-layer BPTT is an argument of the launch (mgr.h MGR_BPTT_FORM_*; AUTO = the context's tune key 16):
+        # The form of the narrow-layer BPTT is an argument of the launch (mgr.h MGR_BPTT_FORM_*; AUTO = the context's MGR_TUNE_BPTT_FORM):
         # beside the next batch's encoder scans the form that yields to them - or, beside FUSED encoder scans (CUs of its own) and if the
         # schedule asks for it, the direct gather with one barrier per step; a launch that has the chip to itself takes the context's.
         form = _capi.BPTT_FORM_AUTO

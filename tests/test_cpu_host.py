@@ -485,10 +485,10 @@ def test_local_world_size_does_not_take_a_multi_node_world_for_the_node(monkeypa
     assert subprocess.run([_sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True).stdout.split() == ["None"]
 
 
-def test_binding_constants_and_structs_match_the_header():
-    """The ctypes binding restates enums and struct layouts of include/mgr.h by hand: the launch forms, MGR_SEQ_NONE, the ABI revision,
-    the profiling families, and the member lists of the three structs it fills field by field (the library reports their sizes at
-    load time - mgr_abi_struct_sizes - but only a GPU box loads it; this is the CPU-side half of the guard)."""
+def test_binding_constants_tune_keys_and_structs_match_the_header():
+    """The ctypes binding restates enums and struct layouts of include/mgr.h by hand: the launch forms, the tune keys, MGR_SEQ_NONE, the
+    ABI revision, the profiling families, and the member lists of the three structs it fills field by field (the library reports
+    their sizes at load time - mgr_abi_struct_sizes - but only a GPU box loads it; this is the CPU-side half of the guard)."""
     import re
     from mgr_amd import _capi
     hdr = open(os.path.join(ROOT, "include", "mgr.h")).read()
@@ -500,7 +500,7 @@ def test_binding_constants_and_structs_match_the_header():
         return int(m.group(1), 0)
 
     for c_name, py in (("MGR_SCAN_FORM_AUTO", _capi.SCAN_FORM_AUTO), ("MGR_SCAN_FORM_PLAIN", _capi.SCAN_FORM_PLAIN),
-                       ("MGR_SCAN_FORM_PAIR", _capi.SCAN_FORM_PAIR), ("MGR_SCAN_FORM_FUSED", _capi.SCAN_FORM_FUSED),
+                       ("MGR_SCAN_FORM_FUSED", _capi.SCAN_FORM_FUSED),
                        ("MGR_SCAN_FORM_FUSED_ANY", _capi.SCAN_FORM_FUSED_ANY), ("MGR_BPTT_FORM_AUTO", _capi.BPTT_FORM_AUTO),
                        ("MGR_BPTT_FORM_TRIMMED", _capi.BPTT_FORM_TRIMMED), ("MGR_BPTT_FORM_YIELDING", _capi.BPTT_FORM_YIELDING),
                        ("MGR_BPTT_FORM_DIRECT", _capi.BPTT_FORM_DIRECT), ("MGR_BPTT_FORM_FUSED", _capi.BPTT_FORM_FUSED),
@@ -510,6 +510,9 @@ def test_binding_constants_and_structs_match_the_header():
                        ("MGR_K_ALLREDUCE", _capi.K_ALLREDUCE)):
         assert enum(c_name) == py, c_name
     assert enum("MGR_K_COUNT") == len(_capi.KERNEL_FAMILIES)
+    tune = dict((n, int(v)) for n, v in re.findall(r"\bMGR_TUNE_(\w+)\s*=\s*(\d+)", flat))
+    assert tune["SCAN_PATH"] == 0 and tune["COUNT"] == 24 and len(set(tune.values())) == len(tune)
+    assert tune == {n[len("TUNE_"):]: v for n, v in vars(_capi).items() if n.startswith("TUNE_")}
     assert int(re.search(r"#define MGR_ABI_REVISION\s+(\d+)", hdr).group(1)) == _capi.ABI_REVISION
     assert int(re.search(r"#define MGR_SEQ_NONE\s+(0x[0-9A-Fa-f]+)u", hdr).group(1), 16) == _capi.SEQ_NONE
 

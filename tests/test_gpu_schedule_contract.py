@@ -127,6 +127,34 @@ def test_struct_size_guards_the_options(device):
         a.free()
 
 
+def test_retired_scan_forms_are_refused(device):
+    """mgr.h: the pair form of the forward scan (tune key 4 = 2, launch form 2) and the fused form whose halves gather alone (tune key
+    17 != 0) are retired.  Asking for either fails with a message and changes nothing: the key keeps its value, the launch writes no
+    output and hands back no launch number."""
+    from mgr_amd import _capi
+    lib = device.lib
+    for key, val in ((_capi.TUNE_SCAN_FORM, 2), (17, 1)):
+        before, after = C.c_int(), C.c_int()
+        _capi.check(lib.mgr_tune_get(device.ctx, key, C.byref(before)))
+        assert lib.mgr_tune(device.ctx, key, val) != 0, key
+        assert b"retired" in lib.mgr_last_error(), key
+        _capi.check(lib.mgr_tune_get(device.ctx, key, C.byref(after)))
+        assert after.value == before.value, key
+    B, T, H = 33, 6, 100
+    _, Zp, Up = _scan_setup(device, B, T, H, seed=3)
+    Y = device.array(np.full((B, T, H), 7.0, np.float32))
+    arr = _capi.make_scan_jobs([dict(Z=Zp, Up=Up, Y=Y, ldy=H, B=B, T=T, H=H, reverse=0)])
+    ws = device.bytes(lib.mgr_lstm_scan_multi_ws_bytes(1, arr))
+    seq = C.c_uint(7)
+    opts = _capi.make_launch_opts(2, C.addressof(seq))
+    assert lib.mgr_lstm_scan_fwd_multi_ex(device.ctx, 1, arr, ws.ptr, ws.nbytes, C.byref(opts)) != 0
+    assert b"retired" in lib.mgr_last_error()
+    device.sync()
+    assert seq.value == 7 and (Y.download() == 7.0).all()
+    for a in (Zp, Up, Y, ws):
+        a.free()
+
+
 def _fusion_run(device, B, T, steps, sched, between=None, seed=5):
     """`steps` device-RNG training steps of the reference-size fusion network announced two calls ahead (what bench.py and
     fit_generator do); between(eng, i) runs after step i's loss was read."""
@@ -241,10 +269,10 @@ def test_drop_paths_of_the_two_ahead_schedule_equal_the_plain_schedule(device):
         assert np.array_equal(gq[k], gp[k]), k
 
 
-def test_tune_keys_of_the_caller_survive_a_fused_step(device):
+def test_legal_tune_keys_of_the_caller_survive_a_fused_step(device):
     """the engine used to set tune keys 4, 12 and 16 around its launches and reset them to 0 - a user's or bench.py's
     own `--tune` setting was gone after the first fused step.  The forms are launch arguments now and key 12 is restored."""
-    vals = {4: 2, 12: 2, 16: 1}
+    vals = {4: 1, 12: 2, 16: 1}
     for k, v in vals.items():
         device.call("mgr_tune", k, v)
     try:

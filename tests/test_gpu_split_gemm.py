@@ -153,11 +153,10 @@ def test_weight_gradient_from_split_rows(device, B, T, F, H, p, reverse):
 
 
 @pytest.mark.parametrize("hs,B,T", [((500, 300), 40, 21), ((300,), 64, 19), ((100,), 33, 24), ((500,), 16, 9)])
-def test_pair_form_of_the_scan_is_bit_identical_and_scans_write_split_rows(device, hs, B, T):
-    """lstm_cluster.hip, cluster_run_k16p (two 16-sample groups per workgroup, one workgroup per CU; tune key 4 = 2 forces it, 1
-    forbids it): Y, gates, c and the transposed copies bit for bit those of the one-group form - B = 40 / 33 leave the last cluster
-    with a single group, B = 16 has nothing to pair.  And mgr_scan_job.yt_split: the transposed copy in the split row format is, bit
-    for bit, the split of the f32 copy (hi = rn_f16(y 2^13), lo = rn_f16(y 2^13 - hi)), zeros behind T."""
+def test_scans_write_split_rows(device, hs, B, T):
+    """mgr_scan_job.yt_split (lstm_cluster.hip, the K-split scan kernels write the transposed copy themselves): the copy in the split
+    row format is, bit for bit, the split of the f32 copy (hi = rn_f16(y 2^13), lo = rn_f16(y 2^13 - hi)), zeros behind T, and asking
+    for it changes neither Y nor the gates nor c.  B = 40 / 33 leave the last 16-sample group ragged."""
     from mgr_amd import _capi
     dev = device
     rng = np.random.default_rng(sum(hs) + B + T)
@@ -176,7 +175,7 @@ def test_pair_form_of_the_scan_is_bit_identical_and_scans_write_split_rows(devic
             base_jobs.append(dict(Z=Z, Up=Up, H=H, reverse=d, col=col))
             col += H
 
-    def run(pair, split):
+    def run(split):
         Y = dev.zeros((B, T, W))
         YT = dev.array(np.full((B, W, ldt), 7.0, f32))
         jobs = []
@@ -189,7 +188,6 @@ def test_pair_form_of_the_scan_is_bit_identical_and_scans_write_split_rows(devic
                              reverse=j["reverse"], YT=YT.ptr + c0 * ldt * 4, ytb=W * ldt, ldt=ldt, yt_split=int(split)))
         dev.call("mgr_tune", 0, 3)      # clusters with an exchange at every H (the K-split step)
         dev.call("mgr_tune", 1, 1)
-        dev.call("mgr_tune", 4, 2 if pair else 1)
         try:
             arr = _capi.make_scan_jobs(jobs)
             ws = dev.bytes(dev.lib.mgr_lstm_scan_multi_ws_bytes(len(jobs), arr))
@@ -197,25 +195,21 @@ def test_pair_form_of_the_scan_is_bit_identical_and_scans_write_split_rows(devic
         finally:
             dev.call("mgr_tune", 0, 0)
             dev.call("mgr_tune", 1, 0)
-            dev.call("mgr_tune", 4, 0)
         return Y.download(), YT.download(), [o.download() for o in outs]
 
-    y0, yt0, o0 = run(False, False)
-    y1, yt1, o1 = run(True, False)
-    assert np.array_equal(y0, y1) and np.array_equal(yt0, yt1) and all(np.array_equal(a, b) for a, b in zip(o0, o1))
+    y0, yt0, o0 = run(False)
     assert np.array_equal(yt0[:, :, :T], y0.transpose(0, 2, 1)) and not yt0[:, :, T:].any()
-    for pair in (False, True):
-        y2, yts, o2 = run(pair, True)
-        assert np.array_equal(y2, y0) and all(np.array_equal(a, b) for a, b in zip(o0, o2))
-        assert np.array_equal(yts.view(np.uint32), _split_rows(y0, ldt).view(np.uint32))
+    y2, yts, o2 = run(True)
+    assert np.array_equal(y2, y0) and all(np.array_equal(a, b) for a, b in zip(o0, o2))
+    assert np.array_equal(yts.view(np.uint32), _split_rows(y0, ldt).view(np.uint32))
 
 
 @pytest.mark.parametrize("B,T", [(64, 11), (55, 7)])
-def test_fused_form_of_the_encoder_scans_is_bit_identical(device, B, T):
-    """lstm_cluster.hip, k_scan_cluster_k16f (tune key 4 = 3): 8-wave workgroups that run TWO unit groups of their cluster, one workgroup
+def test_shared_gather_fused_form_of_the_encoder_scans_is_bit_identical(device, B, T):
+    """lstm_cluster.hip, k_scan_cluster_k16fs (tune key 4 = 3): 8-wave workgroups that run TWO unit groups of their cluster, one workgroup
     per CU - taken only by launches that do not fit one workgroup per CU as they are, i.e. the encoder depths of config F (audio H = 500 +
     skeletal H = 300, both directions, B = 64: 408 workgroups -> 208).  Y, gates, c and the split transposed copies bit for bit those of
-    the default form; skeletal clusters have an odd number of unit groups (19): the last workgroup's second half only keeps the barriers."""
+    the default form; skeletal clusters have an odd number of unit groups (19): the last workgroup's second half runs without valid cells."""
     from mgr_amd import _capi
     dev = device
     hs = (500, 300)
@@ -235,7 +229,7 @@ def test_fused_form_of_the_encoder_scans_is_bit_identical(device, B, T):
             base_jobs.append(dict(Z=Z, Up=Up, H=H, reverse=d, col=col))
             col += H
 
-    def run(fused, own_gather=0):
+    def run(fused):
         Y = dev.zeros((B, T, W))
         YT = dev.array(np.full((B, W, ldt), 7.0, f32))
         jobs, outs = [], []
@@ -247,7 +241,6 @@ def test_fused_form_of_the_encoder_scans_is_bit_identical(device, B, T):
                              reverse=j["reverse"], YT=YT.ptr + c0 * ldt * 4, ytb=W * ldt, ldt=ldt, yt_split=1))
         dev.call("mgr_tune", 1, 1)
         dev.call("mgr_tune", 4, 3 if fused else 0)
-        dev.call("mgr_tune", 17, own_gather)
         try:
             arr = _capi.make_scan_jobs(jobs)
             ws = dev.bytes(dev.lib.mgr_lstm_scan_multi_ws_bytes(len(jobs), arr))
@@ -255,17 +248,13 @@ def test_fused_form_of_the_encoder_scans_is_bit_identical(device, B, T):
         finally:
             dev.call("mgr_tune", 1, 0)
             dev.call("mgr_tune", 4, 0)
-            dev.call("mgr_tune", 17, 0)
         return Y.download(), YT.download(), [o.download() for o in outs]
 
     y0, yt0, o0 = run(False)
     assert np.isfinite(y0).all() and np.abs(y0).max() > 0.1
-    # round 6: the two halves of a fused workgroup SHARE one gather of the h image through LDS (k_scan_cluster_k16fs, the default);
-    # tune key 17 = 1: each half fetches the whole image itself (round 5's k_scan_cluster_k16f) - all three the same bits
-    for own_gather in (0, 1):
-        y1, yt1, o1 = run(True, own_gather)
-        assert np.array_equal(y0, y1) and np.array_equal(yt0.view(np.uint32), yt1.view(np.uint32)), own_gather
-        assert all(np.array_equal(a, b) for a, b in zip(o0, o1)), own_gather
+    y1, yt1, o1 = run(True)
+    assert np.array_equal(y0, y1) and np.array_equal(yt0.view(np.uint32), yt1.view(np.uint32))
+    assert all(np.array_equal(a, b) for a, b in zip(o0, o1))
 
 
 @pytest.mark.parametrize("H,B,T", [(100, 64, 40), (128, 20, 9), (64, 33, 17), (100, 16, 1)])
