@@ -161,9 +161,17 @@ int mgr_transpose_bt_split(mgr_ctx* ctx, const float* X, int ldx, float* XS, int
 int mgr_transpose_bt_split_shift(mgr_ctx* ctx, const float* X, int ldx, float* XS, int ldt, int B, int T, int F, int tshift);
 /* Frozen weights: frozen != 0 promises that the contents of Wp (a packed input-weight matrix passed to mgr_lstm_input_proj_dropout_ts) do
  * not change until the next call of this function for the same pointer; the (hi, lo) weight planes and the largest |W| that
- * mgr_lstm_input_proj_dropout_ts leaves in its workspace are then reused by later calls with the same (Wp, workspace, F, H) instead of
+ * mgr_lstm_input_proj_dropout_ts leaves in its workspace are then reused by later calls with the same (Wp, workspace, B, F, H) instead of
  * being rebuilt (the frozen encoders of the fusion network, multimodal_fusion/multimodal.py:118-130: 4 of the 6 conversions of a step).
- * Every call (either value) drops what was kept for Wp - call it again after rewriting the weights.  Host-side state only. */
+ * Every call (either value) drops what was kept for Wp - call it again after rewriting the weights.  Host-side state only.
+ *   Kept planes are forgotten (the next call with that key rebuilds them) by every library call that writes bytes they lie in:
+ *   mgr_memset, mgr_h2d, mgr_h2d_async and mgr_d2d into that range (a pointer into the workspace included), every entry point given
+ *   that workspace (or a range over it) as its own ws, and mgr_lstm_input_proj_dropout_ts with another key on it.  mgr_free of a buffer
+ *   ends the promise of every weight inside it and forgets every plane kept in it.  Copies into Wp itself do not forget: a rewrite
+ *   behind the promise goes unnoticed.  proj_ws of mgr_lstm_param_grads_dropout_ts is only read.  Writes the library cannot see - an
+ *   output argument of another call pointing into the workspace, the caller's own kernels - must not touch a workspace with kept planes.
+ *   Ordering is the caller's, as for any reuse of a workspace (every call rewrites its lists and mask-factor word): a call on another
+ *   stream that reuses kept planes must be ordered after the call that built them (an event, mgr_stream_wait). */
 int mgr_weight_planes_cache(mgr_ctx* ctx, const float* Wp, int frozen);
 /* Recurrence. reverse=1 walks t = T-1..0 and writes outputs at their original t (Bidirectional backward
  * sub-layer).  Y[b,t,0:H] with row stride ldy gets h_t (+ R[b,t,0:H] with stride ldr when R != NULL: the

@@ -266,6 +266,7 @@ int mgr_ctc_beam_search(mgr_ctx* c, const float* P, const int32_t* input_len, in
                         int beam, float eps, int merge_repeated, int32_t* out, int32_t* out_len, double* logp, void* ws,
                         size_t ws_bytes) {
   MGR_REQUIRE(c && P && input_len && out && out_len && logp, "null argument");
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   MGR_REQUIRE(B > 0 && T > skip && skip >= 0 && C > 1 && C <= MAXC, "bad shape (C <= %d)", MAXC);
   MGR_REQUIRE(beam >= 1 && beam <= MAXW, "beam width %d out of [1,%d]", beam, MAXW);
   MGR_REQUIRE(beam * (C + 1) <= 64 * KMAX, "beam*(C+1) too large");

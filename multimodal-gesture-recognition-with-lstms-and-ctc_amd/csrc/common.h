@@ -50,11 +50,14 @@ struct mgr_ctx {
   int persist_serialised;   // launches that had to be ordered behind another stream's persistent launch
   unsigned attr_done;       // bit k: function attributes of kernel family k have been set on this context's device
   // split weight planes of FROZEN weights (gemm_split.hip, mgr_weight_planes_cache): weights the caller promised not to rewrite, and
-  // the workspaces that hold their planes as of that promise
+  // the workspaces that hold their planes as of that promise.  Key (Wp, ws, B, F, H): B and F place the planes inside ws, F and H
+  // size them; [region, region + region_bytes) are the bytes of ws the entry relies on (the largest-|W| word block and the planes)
   struct PlaneEntry {
     const void* Wp;
     const void* ws;
-    int F, H;
+    int B, F, H;
+    const char* region;
+    size_t region_bytes;
   };
   const void* frozen_w[MGR_MAX_FROZEN];
   PlaneEntry planes[MGR_MAX_FROZEN];
@@ -63,11 +66,16 @@ struct mgr_ctx {
 
 int mgr_fail(int code, const char* fmt, ...);
 
-// cached split weight planes (gemm_split.hip, mgr_weight_planes_cache) live in a projection workspace: any OTHER use of that workspace
-// forgets them
-static inline void mgr_planes_forget_ws(mgr_ctx* c, const void* ws) {
+// cached split weight planes (gemm_split.hip, mgr_weight_planes_cache) live in a projection workspace: every call that writes the
+// n bytes at p (a copy, a memset, an entry point given a workspace) forgets the entries whose kept bytes it overlaps
+static inline bool mgr_planes_overlap(const mgr_ctx::PlaneEntry& e, const void* p, size_t n) {
+  const char* a = static_cast<const char*>(p);
+  return e.Wp && a < e.region + e.region_bytes && e.region < a + n;
+}
+static inline void mgr_planes_forget_range(mgr_ctx* c, const void* p, size_t n) {
+  if (!p || !n) return;
   for (int i = 0; i < MGR_MAX_FROZEN; ++i)
-    if (c->planes[i].ws == ws) c->planes[i] = mgr_ctx::PlaneEntry{nullptr, nullptr, 0, 0};
+    if (mgr_planes_overlap(c->planes[i], p, n)) c->planes[i] = mgr_ctx::PlaneEntry{};
 }
 
 #define MGR_HIP(expr)                                                                      \

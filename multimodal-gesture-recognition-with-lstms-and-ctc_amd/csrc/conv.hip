@@ -346,6 +346,7 @@ size_t mgr_conv_pool_bwd_weights_ws_bytes(int N, int Hin, int Win, int Cin, int 
 int mgr_conv_pool_bwd_weights(mgr_ctx* c, const float* X, const float* dY, const uint8_t* code, int N, int Hin, int Win, int Cin, int ks,
                               int Cout, float* dW, float* db, void* ws, size_t ws_bytes) {
   MGR_REQUIRE(c && X && dY && code && dW && db && ws, "null argument");
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   Shape s;
   if (int r = check_shape(N, Hin, Win, Cin, ks, Cout, &s)) return r;
   const size_t need = mgr_conv_pool_bwd_weights_ws_bytes(N, Hin, Win, Cin, ks, Cout);

@@ -489,6 +489,7 @@ int mgr_ctc_loss_grad(mgr_ctx* c, const float* P, const int32_t* labels, const i
                       const int32_t* label_len, int B, int T, int C, int Lmax, int skip, int blank, float eps,
                       float gscale, float* loss, float* dLogits, void* ws, size_t ws_bytes) {
   MGR_REQUIRE(c && P && labels && input_len && label_len && loss, "null argument");
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   MGR_REQUIRE(B > 0 && T > skip && skip >= 0 && C > 1 && Lmax > 0, "bad shape B=%d T=%d C=%d Lmax=%d skip=%d", B, T, C, Lmax, skip);
   MGR_REQUIRE(blank >= 0 && blank < C, "blank %d out of range", blank);
   MGR_REQUIRE(Lmax + 1 <= 256, "Lmax %d too large (max 255)", Lmax);

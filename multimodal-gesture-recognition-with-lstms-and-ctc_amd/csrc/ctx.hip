@@ -165,22 +165,36 @@ int mgr_free(mgr_ctx* c, void* dptr) {
   MGR_HIP(hipSetDevice(c->device));
   if (dptr == c->status_bound) c->status_bound = nullptr;   // a freed status block is not reported into any more
   if (dptr == c->gate_flag) c->gate_flag = nullptr;
-  for (int i = 0; i < MGR_MAX_FROZEN; ++i) {   // (cached weight planes: neither the weights nor the workspace outlive their buffer)
-    if (c->frozen_w[i] == dptr) c->frozen_w[i] = nullptr;
-    if (c->planes[i].Wp == dptr || c->planes[i].ws == dptr) c->planes[i] = mgr_ctx::PlaneEntry{nullptr, nullptr, 0, 0};
+  // cached weight planes: neither a promise nor kept planes outlive the buffer they lie in - views into it included (a later
+  // allocation at the same address must not inherit them)
+  void* base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, dptr) != hipSuccess || !base) {
+    (void)hipGetLastError();   // (not a device allocation: hipFree reports it below)
+    base = dptr;
+    size = 1;
   }
+  const char* lo = static_cast<const char*>(base);
+  const auto inside = [&](const void* p) { return p && static_cast<const char*>(p) >= lo && static_cast<const char*>(p) < lo + size; };
+  for (int i = 0; i < MGR_MAX_FROZEN; ++i) {
+    if (inside(c->frozen_w[i])) c->frozen_w[i] = nullptr;
+    if (inside(c->planes[i].Wp)) c->planes[i] = mgr_ctx::PlaneEntry{};
+  }
+  mgr_planes_forget_range(c, base, size);
   MGR_HIP(hipFree(dptr));
   return 0;
 }
 
 int mgr_memset(mgr_ctx* c, void* d, int byte, size_t n) {
   MGR_REQUIRE(c && d, "null argument");
+  mgr_planes_forget_range(c, d, n);
   MGR_HIP(hipMemsetAsync(d, byte, n, mgr_stream(c)));
   return 0;
 }
 
 int mgr_h2d(mgr_ctx* c, void* d, const void* h, size_t n) {
   MGR_REQUIRE(c && d && h, "null argument");
+  mgr_planes_forget_range(c, d, n);
   MGR_HIP(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, mgr_stream(c)));
   // pageable host memory: make the call synchronous w.r.t. the host buffer (caller may free it)
   MGR_HIP(hipStreamSynchronize(mgr_stream(c)));
@@ -202,6 +216,7 @@ int mgr_host_free(mgr_ctx* c, void* p) {
 
 int mgr_h2d_async(mgr_ctx* c, void* d, const void* h_pinned, size_t n) {
   MGR_REQUIRE(c && d && h_pinned, "null argument");
+  mgr_planes_forget_range(c, d, n);
   // h_pinned must come from mgr_host_alloc and stay untouched until the stream has passed this copy
   MGR_HIP(hipMemcpyAsync(d, h_pinned, n, hipMemcpyHostToDevice, mgr_stream(c)));
   return 0;
@@ -262,6 +277,7 @@ int mgr_event_sync(mgr_ctx* c, int ev) {
 
 int mgr_d2d(mgr_ctx* c, void* dst, const void* src, size_t n) {
   MGR_REQUIRE(c && dst && src, "null argument");
+  mgr_planes_forget_range(c, dst, n);
   MGR_HIP(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, mgr_stream(c)));
   return 0;
 }

@@ -424,6 +424,7 @@ int mgr_dense_bwd(mgr_ctx* c, const float* A, int lda, const float* dmask, float
                   const float* dLogits, const float* Wd, float* dWd, float* dbd, float* dA, int ldda, int B, int T,
                   int D, int C, void* ws, size_t ws_bytes) {
   MGR_REQUIRE(c && A && dLogits && Wd && dWd && dbd, "null argument");
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   MGR_REQUIRE(B > 0 && T > 0 && D > 0 && C > 0 && lda >= D, "bad shape");
   MGR_REQUIRE(C <= 48, "C=%d > 48 unsupported", C);
   MGR_REQUIRE(ws && ws_bytes >= mgr_dense_bwd_ws_bytes(B, T, D, C), "workspace too small");
@@ -472,6 +473,7 @@ int mgr_head_fwd_bwd(mgr_ctx* c, const float* A, int lda, const float* dmask, fl
                      int skip, int blank, float eps, float gscale, float* P, float* loss, float* loss_mean, float* dLogits, float* dWd,
                      float* dbd, float* dA, int ldda, void* ws, size_t ws_bytes) {
   MGR_REQUIRE(c && dLogits && ws && ws_bytes >= mgr_head_ws_bytes(B, T, D, C, Lmax), "head: null argument or workspace too small");
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   int r = mgr_dense_softmax_fwd(c, A, lda, dmask, p, seed, Wd, bd, P, B, T, D, C);
   if (r) return r;
   const size_t wc = mgr_align_up(mgr_ctc_ws_bytes(B, T, C, Lmax), 256);

@@ -1533,7 +1533,7 @@ int mgr_lstm_input_proj_dropout(mgr_ctx* c, const float* X, int ldx, const float
                       aligned16(Wp);
   if (!sparse) return mgr_lstm_input_proj(c, X, ldx, mask4, Wp, bp, Z, B, T, F, H);
   MGR_REQUIRE(ws && ws_bytes >= mgr_lstm_input_proj_dropout_ws_bytes(B, F, H), "workspace too small");
-  mgr_planes_forget_ws(c, ws);   // (this call writes its own lists / weight copies into the workspace: cached split planes in it are gone)
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its own lists / weight copies into the workspace: cached split planes in it are gone)
   return input_proj_dropout_impl(c, X, ldx, false, mask4, drop_rate, Wp, bp, Z, B, T, F, H, ws, ws_bytes);
 }
 
@@ -1548,7 +1548,7 @@ int mgr_lstm_input_proj_dropout_t(mgr_ctx* c, const float* XT, int ldt, const fl
   MGR_REQUIRE(aligned16(XT) && aligned16(bp) && aligned16(Z) && aligned16(Wp), "XT / bp / Z / Wp must be 16-byte aligned");
   MGR_REQUIRE((size_t)F * ldt < (1u << 31), "sample block too large");
   MGR_REQUIRE(ws && ws_bytes >= mgr_lstm_input_proj_dropout_ws_bytes(B, F, H), "workspace too small");
-  mgr_planes_forget_ws(c, ws);   // (this call writes its own lists / weight copies into the workspace: cached split planes in it are gone)
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its own lists / weight copies into the workspace: cached split planes in it are gone)
   return input_proj_dropout_impl(c, XT, ldt, true, mask4, drop_rate, Wp, bp, Z, B, T, F, H, ws, ws_bytes, x_absmax);
 }
 
@@ -1645,6 +1645,7 @@ int mgr_lstm_param_grads(mgr_ctx* c, const float* X, int ldx, const float* mask4
                          const float* dZ, float* dWp, float* dUp, float* dbp, int B, int T, int F, int H, int reverse,
                          void* ws, size_t ws_bytes) {
   MGR_REQUIRE(c && X && Hs && dZ && dWp && dUp && dbp, "null argument");
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   MGR_REQUIRE(B > 0 && T > 0 && F > 0 && H > 0 && ldx >= F && ldh >= H, "bad shape");
   MGR_REQUIRE(ws && ws_bytes >= mgr_lstm_param_grads_ws_bytes(B, T, F, H), "workspace too small");
   MGR_REQUIRE(aligned16(dZ), "dZ must be 16-byte aligned");
@@ -1735,6 +1736,7 @@ int mgr_lstm_param_grads_dropout(mgr_ctx* c, const float* X, int ldx, const floa
                                  int ldh, const float* dZ, float* dWp, float* dUp, float* dbp, int B, int T, int F, int H,
                                  int reverse, void* ws, size_t ws_bytes) {
   MGR_REQUIRE(c && X && Hs && dZ && dWp && dUp && dbp, "null argument");
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   MGR_REQUIRE(B > 0 && T > 0 && F > 0 && H > 0 && ldx >= F && ldh >= H, "bad shape");
   MGR_REQUIRE(aligned16(dZ), "dZ must be 16-byte aligned");
   const bool sparse = sparse_dw_shape(c, mask4, drop_rate, F);
@@ -1756,6 +1758,7 @@ int mgr_lstm_param_grads_dropout_t(mgr_ctx* c, const float* XT, int ldt, const f
                                    const float* dZ, float* dWp, float* dUp, float* dbp, int B, int T, int F, int H, int reverse,
                                    void* ws, size_t ws_bytes, float x_absmax) {
   MGR_REQUIRE(c && XT && mask4 && Hs && dZ && dWp && dUp && dbp, "null argument");
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   MGR_REQUIRE(B > 0 && T > 0 && F > 0 && H > 0 && ldh >= H, "bad shape");
   MGR_REQUIRE(ldt % 4 == 0 && ldt >= (T + BK - 1) / BK * BK, "the transposed copy must be padded to whole stages of %d time steps (ldt %d, T %d)", BK, ldt, T);
   MGR_REQUIRE(aligned16(dZ) && aligned16(XT), "dZ / XT must be 16-byte aligned");

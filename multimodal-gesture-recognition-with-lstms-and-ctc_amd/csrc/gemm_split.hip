@@ -675,18 +675,26 @@ int mgr_lstm_input_proj_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const f
     c->attr_done |= 16u;
   }
   mgr_prof_begin(c, MGR_K_GEMM_NN);
-  // Frozen weights (mgr_weight_planes_cache): the planes this workspace holds from an earlier call are still those of Wp - the largest
-  // |W| (words[0]) and the (hi, lo) planes are not rebuilt, only the mask factor word is reset (4 of the 6 conversions of a config-F step)
-  bool frozen = false, cached = false;
-  int free_slot = -1;
+  // Frozen weights (mgr_weight_planes_cache): the planes this workspace holds from an earlier call with the same (Wp, ws, B, F, H) are
+  // still those of Wp - the largest |W| (words[0]) and the (hi, lo) planes are not rebuilt, only the mask factor word is reset (4 of
+  // the 6 conversions of a config-F step)
+  const char* region = reinterpret_cast<const char*>(words);   // (what an entry relies on: the word block and the planes)
+  const size_t region_bytes = 256 + proj_ts_planes_bytes(F, H);
+  bool frozen = false;
+  int hit = -1;
   for (int i = 0; i < MGR_MAX_FROZEN; ++i) frozen = frozen || (c->frozen_w[i] == Wp);
   if (frozen) {
     for (int i = 0; i < MGR_MAX_FROZEN; ++i) {
       const mgr_ctx::PlaneEntry& e = c->planes[i];
-      if (e.Wp == Wp && e.ws == ws && e.F == F && e.H == H) cached = true;
-      if (!e.Wp && free_slot < 0) free_slot = i;
+      if (e.Wp == Wp && e.ws == ws && e.B == B && e.F == F && e.H == H) hit = i;
     }
   }
+  // this call writes [ws, ws + its size) - all of it but the hit entry's own bytes: every other entry that lies there is forgotten,
+  // frozen Wp or not
+  const size_t need = mgr_lstm_input_proj_dropout_ts_ws_bytes(B, F, H);
+  for (int i = 0; i < MGR_MAX_FROZEN; ++i)
+    if (i != hit && mgr_planes_overlap(c->planes[i], ws, need)) c->planes[i] = mgr_ctx::PlaneEntry{};
+  const bool cached = hit >= 0;
   MGR_HIP(hipMemsetAsync(words + (cached ? 1 : 0), 0, (cached ? 1 : 2) * sizeof(unsigned), s));
   hipLaunchKernelGGL(k_lists32, dim3(4 * B), dim3(64), 0, s, mask4, F, Fp32, lists, kcnt, kpos, words + 1);
   if (!cached) {
@@ -695,8 +703,11 @@ int mgr_lstm_input_proj_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const f
     const size_t n = (size_t)(F + 1) * Hp;
     hipLaunchKernelGGL(k_wplanes, dim3((int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, s, Wp, WSp, F, H, Hp, words);
     if (frozen) {   // (a full table forgets its oldest entry: forgetting is always safe)
-      if (free_slot < 0) free_slot = (int)(c->planes_evict++ % MGR_MAX_FROZEN);
-      c->planes[free_slot] = mgr_ctx::PlaneEntry{Wp, ws, F, H};
+      int slot = -1;
+      for (int i = 0; i < MGR_MAX_FROZEN && slot < 0; ++i)
+        if (!c->planes[i].Wp) slot = i;
+      if (slot < 0) slot = (int)(c->planes_evict++ % MGR_MAX_FROZEN);
+      c->planes[slot] = mgr_ctx::PlaneEntry{Wp, ws, B, F, H, region, region_bytes};
     }
   }
   // 128-unit tiles (8 waves, one workgroup per CU) where they waste little of their width; MGR_TUNE_PROJ_TS_TILE: 1 = always 64,
@@ -736,6 +747,7 @@ int mgr_lstm_param_grads_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const 
                                     void* ws, size_t ws_bytes, const unsigned* dzmax, const float* dbsum, const void* proj_ws,
                                     const float* HsT) {
   MGR_REQUIRE(c && XS && mask4 && Hs && dZ && dWp && dUp && dbp, "null argument");
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone; proj_ws is only read)
   MGR_REQUIRE(B > 0 && T > 0 && H > 0 && F >= 16 && F <= 2048 && ldh >= H, "bad shape (16 <= F <= 2048)");
   MGR_REQUIRE(ldt % 32 == 0 && ldt >= (T + DW_TK - 1) / DW_TK * DW_TK, "the split copy must be padded to whole stages of %d time steps (ldt %d, T %d)", DW_TK, ldt, T);
   MGR_REQUIRE(aligned16(dZ) && aligned16(XS), "dZ / XS must be 16-byte aligned");
@@ -830,7 +842,7 @@ int mgr_weight_planes_cache(mgr_ctx* c, const float* Wp, int frozen) {
   MGR_REQUIRE(c && Wp, "null argument");
   // whatever planes were kept for Wp are dropped: the call marks a point where the weights may have been rewritten
   for (int i = 0; i < MGR_MAX_FROZEN; ++i) {
-    if (c->planes[i].Wp == Wp) c->planes[i] = mgr_ctx::PlaneEntry{nullptr, nullptr, 0, 0};
+    if (c->planes[i].Wp == Wp) c->planes[i] = mgr_ctx::PlaneEntry{};
     if (c->frozen_w[i] == Wp) c->frozen_w[i] = nullptr;
   }
   if (!frozen) return 0;
@@ -842,7 +854,7 @@ int mgr_weight_planes_cache(mgr_ctx* c, const float* Wp, int frozen) {
   // table full (engines that were never closed): the oldest promise is forgotten - its weights are simply rebuilt per call again
   const int victim = (int)(c->frozen_evict++ % MGR_MAX_FROZEN);
   for (int i = 0; i < MGR_MAX_FROZEN; ++i)
-    if (c->planes[i].Wp == c->frozen_w[victim]) c->planes[i] = mgr_ctx::PlaneEntry{nullptr, nullptr, 0, 0};
+    if (c->planes[i].Wp == c->frozen_w[victim]) c->planes[i] = mgr_ctx::PlaneEntry{};
   c->frozen_w[victim] = Wp;
   return 0;
 }

@@ -257,6 +257,7 @@ extern "C" int mgr_mfcc(mgr_ctx* c, const int16_t* samples, const int64_t* sampl
                         int out_stride, const int32_t* loChan, const double* loWt, float* out, const int64_t* out_offsets, void* ws,
                         size_t ws_bytes) {
   MGR_REQUIRE(c && sample_offsets && loChan && loWt && out_offsets && ws, "null argument");
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   MGR_REQUIRE(n_utts >= 1 && n_utts <= 65535, "n_utts must be in [1, 65535]");
   MGR_REQUIRE(n_frames >= 0 && n_frames < (1ll << 40), "bad n_frames");
   MGR_REQUIRE(fftN >= MFCC_MIN_FFT && fftN <= MFCC_MAX_FFT && (fftN & (fftN - 1)) == 0, "fftN must be a power of two in [256, 2048]");

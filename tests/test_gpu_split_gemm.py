@@ -19,6 +19,19 @@ def _split_rows(X, ldt):
     return xs.reshape(B, F, 2 * ldt).view(f32)
 
 
+def _proj_ref(X, M, W, bias):
+    """fp64 statement of the projection with the Keras per-gate input-dropout mask: Z[b, t, 4u + g] = (X[b, t] * M[g, b]) . W[:, 4u + g]
+    + bias[4u + g]; M None = no dropout."""
+    B, T, F = X.shape
+    N = W.shape[1]
+    gate = np.arange(N) % 4
+    ref = np.empty((B, T, N))
+    for g in range(4):
+        Xg = X.astype(np.float64) if M is None else X.astype(np.float64) * M[g][:, None, :]
+        ref[:, :, gate == g] = Xg @ W[:, gate == g].astype(np.float64) + bias[gate == g]
+    return ref
+
+
 @pytest.mark.parametrize("B,T,F,H,p", [(2, 200, 1000, 132, 0.5), (3, 130, 64, 100, 0.5), (2, 257, 1600, 100, 0.5), (1, 128, 48, 300, 0.6),
                                         (2, 90, 16, 20, 0.9), (2, 140, 600, 300, 0.6), (2, 77, 131, 500, 0.4), (2, 64, 160, 40, 1.0),
                                         (2, 100, 96, 64, 0.0)])
@@ -42,10 +55,7 @@ def test_projection_from_split_rows(device, B, T, F, H, p):
     ws = dev.bytes(dev.lib.mgr_lstm_input_proj_dropout_ts_ws_bytes(B, F, H))
     dev.call("mgr_memset", ws, 0xFF, ws.nbytes)              # the workspace arrives dirty
     Z = dev.empty((B, T, N))
-    gate = np.arange(N) % 4
-    ref = np.empty((B, T, N))
-    for g in range(4):
-        ref[:, :, gate == g] = (X.astype(np.float64) * M[g][:, None, :]) @ W[:, gate == g].astype(np.float64) + bias[gate == g]
+    ref = _proj_ref(X, M, W, bias)
     tol = 2e-5 * max(1.0, np.abs(ref).max())
     outs = []
     for tile in (1, 2, 0):        # tune key 12: 128 x 64 tiles (4 waves), 128 x 128 (8 waves), the library's choice
