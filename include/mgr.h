@@ -542,6 +542,23 @@ int mgr_conv_pool_bwd_weights(mgr_ctx* ctx, const float* X, const float* dY, con
 #define MGR_SKELETAL_FEATURE_COLS 23
 int mgr_skeletal_features(mgr_ctx* ctx, const double* joints, size_t n_frames, double* out);
 
+/* ---- activity features of the raw joint files (skeletal_network/velocity.py, r_position.py of the reference), integer
+ * exact.  A ragged batch of n_files files: file f's frames are [offsets[f], offsets[f + 1]) of joints[n_frames][20] = hipX hipY
+ * shcX shcY lsX lsY leX leY lwX lwY lhX lhY rsX rsY reX reY rwX rwY rhX rhY (int32, clamped, within +-2^20; offsets int64 with
+ * offsets[n_files] <= n_frames).  Per file: out[.][5] = lh_v rh_v low lh_dist_rp rh_dist_rp, with lh_v / rh_v = floor of the hand's
+ * Euclidean step from the previous frame (0 in the file's rows 0..3), low = lh_v < mean(lh_v) && rh_v < mean(rh_v) over the file,
+ * rest[f][16] = the truncated medians of lsX .. rhY over the low frames (an even count: (a + b) / 2 of the two middle values,
+ * truncated toward zero), and the distances floor(|rest hand - hand|) (0 in rows 0..3).  rest_given: rest is read instead of
+ * estimated.  status[f] = 0, or 1 when the file has no low-velocity frame (then, unless rest_given, its rest and distances are 0).
+ * One launch, one workgroup per file; deterministic (no atomics on global memory). */
+#define MGR_ACTIVITY_JOINT_COLS 20
+#define MGR_ACTIVITY_REST_COLS 16
+#define MGR_ACTIVITY_OUT_COLS 5
+#define MGR_ACTIVITY_MAX_FILES 65536
+#define MGR_ACTIVITY_MAX_FRAMES (1LL << 26)
+int mgr_skeletal_activity(mgr_ctx* ctx, const int32_t* joints, const int64_t* offsets, int n_files, long long n_frames, int rest_given,
+                          int32_t* rest, int32_t* out, int32_t* status);
+
 /* ---- HTK HCopy-compatible MFCC_0[_D[_A]] front-end of the audio network (README.md: 13 MFCCs + deltas + accelerations, made with
  * HTK's HCopy from config_HCopy; algorithm restated in DESIGN 9c).  A batch of n_utts ragged utterances: samples (raw int16, no
  * scaling) of utterance u are [sample_offsets[u], sample_offsets[u + 1]); it has (N - frameSize) / frameRate + 1 frames when

@@ -83,6 +83,7 @@ SIGNATURES = {
     "mgr_resident_wait_stats": (i32, [vp, vp]),
     "mgr_persist_stats": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
     "mgr_skeletal_features": (i32, [vp, vp, sz, vp]),
+    "mgr_skeletal_activity": (i32, [vp, vp, vp, i32, C.c_longlong, i32, vp, vp, vp]),
     "mgr_mfcc_ws_bytes": (sz, [i32, C.c_longlong, i32, i32, i32, i32]),
     "mgr_mfcc": (i32, [vp, vp, vp, i32, C.c_longlong, i32, i32, i32, i32, i32, i32, C.c_double, i32, i32, i32, vp, vp, vp, vp, vp,
                        sz]),

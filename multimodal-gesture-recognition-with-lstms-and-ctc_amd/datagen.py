@@ -95,7 +95,8 @@ class CsvStore:
                 df = df.drop(columns=[c for c in ('file_number', '39', '40') if c in df.columns])
                 self.audio[int(m[0])] = df.iloc[::audio_stride, :].to_numpy(dtype=float)   # 100 fps MFCC -> 20 fps
         if skeletal_csv is not None:
-            df = pd.read_csv(skeletal_csv)
+            # a path, or the table itself (e.g. skeletal_network.activity.skeletal_tables' train table made from raw joint files)
+            df = skeletal_csv if isinstance(skeletal_csv, pd.DataFrame) else pd.read_csv(skeletal_csv)
             cols = skeletal_columns or SKELETAL_COLUMNS
             data = df[cols].to_numpy(dtype=float)
             data = (data - data.mean(axis=0)) / data.std(axis=0)       # sklearn.preprocessing.scale over the whole file

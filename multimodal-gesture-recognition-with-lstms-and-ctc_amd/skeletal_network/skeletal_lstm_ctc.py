@@ -19,9 +19,11 @@ class DataGenerator(BaseDataGenerator):
 
     def __init__(self, minibatch_size, numfeats, maxlen, val_split, nb_classes, absolute_max_sequence_len=28,
                  in_file='Training_set_skeletal.csv', train_lab_file='../training.csv', synthetic_files=None,
-                 seed=20131902, rank=0, world=1):
+                 seed=20131902, rank=0, world=1, store=None):
         self.numfeats = numfeats
-        if synthetic_files is None and os.path.isfile(in_file) and os.path.isfile(train_lab_file):
+        if store is not None:      # e.g. datagen.CsvStore(None, skeletal_tables(raw joint dir)[0], label_csv)
+            pass
+        elif synthetic_files is None and os.path.isfile(in_file) and os.path.isfile(train_lab_file):
             store = CsvStore(None, in_file, train_lab_file)
         else:
             n = synthetic_files if synthetic_files is not None else 393
