@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """bench.py - headline metric of BASELINE.json on MI355X:
-train frames/sec (+ CTC-loss delta vs the fp64 oracle), fusion BiLSTM+CTC, B=64 per GPU, T=1900.
+train frames/sec, fusion BiLSTM+CTC, B=64 per GPU, T=1900.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -10,7 +10,12 @@ One JSON line on rank 0.  Inputs are synthetic and resident in HBM before the ti
 full training step (frozen encoders fwd, fusion BiLSTM fwd/bwd, CTC, Adam) with device-side noise/dropout
 RNG and one loss read-back, exactly K of them between barrier+sync pairs; value = all ranks' frames / max time.
 The multi-process rendezvous (RCCL unique id) is a plain TCP exchange on MASTER_ADDR:MASTER_PORT+101; torch is not imported.
+A plain run sets up, warms up, times its K steps and prints its line: nothing beside the headline that takes a run of its own.
 
+    python bench.py --full                          # + the legs beside the headline (one rank; full_legs): the same timed steps
+                                                    # on the f32 MFMA kernels, CTC loss and gradients vs the fp64 oracle at B=2,
+                                                    # the oracle's fp32 CPU step at the full shape (~25 s of host work);
+                                                    # --no-f32-leg / --no-parity / --no-cpu leave one out
     python bench.py --steps 20 --dump-outputs DIR   # + DIR/<name>.npy: loss, updated trainable weights and gradients of the
                                                     # last timed step (same arguments, same inputs: two builds compare array by array)
     python bench.py --gpus 2 --comm host      # world > 1 WITHOUT RCCL: gradients are summed on the host (parallel.HostComm);
@@ -100,6 +105,23 @@ def _spawn_ranks(n):
     return rc
 
 
+def full_legs(args, world):
+    """What a run measures beside its headline: nothing unless --full.  With it, on one rank: "f32" - the timed steps once more on
+    the f32 MFMA kernels (unless --tune already put the headline there), "parity" - CTC loss and gradients against the fp64
+    oracle, "cpu" - the oracle's fp32 step on the host; --no-f32-leg / --no-parity / --no-cpu leave one out."""
+    if not args.full or world != 1:
+        return set()
+    tuned = dict(kv.split("=") for kv in args.tune)
+    legs = set()
+    if not args.no_f32_leg and tuned.get("14", "0") == "0" and tuned.get("15", "0") == "0":
+        legs.add("f32")
+    if not args.no_parity:
+        legs.add("parity")
+    if not args.no_cpu:
+        legs.add("cpu")
+    return legs
+
+
 class Watchdog:
     """A rank that makes no progress for `limit` seconds ends itself with exit code 3 (os._exit from a timer thread: no exec, no
     cleanup that could block on the GPU).  Under torch.distributed.run the launcher then terminates the other ranks; under
@@ -127,7 +149,7 @@ class Watchdog:
                 os._exit(3)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -135,12 +157,14 @@ def main():
     ap.add_argument("--config", default="F")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override")
     ap.add_argument("--maxlen", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the legs beside the headline (one rank): f32 MFMA leg, fp64-oracle parity, CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--show-plan", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true", help="do not overlap the next step's frozen-encoder pass")
     ap.add_argument("--scan-path", type=int, default=0, help="0 auto, 3/4 clusters of 4/8 tiles per workgroup")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-f32-leg", action="store_true", help="skip the second timed leg on the f32 MFMA kernels (tune 14 = 15 = 1)")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the CTC parity against the fp64 oracle")
+    ap.add_argument("--no-f32-leg", action="store_true", help="--full without the second timed leg on the f32 MFMA kernels (tune 14 = 15 = 1)")
     ap.add_argument("--tune", action="append", default=[], help="KEY=VALUE for mgr_tune (A/B of kernel variants; may be repeated)")
     ap.add_argument("--no-transposed", action="store_true", help="dropout-aware projections gather columns of the row-major input")
     ap.add_argument("--scan-with-fproj", action="store_true", help="the deepest encoder scan starts together with the fusion projections (round 4)")
@@ -169,10 +193,14 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="after the timed steps, write what the last one computed (loss, updated trainable weights, their gradients) "
                          "as DIR/<name>.npy - rank 0, before the f32 leg")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         raise SystemExit("bench.py: --steps must be at least 1")
+    return args
 
+
+def main():
+    args = parse_args()
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -312,9 +340,9 @@ def main():
 
     # ---- the same K steps on the f32 MFMA kernels (tune keys 14 = 15 = 1), same process, same warm-up: the strict-f32 time beside
     # the split-f16 headline.  `value` above is never touched by it.
+    legs = full_legs(args, world)
     f32_leg = None
-    tuned0 = dict(kv.split("=") for kv in args.tune)
-    if not args.no_f32_leg and world == 1 and tuned0.get("14", "0") == "0" and tuned0.get("15", "0") == "0":
+    if "f32" in legs:
         dev.call("mgr_tune", 14, 1)
         dev.call("mgr_tune", 15, 1)
         try:
@@ -381,10 +409,10 @@ def main():
         # ---- parity: same weights / batch / injected randomness on a short-T slice vs the fp64 oracle ----
         parity = None
         dog.limit = max(dog.limit, 600.0) if dog.limit > 0 else 0   # (the CPU legs below are minutes of host work, not a hang)
-        if not args.no_parity and world == 1:
+        if "parity" in legs:
             parity = loss_parity(spec, dev, T, dict(kv.split("=") for kv in args.tune))
         cpu = None
-        if not args.no_cpu and world == 1:   # the CPU leg is reported at N=1 only (torchrun also pins OMP_NUM_THREADS=1)
+        if "cpu" in legs:   # the CPU leg is reported at N=1 only (torchrun also pins OMP_NUM_THREADS=1)
             cpu_T = args.cpu_T or T
             cpu_B = args.cpu_B or B
             v, sec, _ = cpu_baseline(spec.to_dict(), 7, cpu_T, cpu_B)

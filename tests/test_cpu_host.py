@@ -339,6 +339,26 @@ def test_bench_launcher_hands_out_distinct_local_ranks_and_rank_r_binds_device_r
         bench.rank_device(0, 0, 1, "rccl")
 
 
+def test_bench_plain_run_takes_no_leg_beside_the_headline():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` sets up, warms up, times its steps and prints its line; the f32 MFMA leg,
+    the parity against the fp64 oracle and the CPU baseline run with --full only, on one rank, each left out by its --no-* switch."""
+    import bench
+
+    def legs(*argv, world=1):
+        return bench.full_legs(bench.parse_args(list(argv)), world)
+
+    assert not bench.parse_args([]).full
+    assert legs("--gpus", "1", "--steps", "5", "--warmup", "2") == set()
+    assert legs("--no-cpu", "--no-parity", "--no-f32-leg") == set()
+    assert legs("--full") == {"f32", "parity", "cpu"}
+    assert legs("--full", "--no-cpu") == {"f32", "parity"}
+    assert legs("--full", "--no-parity", "--no-f32-leg") == {"cpu"}
+    assert legs("--full", "--tune", "15=1") == {"parity", "cpu"}     # the headline already runs on the f32 kernels
+    assert legs("--full", world=2) == set()
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
 def test_effective_cores_honours_the_cgroup_quota_and_import_caps_blas_pools(tmp_path):
     """mgr_amd/_hostenv.py: the GPU boxes show 256 cores and grant 16 cores' worth of CPU time; a BLAS pool sized by the core
     count got the whole process frozen for tens of ms (profiles/r03_host_stalls.txt).  Importing the package (before numpy

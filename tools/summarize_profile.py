@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Summarise gpurun_out/<tag>_* (bench JSON, rocprofv3 kernel stats, PMC passes) into profiles/<tag>_summary.md
-and copy the raw per-kernel CSV summaries next to it."""
+"""Summarise $OUT/<tag>_* (what tools/profile_round.sh wrote: bench JSON, rocprofv3 kernel stats, PMC passes; OUT defaults to
+out/) into profiles/<tag>_summary.md and copy the raw per-kernel CSV summaries next to it."""
 import collections
 import csv
 import json
@@ -10,7 +10,7 @@ import shutil
 import sys
 
 tag = sys.argv[1]
-G = "gpurun_out"
+G = os.environ.get("OUT", "out")
 os.makedirs("profiles", exist_ok=True)
 
 
