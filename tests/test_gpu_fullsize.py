@@ -109,29 +109,17 @@ def test_config_F_full_size_step_and_pipelined_determinism(device):
     assert st.value == 0
 
 
-def _oracle_chunk(args):
-    """Pool worker: the oracle's loss_and_grads on a slice of the batch, in fp64 and in fp32 (the error model of
-    tests/test_gpu_baseline_configs.py).  The gradients come back scaled to the FULL batch's mean (x chunk / B)."""
-    sd, w, xs, labels, il, ll, rand, B = args
-    n = labels.shape[0]
-    w64 = {k: v.astype(np.float64) for k, v in w.items()}
-    _, lb64, g64, _ = nr.loss_and_grads(sd, w64, xs, labels, il, ll, rand)
-    f32 = lambda d: {k: (None if v is None else np.asarray(v, np.float32)) for k, v in d.items()}
-    _, _, g32, _ = nr.loss_and_grads(sd, f32(w), f32(xs), labels, il, ll, f32(rand))
-    return lb64, {k: v * (n / B) for k, v in g64.items()}, {k: v.astype(np.float64) * (n / B) for k, v in g32.items()}
-
-
 @pytest.mark.slow
 def test_config_F_bench_shape_every_sample_and_the_gradients_against_the_oracle(device):
     """BASELINE configs[2] at the bench line's own shape, B = 64, T = 1900, injected randomness: ALL 64 per-sample CTC losses
     (1e-4 relative, north_star's bound) and every trainable gradient against the fp64 oracle: within 1e-4 of the tensor's largest
     entry (the kernels measure 1e-5; the distance of the SAME oracle run in float32 is printed beside it).  B = 64 means 4 batch groups x 2 directions x multi-CU clusters in every scan - what the
-    B = 2 full-T case cannot show.  The oracle runs in a process pool forked from the clean fork server (8 slices of 8 samples)."""
+    B = 2 full-T case cannot show.  The oracle runs in a process pool forked from the clean fork server (8 slices of 8 samples,
+    tests/helpers.py:oracle_by_slices)."""
     from mgr_amd.configs import baseline_config
     from mgr_amd.engine import Engine
     from mgr_amd.synthetic import synthetic_arrays, synthetic_weights
-    from multiprocessing import forkserver
-    from tests.helpers import rel_err
+    from tests.helpers import oracle_by_slices, rel_err
     spec, B, T, Lmax = baseline_config("F")
     assert (B, T) == (64, 1900)
     w = synthetic_weights(spec, 20131900 + 3)
@@ -145,23 +133,12 @@ def test_config_F_bench_shape_every_sample_and_the_gradients_against_the_oracle(
     g = eng.get_grads()
     eng._check_scans()
     eng.close()
-    jobs = []
-    for i in range(0, B, 8):
-        sub = slice(i, i + 8)
-        r2 = {k: (v[:, sub] if (k.endswith("/mask") and k != "head/mask") else v[sub]) for k, v in rand.items()}
-        jobs.append((sd, w, {k: v[sub] for k, v in xs.items()}, labels[sub], il[sub], ll[sub], r2, B))
-    if getattr(forkserver._forkserver, "_forkserver_pid", None) is not None:
-        with mp.get_context("forkserver").Pool(8) as pool:
-            res = pool.map(_oracle_chunk, jobs)
-    else:
-        res = [_oracle_chunk(j) for j in jobs]
-    ref_lb = np.concatenate([r[0] for r in res])
+    ref = oracle_by_slices(sd, w, xs, labels, il, ll, rand, chunk=8)               # 8 slices x (fp64, numpy float32) = 16 jobs
+    ref_lb = ref["lb"]
     assert np.allclose(lb, ref_lb, rtol=1e-4), np.abs(lb / ref_lb - 1).max()        # every one of the 64 samples
-    assert set(g) == set(res[0][1])
+    assert set(g) == set(ref["g"])
     for k in g:
-        ref = sum(r[1][k] for r in res)
-        r32 = sum(r[2][k] for r in res)
-        eg, eg32 = rel_err(g[k], ref), rel_err(r32, ref)
+        eg, eg32 = rel_err(g[k], ref["g"][k]), rel_err(ref["g32"][k], ref["g"][k])
         print("   grad %-20s gpu %.2e, numpy-f32 %.2e" % (k, eg, eg32))
         # (round 5: the bound is what the kernels achieve with a margin of ten - measured 8e-6 ... 2e-5 - not the 5e-3 of the
         # numpy-float32 error model: a regression of the split-f16 path by one order of magnitude fails here)
@@ -188,9 +165,9 @@ def test_config_D_decode_full_set_matches_oracle_on_every_sequence(device):
     g_beam, g_scores = decoding.beam_search_decode(P, il, beam_width=beam, dev=device)
     g_greedy = decoding.greedy_decode(P, 0.5, dev=device)
     chunks = [(P[i:i + 6], il[i:i + 6], beam) for i in range(0, N, 6)]
-    from multiprocessing import forkserver
-    if getattr(forkserver._forkserver, "_forkserver_pid", None) is not None:
-        with mp.get_context("forkserver").Pool(min(46, os.cpu_count() or 1)) as pool:
+    from tests.helpers import ORACLE_CPUS, fork_server_running
+    if fork_server_running():
+        with mp.get_context("forkserver").Pool(min(ORACLE_CPUS, os.cpu_count() or 1)) as pool:
             res = pool.map(_oracle_decode_chunk, chunks)
     else:
         res = [_oracle_decode_chunk(c) for c in chunks]
