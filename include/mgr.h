@@ -514,6 +514,37 @@ int mgr_ctc_beam_search(mgr_ctx* ctx, const float* P, const int32_t* input_len, 
                         int blank, int beam, float eps, int merge_repeated, int32_t* out, int32_t* out_len,
                         double* logp, void* ws, size_t ws_bytes);
 
+/* ---- K11: locating gestures in time.  The reference "spots and classifies gestures from two continuous streams" and keeps
+ * only the label sequence (sequence_decoding.py:38-53 of each network); these two calls keep the frame positions as well. ---- */
+/* Viterbi forced alignment: the single most probable CTC alignment of each sample's label sequence.  Conventions are those of
+ * mgr_ctc_loss_grad, argument for argument: P[:, skip:, :], y = softmax(log(P+eps)), labels int32 [B,Lmax] padded -1 (values outside
+ * the class range are clipped into it, as there), blank = C-1 in the reference, ws >= mgr_ctc_align_ws_bytes.
+ *   path [B,T-skip] int32: the class emitted at each frame (a label or blank); -1 from input_len on.
+ *   seg  [B,Lmax,2] int32: first and last frame (inclusive, indices of the ORIGINAL sequence: t + skip) at which label k is
+ *                          emitted; -1 for k >= label_len.  Blank stretches are not reported.
+ *   conf [B,Lmax] float:   mean of P[b,t,l_k] (the raw softmax, what the reference's threshold looks at) over those frames; 0 for
+ *                          k >= label_len.
+ *   logp [B] double:       natural-log probability of the path under y.
+ * Ties: a back-pointer tie takes the smallest step (stay, one state, two states), a tie of the two final states the last blank; the
+ * step over two states is allowed only onto a label that differs from the previous one, as in the loss.  Edge cases: label_len 0
+ * gives an all-blank path and no segments; a label sequence that does not fit its input length (where the loss is +inf), or an
+ * input length of 0, gives logp = -inf, path and seg -1, conf 0 for that sample, the other samples of the batch are unaffected.
+ * Deterministic; samples are independent of each other (a sample's result does not depend on the rest of the batch). */
+size_t mgr_ctc_align_ws_bytes(int B, int T, int C, int Lmax);
+int mgr_ctc_align(mgr_ctx* ctx, const float* P, const int32_t* labels, const int32_t* input_len, const int32_t* label_len, int B, int T,
+                  int C, int Lmax, int skip, int blank, float eps, int32_t* path, int32_t* seg, float* conf, double* logp, void* ws,
+                  size_t ws_bytes);
+/* The greedy decode of K9 with its frame positions, all on the device: frame argmax (first index on ties), the reference's confidence
+ * filter in its net effect (sequence_decoding.py:45-48: for every label s the first k_s frames whose best label is s are dropped, k_s
+ * = the number of frames whose best label is s with probability < thr, compared in float32; thr < 0: no filter), then the collapse of
+ * equal neighbours among the surviving frames.  Per sample: n_runs [B] = the number of runs - the TRUE count, also when it exceeds cap -
+ * and for run r < min(n_runs, cap): lab [B,cap] its label (blank runs are kept), seg [B,cap,2] the original indices (t + skip) of its
+ * first and last surviving frame, conf [B,cap] the mean of the frame maxima over its surviving frames; rows n_runs <= r < cap hold
+ * -1, -1, 0.  n_runs can reach T - skip.  Needs no workspace (the per-frame arrays live in LDS): T - skip <= MGR_SEGMENTS_MAX_FRAMES. */
+#define MGR_SEGMENTS_MAX_FRAMES 8192
+int mgr_greedy_segments(mgr_ctx* ctx, const float* P, int B, int T, int C, int skip, float thr, int cap, int32_t* n_runs, int32_t* lab,
+                        int32_t* seg, float* conf);
+
 /* ---- K10: TimeDistributed CNN front-end of the RGB network (rgb_network/cnn_lstm.py: conv_1 / conv_3 / conv_5, each followed by
  * MaxPooling2D) ------------------------------------------------------------------------------------------------------------------
  * Per frame of N = B*T frames, channels-last: X [N][Hin][Win][Cin] -> valid Conv2D (W [ks][ks][Cin][Cout], b [Cout]) -> ReLU ->

@@ -1,7 +1,7 @@
 """Decode for the audio network (reference audio_network/sequence_decoding.py:19-69): word-level classes, thr .75."""
 import numpy as np
 
-from ..decoding import greedy_decode, greedy_decode_argmax, write_mlf
+from ..decoding import greedy_decode, greedy_decode_argmax, greedy_segments, write_mlf
 
 _words = ["oov", "Vattene", "Vieni", "qui", "Perfetto", "E'", "un", "furbo", "Che", "due", "palle", "vuoi", "Vanno",
           "d'accordo", "Sei", "Pazzo", "Cos'hai", "combinato", "Non", "me", "ne", "frega", "niente", "ok", "Cosa", "ti",
@@ -28,3 +28,15 @@ def decode_argmax(best, prob, f_list, out_file=None):
     if out_file is not None:
         write_mlf(out_file, ret, f_list, ignore_list, "Sample%05d_audio")
     return ret
+
+
+def decode_segments(pred_out, f_list, out_file="ctc_recout_timed.mlf"):
+    """decode_batch with start and end times: pred_out (N, T, C) softmax - or the per-sample segment lists that
+    Model.predict_generator(decode="segments", threshold=THRESHOLD) computed on the device.  The same filter, collapse, class map and
+    ignore list; every MLF line reads "start end name" in HTK's 100 ns units (50 ms per frame).  The times are the frames at which the
+    network commits to the class, not the extent of the movement.  Returns (label-name lists, segment lists)."""
+    segs = pred_out if isinstance(pred_out, list) else greedy_segments(np.asarray(pred_out), THRESHOLD, skip=2)
+    ret = [[map_gest[s[0]] for s in sg] for sg in segs]
+    if out_file is not None:
+        write_mlf(out_file, ret, f_list, ignore_list, "Sample%05d_audio", segments=segs)
+    return ret, segs

@@ -1,7 +1,7 @@
 """Decode helpers shared by the three sequence_decoding modules (K9).
 
 Frame-wise max / argmax runs on the GPU (mgr_frame_argmax); the reference's confidence filter and the
-repeat collapse run on the host.  The filter reproduces the NET EFFECT of the reference's Python-2 loop
+repeat collapse run on the host (greedy_decode) or, with the frame positions kept, on the GPU (greedy_segments).  The filter reproduces the NET EFFECT of the reference's Python-2 loop
 (multimodal_fusion/sequence_decoding.py:45-48: ``list.remove`` deletes the first element equal to the value,
 not the visited one): for every label s, the first k_s occurrences of s are dropped, where k_s is the number
 of frames whose best label is s with probability below the threshold.  Blanks are kept (they decode to "sil").
@@ -69,17 +69,129 @@ def greedy_decode_argmax(best, prob, thr):
     return [confidence_filter_collapse(best[j], prob[j], thr) for j in range(best.shape[0])]
 
 
-def write_mlf(path, decoded_names, f_list, ignore_list, name_fmt="Sample%05d"):
-    """HTK master label file in the reference's layout (sequence_decoding.py:35-36,57-65)."""
+# HTK label times are in 100 ns units.  One network frame is 50 ms in every modality: the skeletal stream is Kinect's 20 frames / s, and
+# the audio stream is 10 ms MFCC frames of which every data_generator of the reference takes every fifth (iloc[::5]).
+FRAME_PERIOD_HTK = 500000
+
+
+def write_mlf(path, decoded_names, f_list, ignore_list, name_fmt="Sample%05d", segments=None, frame_period=FRAME_PERIOD_HTK):
+    """HTK master label file in the reference's layout (sequence_decoding.py:35-36,57-65).
+    segments (optional): per sample one (label, first_frame, last_frame, confidence) tuple per name - what greedy_segments /
+    forced_align return; each line then reads "start end name" in HTK's 100 ns units, start = first_frame * frame_period and end =
+    (last_frame + 1) * frame_period (the end of the last frame).  Without segments the file is the reference's, byte for byte."""
     with open(path, "w") as of:
         of.write("#!MLF!#\n")
-        for names, f_num in zip(decoded_names, f_list):
+        for j, (names, f_num) in enumerate(zip(decoded_names, f_list)):
             if int(f_num) in ignore_list:
                 continue
             of.write('"*/%s.rec"\n' % (name_fmt % int(f_num)))
-            for cl in names:
-                of.write("%s\n" % cl)
+            if segments is None:
+                for cl in names:
+                    of.write("%s\n" % cl)
+            else:
+                if len(segments[j]) != len(names):
+                    raise ValueError("sample %d: %d segments for %d names" % (j, len(segments[j]), len(names)))
+                for cl, sg in zip(names, segments[j]):
+                    of.write("%d %d %s\n" % (int(sg[1]) * int(frame_period), (int(sg[2]) + 1) * int(frame_period), cl))
             of.write(".\n")
+
+
+def greedy_segments(pred_out, thr, skip=2, dev=None, max_segments=256):
+    """greedy_decode with the frame positions it discards, all on the GPU (mgr_greedy_segments): per sample a list of
+    (label, first_frame, last_frame, confidence) - the run's label (blanks kept), the indices in the ORIGINAL sequence (t + skip) of its
+    first and last surviving frame, and the mean of the frame maxima over its surviving frames.  The labels are those of
+    greedy_decode(pred_out, thr, skip).  max_segments sizes the first download; a sample with more runs (the device always reports the
+    true count) makes the call run again with room for T - skip."""
+    dev = dev or default_device()
+    P = np.ascontiguousarray(pred_out, dtype=np.float32)
+    N, T, Cn = P.shape
+    dP = dev.array(P)
+    dn = dev.empty((N,), np.int32)
+    try:
+        cap = max(1, min(T - skip, int(max_segments)))
+        while True:
+            dl, ds, dc = dev.empty((N, cap), np.int32), dev.empty((N, cap, 2), np.int32), dev.empty((N, cap), np.float32)
+            dev.call("mgr_greedy_segments", dP, N, T, Cn, skip, C.c_float(-1.0 if thr is None else float(thr)), cap, dn, dl, ds, dc)
+            n = dn.download()
+            if int(n.max()) <= cap:
+                lab, seg, conf = dl.download(), ds.download(), dc.download()
+            for a in (dl, ds, dc):
+                a.free()
+            if int(n.max()) <= cap:
+                break
+            cap = T - skip
+    finally:
+        dP.free()
+        dn.free()
+    return segments_from_arrays(n, lab, seg, conf)
+
+
+def segments_from_arrays(n, lab, seg, conf):
+    """The (count, label, [first, last], confidence) arrays of mgr_greedy_segments -> per sample a list of tuples.  Raises when a
+    sample has more runs than the arrays hold."""
+    cap = lab.shape[1]
+    if len(n) and int(np.max(n)) > cap:
+        raise OverflowError("a sample has %d runs, the output holds %d per sample" % (int(np.max(n)), cap))
+    return [[(int(lab[b, r]), int(seg[b, r, 0]), int(seg[b, r, 1]), float(conf[b, r])) for r in range(int(n[b]))] for b in range(len(n))]
+
+
+def pack_labels(labels, label_length=None):
+    """A padded array (-1 or NaN padding, as the generators' the_labels) or a list of label lists -> (int32 (N, Lmax) padded -1,
+    int32 (N,) lengths)."""
+    if isinstance(labels, np.ndarray) or (len(labels) and np.ndim(labels[0]) == 0):
+        lab = np.atleast_2d(np.asarray(labels, dtype=np.float64))
+        lab = np.where(np.isfinite(lab) & (lab >= 0), lab, -1).astype(np.int32)
+    else:
+        Lmax = max([len(r) for r in labels] + [1])
+        lab = -np.ones((len(labels), Lmax), np.int32)
+        for i, r in enumerate(labels):
+            lab[i, :len(r)] = np.asarray(r, np.int32)
+    if lab.shape[1] == 0:
+        lab = -np.ones((lab.shape[0], 1), np.int32)
+    ll = (lab >= 0).sum(axis=1).astype(np.int32) if label_length is None else np.asarray(label_length).reshape(-1).astype(np.int32)
+    return np.ascontiguousarray(lab), ll
+
+
+def alignment_from_arrays(lab, ll, seg, conf, logp):
+    """mgr_ctc_align's seg / conf arrays -> per sample a list of (label, first_frame, last_frame, confidence); a sample whose
+    labels do not fit its input (logp = -inf) has no segments."""
+    out = []
+    for b in range(lab.shape[0]):
+        n = 0 if not np.isfinite(logp[b]) else min(int(ll[b]), lab.shape[1])
+        out.append([(int(lab[b, k]), int(seg[b, k, 0]), int(seg[b, k, 1]), float(conf[b, k])) for k in range(n)])
+    return out
+
+
+def forced_align(pred_out, labels, label_length=None, input_length=None, skip=2, dev=None, return_path=False, eps=1e-8):
+    """Viterbi forced alignment on the GPU (mgr_ctc_align): the single most probable CTC alignment of each sample's label sequence to
+    its posteriors, under the loss's conventions (frames skip .., y = softmax(log(P + eps)), blank = C - 1).
+    Returns (segments, logp[, path]): per sample a list of (label, first_frame, last_frame, confidence) - the frames, as indices of the
+    ORIGINAL sequence, at which the path emits the label, and the mean of P[t, label] over them; logp (N,) float64, the natural-log
+    probability of the path (-inf and no segments where the labels do not fit the input length); path (N, T - skip) int32, the class
+    emitted at every frame (-1 past the input length).  A CTC-trained network emits short spikes: the frames are where the network
+    commits to the gesture, not the extent of the movement."""
+    dev = dev or default_device()
+    P = np.ascontiguousarray(pred_out, dtype=np.float32)
+    N, T, Cn = P.shape
+    lab, ll = pack_labels(labels, label_length)
+    if lab.shape[0] != N:
+        raise ValueError("%d label rows for %d samples" % (lab.shape[0], N))
+    il = np.full(N, T - skip, np.int32) if input_length is None else np.asarray(input_length).reshape(N).astype(np.int32)
+    Lmax = lab.shape[1]
+    dP, dlab, dil, dll = dev.array(P), dev.array(lab), dev.array(il), dev.array(ll)
+    dpath, dseg = dev.empty((N, T - skip), np.int32), dev.empty((N, Lmax, 2), np.int32)
+    dconf, dlogp = dev.empty((N, Lmax), np.float32), dev.empty((N,), np.float64)
+    ws = dev.bytes(dev.lib.mgr_ctc_align_ws_bytes(N, T, Cn, Lmax))
+    try:
+        dev.call("mgr_ctc_align", dP, dlab, dil, dll, N, T, Cn, Lmax, skip, Cn - 1, C.c_float(eps), dpath, dseg, dconf, dlogp, ws, ws.nbytes)
+        seg, conf, logp = dseg.download(), dconf.download(), dlogp.download()
+        path = dpath.download() if return_path else None
+    finally:
+        for a in (dP, dlab, dil, dll, dpath, dseg, dconf, dlogp, ws):
+            a.free()
+    clipped = np.clip(lab, 0, Cn - 1)     # (what the kernels align: out-of-range values clipped into the class range, as the loss)
+    segs = alignment_from_arrays(clipped, ll, seg, conf, logp)
+    return (segs, logp, path) if return_path else (segs, logp)
 
 
 def beam_search_decode(pred_out, input_length=None, beam_width=10, skip=2, merge_repeated=True, dev=None):

@@ -2,7 +2,7 @@
 0.97 confidence threshold, the list.remove quirk, collapse, MLF."""
 import numpy as np
 
-from ..decoding import greedy_decode, write_mlf
+from ..decoding import greedy_decode, greedy_segments, write_mlf
 from ..multimodal_fusion.sequence_decoding import ignore_list, map_gest
 
 THRESHOLD = 0.97
@@ -13,3 +13,15 @@ def decode_batch(pred_out, f_list, out_file="final_ctc_recout.mlf"):
     ret = [[map_gest[i] for i in seq] for seq in ids]
     write_mlf(out_file, ret, f_list, ignore_list, "Sample%05d")
     return ret
+
+
+def decode_segments(pred_out, f_list, out_file="final_ctc_recout_timed.mlf"):
+    """decode_batch with start and end times: pred_out (N, T, C) softmax - or the per-sample segment lists that
+    Model.predict_generator(decode="segments", threshold=THRESHOLD) computed on the device.  The same filter, collapse, class map and
+    ignore list; every MLF line reads "start end name" in HTK's 100 ns units (50 ms per frame).  The times are the frames at which the
+    network commits to the class, not the extent of the movement.  Returns (label-name lists, segment lists)."""
+    segs = pred_out if isinstance(pred_out, list) else greedy_segments(np.asarray(pred_out), THRESHOLD, skip=2)
+    ret = [[map_gest[s[0]] for s in sg] for sg in segs]
+    if out_file is not None:
+        write_mlf(out_file, ret, f_list, ignore_list, "Sample%05d", segments=segs)
+    return ret, segs

@@ -1005,7 +1005,7 @@ class Engine:
     EV_D1P = (55, 56)     # the depth-1 projections into depth-1 Z set 0 / 1 are done (stream 0)
     EV_D1S = (57, 58)     # the depth-1 scans that read depth-1 Z set 0 / 1 are done (stream ES)
 
-    def predict_stream(self, batches, output="posteriors", train_phase=False, beam_width=10, merge_repeated=True):
+    def predict_stream(self, batches, output="posteriors", train_phase=False, beam_width=10, merge_repeated=True, threshold=None):
         """Batches of an inference / validation run are independent of each other: this generator keeps two of them in flight.
         Batch n + 1 is uploaded (copy stream) and runs its encoder pass (stream ES, into the other FEAT buffer) beside batch n's
         fusion layer / head / decode kernels (stream 0) and beside the download of batch n - 1's result (its own stream, into
@@ -1013,20 +1013,27 @@ class Engine:
         predict_generator over the whole set (sequence_decoding.py:118-127) and with the validation loop of every epoch
         (multimodal.py:264-269), one blocking batch at a time.
 
-        batches: iterable of input dicts {stream name: (B, T, F)} - for output="loss" of tuples (inputs, labels, input_length,
-        label_length).  Yields, in order, per batch:
+        batches: iterable of input dicts {stream name: (B, T, F)} - for output="loss" and "align" of tuples (inputs, labels,
+        input_length, label_length).  Yields, in order, per batch:
           "posteriors"  P (B, T, C) float32                  (learning phase 0 unless train_phase)
           "argmax"      (best (B, T - skip) int32, prob (B, T - skip) float32): mgr_frame_argmax on the device, the (B, T, C)
                         posteriors never travel to the host (decoding.confidence_filter_collapse does the rest)
           "beam"        (paths: list of B label lists, log-probabilities (B,) float64): mgr_ctc_beam_search on the device
           "loss"        per-sample CTC losses (B,) float32  (a training engine; learning phase as train_phase)
+          "segments"    list of B lists of (label, first_frame, last_frame, confidence): mgr_greedy_segments(threshold) on the device
+                        where "argmax" runs mgr_frame_argmax - the greedy decode with its frame positions (decoding.greedy_segments)
+          "align"       (segments: list of B lists of (label, first_frame, last_frame, confidence), logp (B,) float64, path
+                        (B, T - skip) int32): mgr_ctc_align of each sample's labels to its posteriors (a training engine, like "loss")
         Results are bit-identical to the one-batch-at-a-time calls (predict / loss_on_batch): same kernels, same order per batch."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         Cn, skip = sp.num_classes, int(sp.ctc["skip"])
-        if output not in ("posteriors", "argmax", "beam", "loss"):
+        if output not in ("posteriors", "argmax", "beam", "loss", "segments", "align"):
             raise ValueError("unknown output %r" % (output,))
         if output == "loss" and self.inference_only:
             raise ValueError("output='loss' needs a training engine (labels, CTC workspace)")
+        if output == "align" and self.inference_only:
+            raise ValueError("output='align' needs a training engine (labels)")
+        labelled = output in ("loss", "align")
         self._bind()
         if self._prefetched is not None:     # a pipelined training encoder pass is in flight: let it finish, then discard it
             dev.wait(0, self.ES)
@@ -1059,6 +1066,22 @@ class Engine:
             wsb = bufs("wsb%d" % beam_width, lambda: self.mem.bytes(self.lib.mgr_ctc_beam_ws_bytes(B, T, Cn, int(beam_width))))
             pins = bufs("beam", lambda: [(dev.pinned((B, T - skip), np.int32), dev.pinned((B,), np.int32), dev.pinned((B,), np.float64))
                                          for _ in range(2)])
+        elif output == "segments":
+            # room for T - skip runs per sample, the most there can be: the count the kernel reports never exceeds what is downloaded
+            cap = T - skip
+            dseg = bufs("dseg", lambda: (self.mem.empty((B,), np.int32), self.mem.empty((B, cap), np.int32),
+                                         self.mem.empty((B, cap, 2), np.int32), self.mem.empty((B, cap), np.float32)))
+            pins = bufs("seg", lambda: [(dev.pinned((B,), np.int32), dev.pinned((B, cap), np.int32), dev.pinned((B, cap, 2), np.int32),
+                                         dev.pinned((B, cap), np.float32)) for _ in range(2)])
+        elif output == "align":
+            Lm = self.Lmax
+            # one set of device outputs per output slot, like the losses below
+            aring = bufs("aring", lambda: [(self.mem.empty((B, T - skip), np.int32), self.mem.empty((B, Lm, 2), np.int32),
+                                            self.mem.empty((B, Lm), np.float32), self.mem.empty((B,), np.float64)) for _ in range(2)])
+            wsa = bufs("wsa", lambda: self.mem.bytes(self.lib.mgr_ctc_align_ws_bytes(B, T, Cn, Lm)))
+            pins = bufs("align", lambda: [(dev.pinned((B, T - skip), np.int32), dev.pinned((B, Lm, 2), np.int32),
+                                           dev.pinned((B, Lm), np.float32), dev.pinned((B,), np.float64)) for _ in range(2)])
+            host_labels = {}
         else:
             pins = bufs("loss", lambda: [dev.pinned((B,), np.float32) for _ in range(2)])
             # one device buffer per output slot, like pring: batch i's copy (its own stream, behind EV_FUSED only) must not find
@@ -1077,6 +1100,14 @@ class Engine:
             elif output == "beam":
                 po, pl, ps = pins[o]
                 r = ([[int(v) for v in po[b, :pl[b]]] for b in range(B)], ps.copy())
+            elif output == "segments":
+                from .decoding import segments_from_arrays
+                r = segments_from_arrays(*pins[o])
+            elif output == "align":
+                from .decoding import alignment_from_arrays
+                lab, ll = host_labels.pop(i)
+                ppath, pseg, pconf, plogp = pins[o]
+                r = (alignment_from_arrays(np.clip(lab, 0, Cn - 1), ll, pseg, pconf, plogp), plogp.copy(), ppath.copy())
             else:
                 r = pins[o].copy()
             # the status block of THIS batch's pass travels with its result (no extra synchronisation): the samples whose hidden
@@ -1107,7 +1138,7 @@ class Engine:
         def start_encoders(i, item):
             """Upload batch i and enqueue its noise / depth-1 projections on stream 0 (two_stage), or nothing yet; returns the
             generator that enqueues the rest of its encoder pass on ES."""
-            inputs = item[0] if output == "loss" else item
+            inputs = item[0] if labelled else item
             f = i % len(ring)
             first = 0 if two_stage else ES
             self._upload_inputs(inputs, None, train_phase, stream=first)
@@ -1178,8 +1209,10 @@ class Engine:
                     # whole life (13.1 instead of 8.3 ms: profiles/r04_predict_timeline.txt) - they wait until it is resident
                     wait_resident(scan_seq[(i + 1) & 1, 0], self.schedule.resident_wait_us)
                 dev.wait_event(0, self.EV_OUT[o])               # batch i - 2's decode / download read the P buffer this pass overwrites
-                if output == "loss":
+                if labelled:
                     self._upload_labels(item[1], item[2], item[3])
+                if output == "align":
+                    host_labels[i] = (self._lab_pin[self._lab_slot][0].copy(), np.asarray(item[3]).reshape(B).astype(np.int32))
                 self.P = pring[o]
                 self._bind(self._pass_status[o])        # (batch i + 1's encoder pass, enqueued above, bound the other block)
                 self._enqueue_fusion_head(train_phase, None, ring[f], self.rng_step + (i - started[0]))
@@ -1187,6 +1220,11 @@ class Engine:
                 if output == "loss":
                     dev.call("mgr_ctc_loss_grad", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1,
                              float(sp.ctc["eps"]), 1.0, lring[o], 0, self.ws_ctc, self.ws_ctc.nbytes)
+                    dev.record(self.EV_LAB[self._lab_slot])
+                    self._lab_user[self._lab_slot] = 1 << 60
+                elif output == "align":
+                    dev.call("mgr_ctc_align", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1,
+                             C.c_float(float(sp.ctc["eps"])), *aring[o], wsa, wsa.nbytes)
                     dev.record(self.EV_LAB[self._lab_slot])
                     self._lab_user[self._lab_slot] = 1 << 60
                 dev.record(self.EV_FUSED[f])
@@ -1205,6 +1243,14 @@ class Engine:
                     dev.d2h_async(pins[o][0], dout)
                     dev.d2h_async(pins[o][1], dlen)
                     dev.d2h_async(pins[o][2], dlogp)
+                elif output == "segments":
+                    dev.call("mgr_greedy_segments", pring[o], B, T, Cn, skip, C.c_float(-1.0 if threshold is None else float(threshold)),
+                             cap, *dseg)
+                    for k in range(4):
+                        dev.d2h_async(pins[o][k], dseg[k])
+                elif output == "align":
+                    for k in range(4):
+                        dev.d2h_async(pins[o][k], aring[o][k])
                 else:
                     dev.d2h_async(pins[o], lring[o])
                 dev.d2h_async(spin[o], self._pass_status[o])

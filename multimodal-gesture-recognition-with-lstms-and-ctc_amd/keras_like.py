@@ -555,13 +555,15 @@ class Model:
         pad = lambda a: np.concatenate([np.asarray(a), np.zeros((B - n,) + np.asarray(a).shape[1:], np.asarray(a).dtype)], axis=0)
         return ({k: pad(v) for k, v in arrs.items()} if isinstance(arrs, dict) else pad(arrs)), n
 
-    def predict_generator(self, generator, steps, verbose=0, decode=None, beam_width=10, **kwargs):
+    def predict_generator(self, generator, steps, verbose=0, decode=None, beam_width=10, threshold=None, **kwargs):
         """keras Model.predict_generator (sequence_decoding.py:118-127): the batches of the run are pipelined through
         Engine.predict_stream - upload and encoder pass of batch n + 1 beside the fusion layer / head of batch n and the
         download of batch n - 1 - and give bit for bit what predict_on_batch gives one batch at a time.
         decode=None returns the softmax outputs (N, T, C) like Keras; decode="argmax" returns (best, prob), each (N, T - skip):
         the per-frame best label and its probability computed on the device (what decode_batch needs; the (N, T, C) posteriors
-        never cross PCIe); decode="beam" returns (paths, log-probabilities) of mgr_ctc_beam_search(beam_width)."""
+        never cross PCIe); decode="beam" returns (paths, log-probabilities) of mgr_ctc_beam_search(beam_width); decode="segments"
+        returns per sample a list of (label, first_frame, last_frame, confidence) - decoding.greedy_segments(posteriors, threshold),
+        computed on the device where "argmax" computes the frame maxima."""
         steps = int(steps)
         if steps <= 0:
             return np.zeros((0,))
@@ -581,11 +583,12 @@ class Model:
                 counts.append(n)
                 yield ins
 
-        output = {None: "posteriors", "argmax": "argmax", "beam": "beam"}[decode]
+        output = {None: "posteriors", "argmax": "argmax", "beam": "beam", "segments": "segments"}[decode]
         outs = []
-        for i, r in enumerate(e.predict_stream(feed(), output=output, train_phase=bool(learning_phase()), beam_width=beam_width)):
+        for i, r in enumerate(e.predict_stream(feed(), output=output, train_phase=bool(learning_phase()), beam_width=beam_width,
+                                               threshold=threshold)):
             n = counts[i]
-            if output == "posteriors":
+            if output in ("posteriors", "segments"):
                 outs.append(r[:n])
             elif output == "argmax":
                 outs.append((r[0][:n], r[1][:n]))
@@ -595,9 +598,49 @@ class Model:
                 print("%d/%d" % (i + 1, steps))
         if output == "posteriors":
             return np.concatenate(outs, axis=0)
+        if output == "segments":
+            return [sg for o in outs for sg in o]
         if output == "argmax":
             return np.concatenate([o[0] for o in outs], axis=0), np.concatenate([o[1] for o in outs], axis=0)
         return [p for o in outs for p in o[0]], np.concatenate([o[1] for o in outs], axis=0)
+
+    def align_generator(self, generator, steps, return_path=False):
+        """Forced alignment over `steps` batches of a training generator (inputs with the_labels / input_length / label_length, as
+        fit_generator takes them), pipelined like evaluate_generator: per sample the most probable CTC alignment of ITS labels to the
+        network's posteriors for it - decoding.forced_align of predict_generator's output, without the posteriors leaving the device.
+        Returns (segments, logp[, path]): per sample a list of (label, first_frame, last_frame, confidence), the paths' natural-log
+        probabilities (N,) float64, and with return_path the frame paths (N, T - skip) int32."""
+        steps = int(steps)
+        if steps <= 0:
+            return ([], np.zeros((0,))) + ((np.zeros((0, 0), np.int32),) if return_path else ())
+        first = next(generator)
+        x0 = first[0]
+        ins0 = self._split_inputs(x0)
+        f0 = next(iter(ins0.values()))
+        B = f0.shape[0]
+        e = self._ensure_engine(B, f0.shape[1], np.asarray(x0["the_labels"]).shape[1])
+        counts = []
+
+        def feed():
+            for i in range(steps):
+                x = (first if i == 0 else next(generator))[0]
+                ins, n = self._pad_batch(self._split_inputs(x), B)
+                counts.append(n)
+                lab = np.asarray(x["the_labels"], np.float64)
+                il, ll = np.asarray(x["input_length"]).reshape(-1), np.asarray(x["label_length"]).reshape(-1)
+                if n < B:       # (padded rows: no labels, one frame)
+                    lab = np.concatenate([lab, -np.ones((B - n, lab.shape[1]))], axis=0)
+                    il, ll = np.concatenate([il, np.ones(B - n, il.dtype)]), np.concatenate([ll, np.zeros(B - n, ll.dtype)])
+                yield ins, lab, il, ll
+
+        segs, logps, paths = [], [], []
+        for i, (sg, lp, pa) in enumerate(e.predict_stream(feed(), output="align", train_phase=bool(learning_phase()))):
+            n = counts[i]
+            segs += sg[:n]
+            logps.append(lp[:n])
+            paths.append(pa[:n])
+        out = (segs, np.concatenate(logps, axis=0))
+        return out + (np.concatenate(paths, axis=0),) if return_path else out
 
     def evaluate_generator(self, generator, steps, **kwargs):
         """Mean CTC loss over `steps` batches (the validation loop of fit_generator, multimodal.py:264-269), pipelined like

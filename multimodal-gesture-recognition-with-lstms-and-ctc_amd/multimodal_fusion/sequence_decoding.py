@@ -1,7 +1,7 @@
 """Decode for the fusion network (reference multimodal_fusion/sequence_decoding.py:21-69)."""
 import numpy as np
 
-from ..decoding import greedy_decode, greedy_decode_argmax, write_mlf
+from ..decoding import greedy_decode, greedy_decode_argmax, greedy_segments, write_mlf
 
 # gesture code -> class name; the blank (21) is emitted as "sil" (reference :26-29)
 map_gest = {0: "oov", 1: "VA", 2: "VQ", 3: "PF", 4: "FU", 5: "CP", 6: "CV", 7: "DC", 8: "SP", 9: "CN", 10: "FN",
@@ -29,3 +29,15 @@ def decode_argmax(best, prob, f_list, out_file=None):
     if out_file is not None:
         write_mlf(out_file, ret, f_list, ignore_list, "Sample%05d")
     return ret
+
+
+def decode_segments(pred_out, f_list, out_file="final_ctc_recout_timed.mlf"):
+    """decode_batch with start and end times: pred_out (N, T, C) softmax - or the per-sample segment lists that
+    Model.predict_generator(decode="segments", threshold=THRESHOLD) computed on the device.  The same filter, collapse, class map and
+    ignore list; every MLF line reads "start end name" in HTK's 100 ns units (50 ms per frame).  The times are the frames at which the
+    network commits to the class, not the extent of the movement.  Returns (label-name lists, segment lists)."""
+    segs = pred_out if isinstance(pred_out, list) else greedy_segments(np.asarray(pred_out), THRESHOLD, skip=2)
+    ret = [[map_gest[s[0]] for s in sg] for sg in segs]
+    if out_file is not None:
+        write_mlf(out_file, ret, f_list, ignore_list, "Sample%05d", segments=segs)
+    return ret, segs

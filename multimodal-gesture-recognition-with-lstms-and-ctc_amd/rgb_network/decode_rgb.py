@@ -3,7 +3,7 @@ the reference's confidence threshold is commented out, so none applies - over th
 MLF writer with the ten-file ignore list."""
 import numpy as np
 
-from ..decoding import confidence_filter_collapse, write_mlf
+from ..decoding import confidence_filter_collapse, greedy_segments, write_mlf
 from ..keras_like import Model
 from ..multimodal_fusion.sequence_decoding import ignore_list, map_gest  # noqa: F401  (the same 22 names and ignore list)
 from .cnn_lstm import load_model as _load_model
@@ -26,3 +26,16 @@ def decode_batch(pred_out, f_list, out_file="ctc_recout.mlf"):
     nums = [int(str(f)[6:11]) if not isinstance(f, (int, np.integer)) else int(f) for f in f_list]
     write_mlf(out_file, ret, nums, ignore_list, "Sample%05d")
     return ret
+
+
+def decode_segments(pred_out, f_list, out_file="ctc_recout_timed.mlf"):
+    """decode_batch with start and end times: pred_out (N, T, C) softmax - or the per-sample segment lists that
+    Model.predict_generator(decode="segments") computed on the device.  No confidence filter (as decode_batch here); the same
+    collapse, class map and ignore list; every MLF line reads "start end name" in HTK's 100 ns units (50 ms per frame).  The times are
+    the frames at which the network commits to the class, not the extent of the movement.  Returns (label-name lists, segment lists)."""
+    nums = [int(str(f)[6:11]) if not isinstance(f, (int, np.integer)) else int(f) for f in f_list]
+    segs = pred_out if isinstance(pred_out, list) else greedy_segments(np.asarray(pred_out), None, skip=2)
+    ret = [[map_gest[s[0]] for s in sg] for sg in segs]
+    if out_file is not None:
+        write_mlf(out_file, ret, nums, ignore_list, "Sample%05d", segments=segs)
+    return ret, segs
