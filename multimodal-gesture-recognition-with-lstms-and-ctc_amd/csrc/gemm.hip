@@ -598,6 +598,175 @@ __global__ __launch_bounds__(128 * WC, WC == 2 ? 2 : 1) void k_gemm_nn_sparse(co
   }
 }
 
+// ------------------------------------------------------------------------------------------------ nn, dropout-aware, narrow inputs
+// The depth-1 projections (row-major X, 16 <= F <= 64; config F: F = 39 / 20, Z of 973 / 584 MB): the sums of k_gemm_nn_sparse<2, false>,
+// bit for bit, with the operands brought in once instead of gathered per gate pass.  That kernel is the wide-K tile walk: per 128 KiB
+// of Z four gate passes, each with a list copy into LDS, barriers and a two-stage pipeline of scattered 4-byte gathers - at 23 kept
+// features two stages, nothing to pipeline; its MFMA work is ~0.1 ms of chip time, its stores 0.16 ms at the HBM rate, and it took
+// 0.39 ms alone (profiles/membound_passes.txt).  Here
+//   * the X rows of a tile are 128 x F contiguous floats: ONE coalesced copy into LDS (odd pitch) serves the four gates;
+//   * the weight slice of the workgroup's 64 units (F x 64 x 4 floats) is read from the PACKED kernel Wp into a gate-major LDS image once
+//     per workgroup, which then walks NP_RPW row tiles of its sample: no k_gate_major launch, nothing kept between calls, so frozen or
+//     rewritten weights make no difference;
+//   * the kept list of a (gate, sample) is a ballot over its mask row, made by wave g for gate g in front of the walk: no
+//     k_mask_compact launch, no list copy per gate pass.  It is the list k_mask_compact writes: kept features ascending with their factor,
+//     then the dropped ones with the (zero) mask value itself, then (feature 0, factor 0) up to a whole stage of 16;
+//   * the MFMA operands are read from those images by list position: in step ks of a stage lane half lh takes position
+//     (2 lh + ks / 4) + 4 (ks % 4) - the dealing of k_gemm_nn_sparse - A = X[row][f], B = W[f][unit] * factor rounded to f32, the gates
+//     one after the other into their own accumulators, bias in the epilogue.  Same operands in the same order into the same
+//     instruction: the same bits.
+// A workgroup does not hold its CU: NP_RPW tiles (~30 us), then the next workgroup is placed; two workgroups of 4 waves per CU at
+// F = 39 (60 KiB of LDS each, 2 of the 8 wave slots per SIMD), so that the stores of one drain while the other computes and the
+// other stream's small kernels still find slots and 40 KiB of LDS on every CU (see the note on persistent workgroups above).
+// Not taken here (the generic kernel runs): the transposed copy, F < 16 or F > 64, MGR_TUNE_PROJ_WIDE_TILES = 2.
+constexpr int NP_MAXF = 64, NP_TU = 64, NP_RPW = 3;
+static inline size_t np_lds_bytes(int F) { return ((size_t)SP_TM * (F | 1) + (size_t)4 * F * NP_TU) * sizeof(float); }
+
+// XR: X elements per thread and tile, 128 F / 256 rounded up to the three sizes the dispatch knows (F <= 20, <= 40, <= 64); the tile's
+// loads are issued together, unconditionally (an index beyond the tile reads its last element again), one tile AHEAD: they are in
+// flight while the previous tile's MFMAs run and its stores drain, and reach LDS behind the barrier that ends its fragment reads.
+template <int XR>
+__global__ __launch_bounds__(256, XR > 20 ? 1 : 2) void k_proj_narrow(const float* __restrict__ X, int ldx, const float* __restrict__ mask4,
+                                                        const float* __restrict__ Wp, const float* __restrict__ bp, float* __restrict__ Z,
+                                                        int B, int T, int F, int H) {
+  constexpr int TM = SP_TM, TU = NP_TU;
+  extern __shared__ __attribute__((aligned(16))) float np_lds[];
+  __shared__ int Lf[4][NP_MAXF];
+  __shared__ float Lv[4][NP_MAXF];
+  __shared__ int Lc[4];
+  const int pitch = F | 1;
+  float* Xs = np_lds;                 // [TM][pitch]: lanes of a half read 32 consecutive rows at one feature - conflict-free
+  float* Ws = np_lds + TM * pitch;    // [4][F][TU]: lanes read 32 consecutive units of one (gate, feature)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int N = 4 * H;
+  const int ncol = (H + TU - 1) / TU, nrow = (T + TM - 1) / TM, nchunk = (nrow + NP_RPW - 1) / NP_RPW;
+  // workgroup -> (sample, chunk of row tiles, unit tile), XCD-aware as in k_gemm_nn_sparse: the unit tiles that share X rows meet in one L2
+  const int x = blockIdx.x & 7, jj = blockIdx.x >> 3;
+  const int rc = (jj / ncol) * 8 + x;
+  if (rc >= nchunk * B) return;
+  const int u0 = (jj % ncol) * TU, b = rc / nchunk, rt0 = (rc % nchunk) * NP_RPW;
+  const int rt1 = rt0 + NP_RPW < nrow ? rt0 + NP_RPW : nrow;
+  {   // the list of gate `wave`: lane = feature
+    const int Fp = (F + SP_SK - 1) / SP_SK * SP_SK;
+    const bool valid = lane < F;
+    const float v = valid ? mask4[((size_t)wave * B + b) * F + lane] : 0.f;
+    const bool kept = valid && v != 0.f;
+    const unsigned long long kb = __ballot(kept), db = __ballot(valid && !kept), lower = (1ull << lane) - 1ull;
+    const int cnt = __popcll(kb);
+    if (valid) {
+      const int pos = kept ? __popcll(kb & lower) : cnt + __popcll(db & lower);
+      Lf[wave][pos] = lane;
+      Lv[wave][pos] = v;
+    } else if (lane < Fp) {
+      Lf[wave][lane] = 0;
+      Lv[wave][lane] = 0.f;
+    }
+    if (lane == 0) Lc[wave] = cnt;
+  }
+  {   // (units beyond H: the last unit's weights, computed and never stored)
+    constexpr int WR = (XR + 1) / 2;   // float4 per thread: F TU / 256
+    float4 w[WR];
+#pragma unroll
+    for (int k = 0; k < WR; ++k) {
+      const int i = tid + 256 * k < F * TU ? tid + 256 * k : F * TU - 1;
+      const int f = i / TU, u = i % TU;
+      const int uc = u0 + u < H ? u0 + u : H - 1;
+      w[k] = *reinterpret_cast<const float4*>(Wp + (unsigned)((f * H + uc) * 4));
+    }
+#pragma unroll
+    for (int k = 0; k < WR; ++k) {
+      const int i = tid + 256 * k;
+      if (i < F * TU) {
+        const int f = i / TU, u = i % TU;
+        Ws[(0 * F + f) * TU + u] = w[k].x;
+        Ws[(1 * F + f) * TU + u] = w[k].y;
+        Ws[(2 * F + f) * TU + u] = w[k].z;
+        Ws[(3 * F + f) * TU + u] = w[k].w;
+      }
+    }
+  }
+  const int ra = wr * 64 + l31, ub = wc * 32 + l31;
+  const int unit = u0 + ub;
+  float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (unit < H) bias = *reinterpret_cast<const float4*>(bp + unit * 4);
+  // X rows r0 .. r0 + 127 of a tile (beyond T: the last row, computed and never stored): element e = row F + col, e = tid + 256 k
+  const int dq = 256 / F, dr = 256 % F, row_0 = tid / F, col_0 = tid % F;
+  const float* Xb = X + (size_t)b * T * ldx;
+  float xv[XR];
+  auto xload = [&](int rt) {
+    int row = row_0, col = col_0;
+#pragma unroll
+    for (int k = 0; k < XR; ++k) {
+      const int rw = row < TM ? row : TM - 1;
+      const int rcl = rt * TM + rw < T ? rt * TM + rw : T - 1;
+      xv[k] = Xb[(unsigned)(rcl * ldx + col)];   // (one sample's [T, ldx] block stays below 2^31 elements: a 32-bit offset from a uniform base)
+      row += dq;
+      col += dr;
+      if (col >= F) {
+        col -= F;
+        ++row;
+      }
+    }
+  };
+  xload(rt0);
+  for (int rt = rt0; rt < rt1; ++rt) {
+    const int r0 = rt * TM;
+    __syncthreads();   // (the previous tile's fragment reads are done; first pass: the lists and the weight image are written)
+    {
+      int row = row_0, col = col_0;
+#pragma unroll
+      for (int k = 0; k < XR; ++k) {
+        if (row < TM) Xs[row * pitch + col] = xv[k];
+        row += dq;
+        col += dr;
+        if (col >= F) {
+          col -= F;
+          ++row;
+        }
+      }
+    }
+    __syncthreads();
+    if (rt + 1 < rt1) xload(rt + 1);
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[g][mt][e] = 0.f;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int nst = (Lc[g] + SP_SK - 1) / SP_SK;
+      const float* Wsg = Ws + (size_t)g * F * TU + ub;
+      const float* Xa = Xs + ra * pitch;
+      for (int st = 0; st < nst; ++st) {
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+          const int p = st * SP_SK + 2 * lh + (ks >> 2) + 4 * (ks & 3);
+          const int f = Lf[g][p];
+          const float bv = Wsg[f * TU] * Lv[g][p];
+          acc[g][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(Xa[f], bv, acc[g][0], 0, 0, 0);
+          acc[g][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(Xa[32 * pitch + f], bv, acc[g][1], 0, 0, 0);
+        }
+      }
+    }
+    if (unit < H) {
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+          const int row = r0 + wr * 64 + mt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+          if (row < T) {
+            typedef float nt_f4 __attribute__((ext_vector_type(4)));
+            const nt_f4 v = {acc[0][mt][reg] + bias.x, acc[1][mt][reg] + bias.y, acc[2][mt][reg] + bias.z, acc[3][mt][reg] + bias.w};
+            __builtin_nontemporal_store(v, reinterpret_cast<nt_f4*>(Z + ((size_t)b * T + row) * N + unit * 4));
+          }
+        }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ nn, dropout-aware, split-f16
 // The same tile walk as k_gemm_nn_sparse<2, true> (transposed activations, 128 rows x 64 units x 4 gates, one K loop per gate over the
 // kept features, 16 list positions per stage) on the f16 matrix pipe (round 4): every f32 operand goes to LDS as an f16 (hi, lo)
@@ -1480,6 +1649,27 @@ static int input_proj_dropout_impl(mgr_ctx* c, const float* X, int ldx, bool tra
   unsigned* gate = (f16 && !trusted) ? wmax + 1 : nullptr;
   const bool lists = !dense || gate;   // the kept-feature lists: what every kernel but the dense one walks (no mask: all features)
   mgr_prof_begin(c, MGR_K_GEMM_NN);
+  // narrow row-major inputs (the depth-1 projections): k_proj_narrow makes its lists and its weight image itself - one launch, nothing
+  // in the workspace.  Not its shapes (they fall through to the generic kernel below): the transposed copy, F < 16 (the
+  // MFMA stage is 16 list positions), F > 64 (a mask row is one ballot, the X tile and the weight slice fit LDS twice per CU up to
+  // F = 40 and once up to 64), and MGR_TUNE_PROJ_WIDE_TILES = 2, which keeps selecting the generic kernel for tests and A/Bs.
+  if (!transposed && mask4 && F >= 16 && F <= NP_MAXF && c->tune[MGR_TUNE_PROJ_WIDE_TILES] != 2) {
+    if (!(c->attr_done & 2048u)) {
+      MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_narrow<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)np_lds_bytes(NP_MAXF)));
+      c->attr_done |= 2048u;
+    }
+    const int nchunk = ((T + SP_TM - 1) / SP_TM + NP_RPW - 1) / NP_RPW;
+    const int nwg = ((H + NP_TU - 1) / NP_TU) * ((nchunk * B + 7) / 8) * 8;
+    if (F <= 20)
+      hipLaunchKernelGGL(k_proj_narrow<10>, dim3(nwg), dim3(256), np_lds_bytes(F), s, X, ldx, mask4, Wp, bp, Z, B, T, F, H);
+    else if (F <= 40)
+      hipLaunchKernelGGL(k_proj_narrow<20>, dim3(nwg), dim3(256), np_lds_bytes(F), s, X, ldx, mask4, Wp, bp, Z, B, T, F, H);
+    else
+      hipLaunchKernelGGL(k_proj_narrow<32>, dim3(nwg), dim3(256), np_lds_bytes(F), s, X, ldx, mask4, Wp, bp, Z, B, T, F, H);
+    MGR_LAUNCH_CHECK();
+    mgr_prof_end(c, MGR_K_GEMM_NN);
+    return 0;
+  }
   if (lists && mask4)
     hipLaunchKernelGGL(k_mask_compact, dim3(4 * B), dim3(64), 0, s, mask4, F, Fp, kidx, kval, kcnt, (int*)nullptr, wmax);
   else if (lists)

@@ -143,30 +143,89 @@ __global__ __launch_bounds__(256) void k_wplanes(const float* __restrict__ Wp, _
 // XS[b][f] = split row of X[b][0..T)[f] (zero for t >= T): the generic producer of the split row format.  tshift: entry t of a row is
 // X[b][t + tshift][f], zero where that step does not exist (tshift = -1 / +1: the rows h_{t-1} / h_{t+1} the recurrent weight gradient of a
 // forward / reverse direction multiplies dz_t with)
-__global__ __launch_bounds__(256) void k_transpose_split(const float* __restrict__ X, int ldx, float* __restrict__ XS, int ldt, int T, int F,
-                                                         long long xsb /* batch stride of XS in floats; 0: F * ldt */, int fill, int tshift) {
-  __shared__ float tile[64][65];
-  const int b = blockIdx.z, t0 = blockIdx.x * 64, f0 = blockIdx.y * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const float* Xb = X + (size_t)b * T * ldx;
-  float* XSb = XS + (size_t)b * (xsb ? (size_t)xsb : (size_t)F * ldt);
+//
+// Tile: TS_TT = 128 time steps x 64 rows per workgroup of 4 waves.  Load: lane = row (256 contiguous bytes of X per wave instruction),
+// every thread takes 32 time steps as 16 pairs (t, t + 1), all 32 loads issued before the first is used; it converts its own values
+// (the scale of a row is per thread) and writes the pair's two hi halves and two lo halves as ONE dword each into the LDS images
+// img[part][row][TS_LP dwords]: the tile crosses the LDS as the f16 values it is stored as, half the bytes of an f32 tile.  Store:
+// 16 lanes per row take 16 bytes (8 time steps) each of the hi part, then of the lo part - a wave instruction writes 256 contiguous
+// bytes of each of 4 rows (one f16 per lane, as this pass stored at first, is 128 bytes per instruction, 32 instructions per thread:
+// 1.1 - 2.0 TB/s in the step, profiles/membound_passes.txt).
+// LDS banks (CDNA guide, section 2): TS_LP = 66.  Writes (ds_write_b32, 32 banks, per 32-lane half): lane = row, bank = (66 row + p)
+// mod 32 = 2 row + p: 16 banks, 2-way - 128 write instructions per tile, nothing beside the 64 KiB the tile moves through HBM; reads
+// (ds_read_b64, 64 banks, per 32-lane half): a half is two rows r, r + 1 x 16 lanes j, dwords 66 r + 4 j + {0, 1} then + {2, 3}: bank
+// pairs 4 j + 2 (r & 1) - all 64 banks once, conflict-free.  An odd pitch (the [64][65] padding of the first version, chosen for one
+// float per lane) would leave the 8-byte reads unaligned; a pitch that is a multiple of 4 puts the 32 rows of a write on 8 banks.
+constexpr int TS_TT = 128, TS_LP = 66;
+__device__ __forceinline__ float dw_zscale(unsigned zm_bits);   // (the row scale of dZS, with the dW product below)
+
+template <bool SCALED>
+__device__ __forceinline__ void ts_tile(const float* __restrict__ Xb, int ldx, float* __restrict__ XSb, int ldt, int T, int F, int fill, int tshift,
+                                        const unsigned* __restrict__ zmax_b, bool vec) {
+  __shared__ __attribute__((aligned(16))) unsigned img[2][64][TS_LP];
+  const int t0 = blockIdx.x * TS_TT, f0 = blockIdx.y * 64;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  {
+    const int f = f0 + lane, fc = f < F ? f : F - 1;
+    float v[16][2];
+    // (every load unconditional, from an address clamped into the tensor, and the value dropped afterwards: a load under a condition
+    //  is a branch per load, and the compiler put a full vmcnt wait into most of them)
 #pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int t = t0 + ty + 4 * i, f = f0 + tx, ts = t + tshift;
-    tile[ty + 4 * i][tx] = (t < T && ts >= 0 && ts < T && f < F) ? Xb[(size_t)ts * ldx + f] : 0.f;
-  }
-  __syncthreads();
+    for (int i = 0; i < 16; ++i)
 #pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int f = f0 + ty + 4 * i, t = t0 + tx;
-    if (f < F && t < fill) {
-      _Float16 hi, lo;
-      ps_split(tile[tx][ty + 4 * i] * XS_SCALE, hi, lo);
-      _Float16* row = reinterpret_cast<_Float16*>(XSb + (size_t)f * ldt);
-      row[t] = hi;
-      row[ldt + t] = lo;
+      for (int h = 0; h < 2; ++h) {
+        const int ts = t0 + 2 * (w + 4 * i) + h + tshift;
+        v[i][h] = Xb[(size_t)(ts < 0 ? 0 : ts < T ? ts : T - 1) * ldx + fc];
+      }
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int t = t0 + 2 * (w + 4 * i) + h, ts = t + tshift;
+        v[i][h] = (t < T && ts >= 0 && ts < T && f < F) ? v[i][h] : 0.f;
+      }
+    float sc = XS_SCALE;
+    if constexpr (SCALED) sc = dw_zscale(zmax_b[fc]);   // (a column beyond F is converted with its neighbour's scale and never stored)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      _Float16 hi0, lo0, hi1, lo1;
+      ps_split(v[i][0] * sc, hi0, lo0);
+      ps_split(v[i][1] * sc, hi1, lo1);
+      const int p = w + 4 * i;
+      img[0][lane][p] = (unsigned)__builtin_bit_cast(unsigned short, hi0) | ((unsigned)__builtin_bit_cast(unsigned short, hi1) << 16);
+      img[1][lane][p] = (unsigned)__builtin_bit_cast(unsigned short, lo0) | ((unsigned)__builtin_bit_cast(unsigned short, lo1) << 16);
     }
   }
+  __syncthreads();
+  const int j = lane & 15;
+  const int t = t0 + 8 * j;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = (lane >> 4) + 4 * w + 16 * i, f = f0 + r;
+    if (f >= F || t >= fill) continue;
+    _Float16* row = reinterpret_cast<_Float16*>(XSb + (size_t)f * ldt);
+    const uint2 h0 = *reinterpret_cast<const uint2*>(&img[0][r][4 * j]), h1 = *reinterpret_cast<const uint2*>(&img[0][r][4 * j + 2]);
+    const uint2 l0 = *reinterpret_cast<const uint2*>(&img[1][r][4 * j]), l1 = *reinterpret_cast<const uint2*>(&img[1][r][4 * j + 2]);
+    if (vec && t + 8 <= fill) {
+      *reinterpret_cast<uint4*>(row + t) = make_uint4(h0.x, h0.y, h1.x, h1.y);
+      *reinterpret_cast<uint4*>(row + ldt + t) = make_uint4(l0.x, l0.y, l1.x, l1.y);
+    } else {   // a ragged end of the filled range, or rows that are not 16-byte aligned: one f16 at a time
+      const unsigned hw[4] = {h0.x, h0.y, h1.x, h1.y}, lw[4] = {l0.x, l0.y, l1.x, l1.y};
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (t + k < fill) {
+          row[t + k] = __builtin_bit_cast(_Float16, (unsigned short)(hw[k >> 1] >> (16 * (k & 1))));
+          row[ldt + t + k] = __builtin_bit_cast(_Float16, (unsigned short)(lw[k >> 1] >> (16 * (k & 1))));
+        }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_transpose_split(const float* __restrict__ X, int ldx, float* __restrict__ XS, int ldt, int T, int F,
+                                                         long long xsb /* batch stride of XS in floats; 0: F * ldt */, int fill, int tshift,
+                                                         int vec /* rows 16-byte aligned: 16-byte stores */) {
+  const int b = blockIdx.z;
+  ts_tile<false>(X + (size_t)b * T * ldx, ldx, XS + (size_t)b * (xsb ? (size_t)xsb : (size_t)F * ldt), ldt, T, F, fill, tshift, nullptr, vec != 0);
 }
 
 // ------------------------------------------------------------------------------------------------ nn on pre-split operands
@@ -449,30 +508,9 @@ __device__ __forceinline__ float dw_zscale(unsigned zm_bits) {   // the power of
 }
 // dZS[b][col] = split row of dZ[b][0..T)[col] * sz(b, col), zero for t >= T
 __global__ __launch_bounds__(256) void k_transpose_split_scaled(const float* __restrict__ dZ, int N, float* __restrict__ dZS, int ldt, int T,
-                                                                const unsigned* __restrict__ zmax) {
-  __shared__ float tile[64][65];
-  const int b = blockIdx.z, t0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const float* Zb = dZ + (size_t)b * T * N;
-  float* Sb = dZS + (size_t)b * N * ldt;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int t = t0 + ty + 4 * i, cc = c0 + tx;
-    tile[ty + 4 * i][tx] = (t < T && cc < N) ? Zb[(size_t)t * N + cc] : 0.f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int cc = c0 + ty + 4 * i, t = t0 + tx;
-    if (cc < N && t < ldt) {
-      const float sz = dw_zscale(zmax[(size_t)b * N + cc]);
-      _Float16 hi, lo;
-      ps_split(tile[tx][ty + 4 * i] * sz, hi, lo);
-      _Float16* row = reinterpret_cast<_Float16*>(Sb + (size_t)cc * ldt);
-      row[t] = hi;
-      row[ldt + t] = lo;
-    }
-  }
+                                                                const unsigned* __restrict__ zmax, int vec) {
+  const int b = blockIdx.z;   // (the tile walk of k_transpose_split; 0 sz behind T as before: an Inf row's padding is NaN too)
+  ts_tile<true>(dZ + (size_t)b * T * N, N, dZS + (size_t)b * N * ldt, ldt, T, N, ldt, 0, zmax + (size_t)b * N, vec != 0);
 }
 
 typedef float dw_f4 __attribute__((ext_vector_type(4)));
@@ -615,20 +653,45 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_split(const char* __restrict_
   }
 }
 
-// dWp[f][4u+g] = sum over the samples that kept feature f for gate g, in sample order
+// dWp[f][4u+g] = sum over the samples that kept feature f for gate g, in sample order.  One thread forms the four gate sums of an
+// (f, u) - the 16 bytes of dWp they fill - and takes the samples in blocks of DG_SB: the 4 DG_SB list positions first, then the P loads
+// of the kept ones, then the adds, sample by sample: 4 DG_SB loads in flight per thread where the first version of this kernel walked
+// one chain of kpos load -> P load -> add per sample (< 1 TB/s).  kpos == nullptr: every row kept at its own position (dU from HsT).
+constexpr int DG_SB = 8;
 __global__ __launch_bounds__(256) void k_dw_gather32(const float* __restrict__ P, const int* __restrict__ kpos, float* __restrict__ dWp, int B, int F,
-                                                     int Fp32, int H) {
-  const size_t n = (size_t)4 * F * H;
+                                                     int Fp32, int H, int vec /* dWp 16-byte aligned */) {
+  const size_t n = (size_t)F * H;
   for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const int u = (int)(i % H);
-    const int f = (int)((i / H) % F);
-    const int g = (int)(i / ((size_t)H * F));
-    float sacc = 0.f;
-    for (int b = 0; b < B; ++b) {
-      const int pos = kpos[((size_t)g * B + b) * F + f];
-      if (pos >= 0) sacc += P[(((size_t)g * B + b) * Fp32 + pos) * H + u];
+    const int f = (int)(i / H);
+    float sacc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int b0 = 0; b0 < B; b0 += DG_SB) {
+      int pos[DG_SB][4];
+      float v[DG_SB][4];
+#pragma unroll
+      for (int k = 0; k < DG_SB; ++k)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) pos[k][g] = b0 + k < B ? (kpos ? kpos[((size_t)g * B + b0 + k) * F + f] : f) : -1;
+#pragma unroll
+      for (int k = 0; k < DG_SB; ++k)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          v[k][g] = 0.f;
+          if (pos[k][g] >= 0) v[k][g] = P[(((size_t)g * B + b0 + k) * Fp32 + pos[k][g]) * H + u];
+        }
+#pragma unroll
+      for (int k = 0; k < DG_SB; ++k)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          if (pos[k][g] >= 0) sacc[g] += v[k][g];
     }
-    dWp[(size_t)f * 4 * H + 4 * u + g] = sacc;
+    float* out = dWp + ((size_t)f * H + u) * 4;
+    if (vec) {
+      *reinterpret_cast<float4*>(out) = make_float4(sacc[0], sacc[1], sacc[2], sacc[3]);
+    } else {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) out[g] = sacc[g];
+    }
   }
 }
 
@@ -783,8 +846,8 @@ int mgr_lstm_param_grads_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const 
   w += mgr_align_up((size_t)4 * B * sizeof(int), 256);
   unsigned* words2 = reinterpret_cast<unsigned*>(w);
   w += 256;
-  int* kpos2 = reinterpret_cast<int*>(w);
-  w += mgr_align_up((size_t)4 * B * H * sizeof(int), 256);
+  // (the list positions of this product are the rows themselves: their block of the layout stays, nothing writes or reads it)
+  w +=mgr_align_up((size_t)4 * B * H * sizeof(int), 256);
   float* P2 = reinterpret_cast<float*>(w);
   hipStream_t s = mgr_stream(c);
   if (!(c->attr_done & 32u)) {
@@ -808,19 +871,21 @@ int mgr_lstm_param_grads_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const 
     hipLaunchKernelGGL(k_lists32, dim3(4 * B), dim3(64), 0, s, mask4, F, Fp32, lists, kcnt, kpos, words + 1);
   }
   if (!dzmax) hipLaunchKernelGGL(k_rowmax_bt, dim3((N + 63) / 64, B), dim3(256), 0, s, dZ, N, T, const_cast<unsigned*>(zmax), (float*)nullptr);
-  hipLaunchKernelGGL(k_transpose_split_scaled, dim3((ldt + 63) / 64, (N + 63) / 64, B), dim3(256), 0, s, dZ, N, dZS, ldt, T, zmax);
+  hipLaunchKernelGGL(k_transpose_split_scaled, dim3((ldt + TS_TT - 1) / TS_TT, (N + 63) / 64, B), dim3(256), 0, s, dZ, N, dZS, ldt, T, zmax,
+                     (int)(ldt % 8 == 0));   // (dZS is 256-byte aligned in the workspace)
   if (HsT) {
     const int grid2 = 8 * ((B + 7) / 8) * 4 * ((Hp32 + DW_BM - 1) / DW_BM) * ((H + DW_BN - 1) / DW_BN);
     MGR_HIP(hipMemsetAsync(words2, 0, 2 * sizeof(unsigned), s));
-    hipLaunchKernelGGL(k_lists32, dim3(4 * B), dim3(64), 0, s, (const float*)nullptr, H, Hp32, lists2, kcnt2, kpos2, words2 + 1);
+    hipLaunchKernelGGL(k_lists32, dim3(4 * B), dim3(64), 0, s, (const float*)nullptr, H, Hp32, lists2, kcnt2, (int*)nullptr, words2 + 1);
     if (c->tune[MGR_TUNE_PROJ_TS_TILE] == 1)
       hipLaunchKernelGGL(k_dw_split<4>, dim3(grid2), dim3(256), 3 * DW_STAGE, s, reinterpret_cast<const char*>(HsT), ldt, lists2, kcnt2, words2 + 1,
                          reinterpret_cast<const char*>(dZS), zmax, P2, B, T, Hp32, H, H);
     else
       hipLaunchKernelGGL(k_dw_split<8>, dim3(grid2), dim3(512), 4 * DW_STAGE, s, reinterpret_cast<const char*>(HsT), ldt, lists2, kcnt2, words2 + 1,
                          reinterpret_cast<const char*>(dZS), zmax, P2, B, T, Hp32, H, H);
-    const size_t n2 = (size_t)4 * H * H;
-    hipLaunchKernelGGL(k_dw_gather32, dim3((int)((n2 + 255) / 256 < 4096 ? (n2 + 255) / 256 : 4096)), dim3(256), 0, s, P2, kpos2, dUp, B, H, Hp32, H);
+    const size_t n2 = (size_t)H * H;
+    hipLaunchKernelGGL(k_dw_gather32, dim3((int)((n2 + 255) / 256 < 4096 ? (n2 + 255) / 256 : 4096)), dim3(256), 0, s, P2, (const int*)nullptr, dUp, B, H,
+                       Hp32, H, (int)aligned16(dUp));   // (every row kept at its own position: no position table)
   }
   const int grid = 8 * ((B + 7) / 8) * 4 * ((Fp32 + DW_BM - 1) / DW_BM) * ((H + DW_BN - 1) / DW_BN);
   // MGR_TUNE_PROJ_TS_TILE (the tile switch of the projection): 1 = the 4-wave form, which fits on a CU beside a workgroup of a
@@ -831,8 +896,9 @@ int mgr_lstm_param_grads_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const 
   else
     hipLaunchKernelGGL(k_dw_split<8>, dim3(grid), dim3(512), 4 * DW_STAGE, s, reinterpret_cast<const char*>(XS), ldt, lists, kcnt, words + 1,
                        reinterpret_cast<const char*>(dZS), zmax, P, B, T, Fp32, F, H);
-  const size_t n = (size_t)4 * F * H;
-  hipLaunchKernelGGL(k_dw_gather32, dim3((int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)), dim3(256), 0, s, P, kpos, dWp, B, F, Fp32, H);
+  const size_t n = (size_t)F * H;
+  hipLaunchKernelGGL(k_dw_gather32, dim3((int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)), dim3(256), 0, s, P, kpos, dWp, B, F, Fp32, H,
+                     (int)aligned16(dWp));
   MGR_LAUNCH_CHECK();
   mgr_prof_end(c, MGR_K_GEMM_TN);
   return 0;
@@ -863,7 +929,8 @@ int mgr_transpose_bt_split(mgr_ctx* c, const float* X, int ldx, float* XS, int l
   MGR_REQUIRE(c && X && XS, "null argument");
   MGR_REQUIRE(B > 0 && T > 0 && F > 0 && ldx >= F && ldt >= T && ldt % 8 == 0, "bad shape");
   mgr_prof_begin(c, MGR_K_MISC);
-  hipLaunchKernelGGL(k_transpose_split, dim3((ldt + 63) / 64, (F + 63) / 64, B), dim3(256), 0, mgr_stream(c), X, ldx, XS, ldt, T, F, 0LL, ldt, 0);
+  hipLaunchKernelGGL(k_transpose_split, dim3((ldt + TS_TT - 1) / TS_TT, (F + 63) / 64, B), dim3(256), 0, mgr_stream(c), X, ldx, XS, ldt, T, F, 0LL, ldt, 0,
+                     (int)aligned16(XS));   // (ldt % 8 == 0: every row and its lo half start on 16 bytes)
   MGR_LAUNCH_CHECK();
   mgr_prof_end(c, MGR_K_MISC);
   return 0;
@@ -873,7 +940,8 @@ int mgr_transpose_bt_split_shift(mgr_ctx* c, const float* X, int ldx, float* XS,
   MGR_REQUIRE(c && X && XS, "null argument");
   MGR_REQUIRE(B > 0 && T > 0 && F > 0 && ldx >= F && ldt >= T && ldt % 8 == 0 && tshift >= -1 && tshift <= 1, "bad shape");
   mgr_prof_begin(c, MGR_K_MISC);
-  hipLaunchKernelGGL(k_transpose_split, dim3((ldt + 63) / 64, (F + 63) / 64, B), dim3(256), 0, mgr_stream(c), X, ldx, XS, ldt, T, F, 0LL, ldt, tshift);
+  hipLaunchKernelGGL(k_transpose_split, dim3((ldt + TS_TT - 1) / TS_TT, (F + 63) / 64, B), dim3(256), 0, mgr_stream(c), X, ldx, XS, ldt, T, F, 0LL, ldt, tshift,
+                     (int)aligned16(XS));
   MGR_LAUNCH_CHECK();
   mgr_prof_end(c, MGR_K_MISC);
   return 0;
@@ -888,7 +956,8 @@ int mgr_rowmax_bt(mgr_ctx* c, const float* dZ, int N, int T, int B, unsigned* zm
 }
 
 int mgr_transpose_bt_split_strided(mgr_ctx* c, const float* X, int ldx, float* XS, int ldt, long long xsb, int ldt_fill, int B, int T, int F) {
-  hipLaunchKernelGGL(k_transpose_split, dim3((ldt_fill + 63) / 64, (F + 63) / 64, B), dim3(256), 0, mgr_stream(c), X, ldx, XS, ldt, T, F, xsb, ldt_fill, 0);
+  hipLaunchKernelGGL(k_transpose_split, dim3((ldt_fill + TS_TT - 1) / TS_TT, (F + 63) / 64, B), dim3(256), 0, mgr_stream(c), X, ldx, XS, ldt, T, F, xsb, ldt_fill, 0,
+                     (int)(aligned16(XS) && ldt % 8 == 0 && xsb % 4 == 0));
   MGR_LAUNCH_CHECK();
   return 0;
 }

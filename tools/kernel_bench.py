@@ -108,6 +108,50 @@ def scan(dev, B, T, H):
         print("scan_bwd B=%d T=%d H=%3d : %7.3f ms  %6.2f us/step" % (B, T, H, ms, ms * 1e3 / T))
 
 
+def membound(dev, B=64, T=1900):
+    """The memory-bound passes of the training step's GEMM phase at the config-F shapes: ms and TB/s of the bytes they must move.
+    The scaled pass over dZ and the gather of the partial tiles are internal to mgr_lstm_param_grads_dropout_ts: run this under
+    `rocprofv3 --kernel-trace --stats -- python tools/kernel_bench.py --what membound` and read them with tools/kernel_stats.py;
+    the pass over dZ has the tile walk and the bytes of mgr_transpose_bt_split at F = 400, which is timed here."""
+    rng = np.random.default_rng(0)
+    ldt = (T + 127) // 128 * 128
+    for F, H, p in ((39, 500, 0.4), (20, 300, 0.6)):        # depth-1 projections: audio, skeletal
+        X = dev.array(rng.standard_normal((B, T, F)).astype(np.float32))
+        Wp = dev.array(rng.standard_normal((F, 4 * H)).astype(np.float32) * 0.05)
+        bp = dev.zeros((4 * H,))
+        m = dev.array(((rng.random((4, B, F)) >= p) / (1.0 - p)).astype(np.float32))
+        Z = dev.empty((B, T, 4 * H))
+        ws = dev.bytes(dev.lib.mgr_lstm_input_proj_dropout_ws_bytes(B, F, H))
+        gb = (B * T * (4 * H + F) * 4.0) / 1e9
+        for wide in (0, 2):
+            dev.call("mgr_tune", 11, wide)
+            ms = timeit(dev, lambda: dev.call("mgr_lstm_input_proj_dropout", X, F, m, p, Wp, bp, Z, B, T, F, H, ws, ws.nbytes))
+            print("depth-1 projection F=%2d H=%3d p=%.1f %s: %7.3f ms  %5.2f TB/s" % (F, H, p, "generic, 128-unit tiles" if wide else "library's choice       ", ms, gb / ms))
+        dev.call("mgr_tune", 11, 0)
+        for a in (X, Wp, bp, m, Z, ws):
+            a.free()
+    for F, what in ((100, "h_prev -> HsT (shift -1)"), (400, "dZ-shaped (N = 400)    ")):
+        X = dev.array(rng.uniform(-1, 1, (B, T, F)).astype(np.float32))
+        XS = dev.zeros((B, F, ldt))
+        ms = timeit(dev, lambda: dev.call("mgr_transpose_bt_split_shift", X, F, XS, ldt, B, T, F, -1 if F == 100 else 0), reps=10)
+        print("split rows along time, %s: %7.3f ms  %5.2f TB/s" % (what, ms, (B * T * F * 4.0 + B * F * ldt * 4.0) / 1e9 / ms))
+        X.free(); XS.free()
+    F, H = 1600, 100                                         # the fusion layer's weight gradients, dU from HsT
+    X = dev.array(rng.uniform(-1, 1, (B, T, F)).astype(np.float32))
+    Y = dev.array(rng.uniform(-1, 1, (B, T, H)).astype(np.float32))
+    dZ = dev.array((rng.standard_normal((B, T, 4 * H)) * 0.1).astype(np.float32))
+    m = dev.array(((rng.random((4, B, F)) >= 0.5) * 2.0).astype(np.float32))
+    XS, HsT = dev.zeros((B, F, ldt)), dev.zeros((B, H, ldt))
+    dev.call("mgr_transpose_bt_split", X, F, XS, ldt, B, T, F)
+    dev.call("mgr_transpose_bt_split_shift", Y, H, HsT, ldt, B, T, H, -1)
+    gW, gU, gb_ = dev.empty((F, 4 * H)), dev.empty((H, 4 * H)), dev.empty((4 * H,))
+    ws = dev.bytes(dev.lib.mgr_lstm_param_grads_dropout_ts_ws_bytes(B, T, F, H, ldt))
+    ms = timeit(dev, lambda: dev.call("mgr_lstm_param_grads_dropout_ts", XS, ldt, m, 0.5, Y, H, dZ, gW, gU, gb_, B, T, F, H, 0, ws, ws.nbytes, 0, 0, 0, HsT))
+    print("weight gradients of the fusion layer (row maxima, scaled pass, dU, dW, two gathers): %7.3f ms" % ms)
+    for a in (X, Y, dZ, m, XS, HsT, gW, gU, gb_, ws):
+        a.free()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="gemm,scan")
@@ -118,7 +162,9 @@ if __name__ == "__main__":
         k, v = kv.split("=")
         dev.call("mgr_tune", int(k), int(v))
     print(dev.name, dev.cu_count, "CUs")
-    if a.what == "gemm1":
+    if a.what == "membound":
+        membound(dev)
+    elif a.what == "gemm1":
         gemm(dev, 64, 1900, 1000, 500)
     elif "gemm" in a.what:
         gemm(dev, 64, 1900, 1000, 500)
