@@ -513,6 +513,24 @@ size_t mgr_ctc_beam_ws_bytes(int B, int T, int C, int beam);
 int mgr_ctc_beam_search(mgr_ctx* ctx, const float* P, const int32_t* input_len, int B, int T, int C, int skip,
                         int blank, int beam, float eps, int merge_repeated, int32_t* out, int32_t* out_len,
                         double* logp, void* ws, size_t ws_bytes);
+/* The same search with a label bigram and an N-best list.  The semantics are those of mgr_ctc_beam_search with
+ * merge_repeated = 0 (a prefix is the labelling), plus:
+ *   ext [(C+1)*C] double (device): the bonus for appending label c after label p is ext[(p+1)*C + c]; row 0 is the empty prefix, the
+ *                  column `blank` is never read.  Every live beam carries the sum of ext over its prefix and a candidate ranks by
+ *                  lse(p_blank, p_nonblank) + that sum; an extension whose entry is -inf is no candidate (a hard grammar).  Ties and
+ *                  -inf candidates as in mgr_ctc_beam_search.  Entries must be finite or -inf: the caller checks, the tables are
+ *                  device memory.
+ *   fin [C+1] double (device) or NULL: added once after the last frame, indexed by last label + 1 (0 = empty prefix).  It takes no
+ *                  part in the pruning: the at most `beam` live beams are ranked again by total + fin (ties to the better rank
+ *                  before; a beam whose sum is -inf is dropped) and the first top_paths are written.
+ *   out [B,top_paths,T-skip] padded -1; out_len [B,top_paths], -1 where fewer than top_paths hypotheses survive; score [B,top_paths]
+ *   = the network's log-probability + the bonuses, -inf where out_len = -1; logp_ctc [B,top_paths] the network's part alone.
+ * input_len 0 gives the empty prefix with logp_ctc = 0 and score = fin[0].  beam <= 32, C <= 64, 1 <= top_paths <= beam.  With
+ * all-zero tables the hypotheses and scores are those of mgr_ctc_beam_search bit for bit.  Deterministic; samples are independent. */
+size_t mgr_ctc_beam_lm_ws_bytes(int B, int T, int C, int beam, int top_paths);
+int mgr_ctc_beam_search_lm(mgr_ctx* ctx, const float* P, const int32_t* input_len, int B, int T, int C, int skip, int blank, int beam,
+                           float eps, const double* ext, const double* fin, int top_paths, int32_t* out, int32_t* out_len,
+                           double* score, double* logp_ctc, void* ws, size_t ws_bytes);
 
 /* ---- K11: locating gestures in time.  The reference "spots and classifies gestures from two continuous streams" and keeps
  * only the label sequence (sequence_decoding.py:38-53 of each network); these two calls keep the frame positions as well. ---- */

@@ -122,6 +122,8 @@ SIGNATURES = {
     "mgr_frame_argmax": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "mgr_ctc_beam_ws_bytes": (sz, [i32, i32, i32, i32]),
     "mgr_ctc_beam_search": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, i32, vp, vp, vp, vp, sz]),
+    "mgr_ctc_beam_lm_ws_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "mgr_ctc_beam_search_lm": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, vp, vp, vp, sz]),
     "mgr_ctc_align_ws_bytes": (sz, [i32, i32, i32, i32]),
     "mgr_ctc_align": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, vp, sz]),
     "mgr_greedy_segments": (i32, [vp, vp, i32, i32, i32, i32, C.c_float, i32, vp, vp, vp, vp]),

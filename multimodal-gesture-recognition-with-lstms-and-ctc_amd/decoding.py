@@ -215,6 +215,117 @@ def beam_search_decode(pred_out, input_length=None, beam_width=10, skip=2, merge
     return [[int(v) for v in o[i, :l[i]]] for i in range(N)], s
 
 
+def bigram_lm(label_seqs, n_classes, blank=None, add_k=1.0):
+    """A bigram over labels from counts (host, numpy): label_seqs is whatever pack_labels takes - an iterable of label lists or a
+    padded array.  Returns (lm (C + 1, C) float64, lm_end (C + 1,) float64), natural-log conditional probabilities: lm[p + 1, c] =
+    log p(c | previous label p), row 0 = start of sequence, lm_end[p + 1] = log p(end | p) - "end of sequence" is one more outcome of
+    every row.  Smoothing is add-k over the non-blank classes plus end; the blank never follows anything (its column is -inf, and the
+    decoder never reads it).  With add_k = 0 unseen transitions are -inf - a hard grammar - and a row without counts is all -inf."""
+    Cn = int(n_classes)
+    blank = Cn - 1 if blank is None else int(blank)
+    label_seqs = label_seqs if isinstance(label_seqs, np.ndarray) else list(label_seqs)
+    counts, ends = np.zeros((Cn + 1, Cn), np.float64), np.zeros(Cn + 1, np.float64)
+    if len(label_seqs):
+        lab, _ = pack_labels(label_seqs)
+        for row in lab:
+            prev = 0
+            for v in row[row >= 0]:
+                if v >= Cn or v == blank:
+                    raise ValueError("label %d is not one of the %d non-blank classes" % (int(v), Cn - 1))
+                counts[prev, v] += 1.0
+                prev = int(v) + 1
+            ends[prev] += 1.0
+    k = float(add_k)
+    smooth = np.full(Cn, k)
+    smooth[blank] = 0.0
+    num, num_end = counts + smooth, ends + k
+    den = num.sum(axis=1) + num_end
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lm = np.where(num > 0, np.log(num / den[:, None]), -np.inf)
+        lm_end = np.where(num_end > 0, np.log(num_end / den), -np.inf)
+    return lm, lm_end
+
+
+def lm_tables(n_classes, lm=None, lm_end=None, alpha=1.0, beta=0.0):
+    """The two tables mgr_ctc_beam_search_lm reads, in fp64: ext (C + 1, C) = alpha * lm + beta (lm=None: zeros) and fin (C + 1,) =
+    alpha * lm_end, or None.  -inf stays -inf whatever alpha is; NaN and +inf are refused here - the kernel reads device memory and
+    cannot say so."""
+    Cn = int(n_classes)
+
+    def scaled(t, shape, shift, what):
+        t = np.asarray(t, np.float64)
+        if t.shape != shape:
+            raise ValueError("%s has shape %s, the decoder needs %s" % (what, t.shape, shape))
+        if np.isnan(t).any() or np.isposinf(t).any():
+            raise ValueError("%s holds NaN or +inf: entries must be finite or -inf" % what)
+        ninf = np.isneginf(t)
+        out = np.where(ninf, -np.inf, float(alpha) * np.where(ninf, 0.0, t) + shift)
+        if not np.all(np.isfinite(out) | ninf):
+            raise ValueError("alpha / beta make %s NaN or infinite" % what)
+        return np.ascontiguousarray(out)
+
+    ext = scaled(np.zeros((Cn + 1, Cn)) if lm is None else lm, (Cn + 1, Cn), float(beta), "lm")
+    fin = None if lm_end is None else scaled(lm_end, (Cn + 1,), 0.0, "lm_end")
+    return ext, fin
+
+
+def nbest_from_arrays(out, out_len, score, logp_ctc, top_paths):
+    """mgr_ctc_beam_search_lm's arrays ((B, top_paths, T - skip), (B, top_paths) x 3) -> (paths, score, logp_ctc).  top_paths = 1:
+    the shapes beam_search_decode returns (a label list per sample, (B,) arrays); otherwise per sample the ranked list of its
+    surviving hypotheses (at most top_paths) and (B, top_paths) arrays with -inf where there is none."""
+    B = out.shape[0]
+    paths = [[[int(v) for v in out[b, k, :out_len[b, k]]] for k in range(top_paths) if out_len[b, k] >= 0] for b in range(B)]
+    if top_paths == 1:
+        return [p[0] if p else [] for p in paths], score[:, 0].copy(), logp_ctc[:, 0].copy()
+    return paths, score.copy(), logp_ctc.copy()
+
+
+def beam_search_lm_decode(pred_out, lm=None, lm_end=None, alpha=1.0, beta=0.0, input_length=None, beam_width=10, top_paths=1, skip=2,
+                          dev=None):
+    """CTC prefix beam search with a label bigram and an N-best list on the GPU (mgr_ctc_beam_search_lm): beam_search_decode
+    (merge_repeated=False) in which a hypothesis ranks by log p_ctc + alpha * (sum of lm over its label pairs) + beta * (its length),
+    plus alpha * lm_end[last label + 1] once at the end (no part in the pruning).  lm (C + 1, C), lm_end (C + 1,) as bigram_lm returns
+    them; -inf entries forbid a transition.  Returns (paths, score, logp_ctc): with top_paths = 1 a label list per sample and two (N,)
+    float64 arrays - the ranking score and the network's part of it -, otherwise per sample the ranked list of its at most top_paths
+    hypotheses and (N, top_paths) arrays, -inf where fewer survive."""
+    dev = dev or default_device()
+    P = np.ascontiguousarray(pred_out, dtype=np.float32)
+    N, T, Cn = P.shape
+    ext, fin = lm_tables(Cn, lm, lm_end, alpha, beta)
+    W, NP = int(beam_width), int(top_paths)
+    il = np.full(N, T - skip, np.int32) if input_length is None else np.asarray(input_length).reshape(N).astype(np.int32)
+    bufs = [dev.array(P), dev.array(il), dev.array(ext)]
+    try:
+        if fin is not None:
+            bufs.append(dev.array(fin))
+        dfin = bufs[3] if fin is not None else None
+        out, olen = dev.empty((N, NP, T - skip), np.int32), dev.empty((N, NP), np.int32)
+        score, logp = dev.empty((N, NP), np.float64), dev.empty((N, NP), np.float64)
+        bufs += [out, olen, score, logp]
+        ws = dev.bytes(dev.lib.mgr_ctc_beam_lm_ws_bytes(N, T, Cn, W, NP))
+        bufs.append(ws)
+        dev.call("mgr_ctc_beam_search_lm", bufs[0], bufs[1], N, T, Cn, skip, Cn - 1, W, C.c_float(1e-8), bufs[2], dfin, NP, out, olen,
+                 score, logp, ws, ws.nbytes)
+        res = nbest_from_arrays(out.download(), olen.download(), score.download(), logp.download(), NP)
+    finally:
+        for a in bufs:
+            a.free()
+    return res
+
+
+def decode_beam_mlf(pred_out, f_list, map_gest, ignore_list, name_fmt, out_file, top_paths=1, **kwargs):
+    """What the networks' decode_beam share: pred_out (N, T, C) softmax - decoded with beam_search_lm_decode(**kwargs) - or the
+    (paths, score, logp_ctc) that Model.predict_generator(decode="beam_lm", top_paths=top_paths) computed on the device.  The 1-best
+    path of every sample goes through the class map into the unchanged write_mlf; returns (1-best name lists, (paths, score,
+    logp_ctc))."""
+    nbest = pred_out if isinstance(pred_out, tuple) else beam_search_lm_decode(np.asarray(pred_out), top_paths=top_paths, **kwargs)
+    best = nbest[0] if np.ndim(nbest[1]) == 1 else [p[0] if p else [] for p in nbest[0]]      # ((N,) scores: one path per sample)
+    ret = [[map_gest[i] for i in seq] for seq in best]
+    if out_file is not None:
+        write_mlf(out_file, ret, f_list, ignore_list, name_fmt)
+    return ret, nbest
+
+
 def edit_distance(a, b):
     la, lb = len(a), len(b)
     d = list(range(lb + 1))

@@ -1005,7 +1005,8 @@ class Engine:
     EV_D1P = (55, 56)     # the depth-1 projections into depth-1 Z set 0 / 1 are done (stream 0)
     EV_D1S = (57, 58)     # the depth-1 scans that read depth-1 Z set 0 / 1 are done (stream ES)
 
-    def predict_stream(self, batches, output="posteriors", train_phase=False, beam_width=10, merge_repeated=True, threshold=None):
+    def predict_stream(self, batches, output="posteriors", train_phase=False, beam_width=10, merge_repeated=True, threshold=None,
+                       lm=None, lm_end=None, alpha=1.0, beta=0.0, top_paths=1):
         """Batches of an inference / validation run are independent of each other: this generator keeps two of them in flight.
         Batch n + 1 is uploaded (copy stream) and runs its encoder pass (stream ES, into the other FEAT buffer) beside batch n's
         fusion layer / head / decode kernels (stream 0) and beside the download of batch n - 1's result (its own stream, into
@@ -1019,6 +1020,9 @@ class Engine:
           "argmax"      (best (B, T - skip) int32, prob (B, T - skip) float32): mgr_frame_argmax on the device, the (B, T, C)
                         posteriors never travel to the host (decoding.confidence_filter_collapse does the rest)
           "beam"        (paths: list of B label lists, log-probabilities (B,) float64): mgr_ctc_beam_search on the device
+          "beam_lm"     (paths, score (B,) or (B, top_paths) float64, logp_ctc likewise): mgr_ctc_beam_search_lm on the device - the
+                        beam search with the label bigram lm / lm_end (weights alpha, beta) and top_paths hypotheses per sample, shaped
+                        as decoding.beam_search_lm_decode returns them; the two tables are uploaded once per call, not per batch
           "loss"        per-sample CTC losses (B,) float32  (a training engine; learning phase as train_phase)
           "segments"    list of B lists of (label, first_frame, last_frame, confidence): mgr_greedy_segments(threshold) on the device
                         where "argmax" runs mgr_frame_argmax - the greedy decode with its frame positions (decoding.greedy_segments)
@@ -1027,7 +1031,7 @@ class Engine:
         Results are bit-identical to the one-batch-at-a-time calls (predict / loss_on_batch): same kernels, same order per batch."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         Cn, skip = sp.num_classes, int(sp.ctc["skip"])
-        if output not in ("posteriors", "argmax", "beam", "loss", "segments", "align"):
+        if output not in ("posteriors", "argmax", "beam", "beam_lm", "loss", "segments", "align"):
             raise ValueError("unknown output %r" % (output,))
         if output == "loss" and self.inference_only:
             raise ValueError("output='loss' needs a training engine (labels, CTC workspace)")
@@ -1066,6 +1070,26 @@ class Engine:
             wsb = bufs("wsb%d" % beam_width, lambda: self.mem.bytes(self.lib.mgr_ctc_beam_ws_bytes(B, T, Cn, int(beam_width))))
             pins = bufs("beam", lambda: [(dev.pinned((B, T - skip), np.int32), dev.pinned((B,), np.int32), dev.pinned((B,), np.float64))
                                          for _ in range(2)])
+        elif output == "beam_lm":
+            from .decoding import lm_tables
+            NP = int(top_paths)
+            if not 1 <= NP <= int(beam_width):          # (before anything is allocated for it; the library checks again)
+                raise ValueError("top_paths %d out of [1, beam_width = %d]" % (NP, int(beam_width)))
+            ext, fin = lm_tables(Cn, lm, lm_end, alpha, beta)
+            dil = bufs("dil", lambda: self.mem.empty((B,), np.int32))
+            dil.upload(np.full(B, T - skip, np.int32))
+            dext = bufs("lm_ext", lambda: self.mem.empty((Cn + 1, Cn), np.float64))
+            dext.upload(ext)
+            dfin = None
+            if fin is not None:
+                dfin = bufs("lm_fin", lambda: self.mem.empty((Cn + 1,), np.float64))
+                dfin.upload(fin)
+            dnb = bufs("dnb%d" % NP, lambda: (self.mem.empty((B, NP, T - skip), np.int32), self.mem.empty((B, NP), np.int32),
+                                              self.mem.empty((B, NP), np.float64), self.mem.empty((B, NP), np.float64)))
+            wsb = bufs("wsl%d_%d" % (beam_width, NP),
+                       lambda: self.mem.bytes(self.lib.mgr_ctc_beam_lm_ws_bytes(B, T, Cn, int(beam_width), NP)))
+            pins = bufs("beam_lm%d" % NP, lambda: [(dev.pinned((B, NP, T - skip), np.int32), dev.pinned((B, NP), np.int32),
+                                                    dev.pinned((B, NP), np.float64), dev.pinned((B, NP), np.float64)) for _ in range(2)])
         elif output == "segments":
             # room for T - skip runs per sample, the most there can be: the count the kernel reports never exceeds what is downloaded
             cap = T - skip
@@ -1100,6 +1124,9 @@ class Engine:
             elif output == "beam":
                 po, pl, ps = pins[o]
                 r = ([[int(v) for v in po[b, :pl[b]]] for b in range(B)], ps.copy())
+            elif output == "beam_lm":
+                from .decoding import nbest_from_arrays
+                r = nbest_from_arrays(*pins[o], NP)
             elif output == "segments":
                 from .decoding import segments_from_arrays
                 r = segments_from_arrays(*pins[o])
@@ -1243,6 +1270,11 @@ class Engine:
                     dev.d2h_async(pins[o][0], dout)
                     dev.d2h_async(pins[o][1], dlen)
                     dev.d2h_async(pins[o][2], dlogp)
+                elif output == "beam_lm":
+                    dev.call("mgr_ctc_beam_search_lm", pring[o], dil, B, T, Cn, skip, Cn - 1, int(beam_width), C.c_float(float(sp.ctc["eps"])),
+                             dext, dfin, NP, *dnb, wsb, wsb.nbytes)
+                    for k in range(4):
+                        dev.d2h_async(pins[o][k], dnb[k])
                 elif output == "segments":
                     dev.call("mgr_greedy_segments", pring[o], B, T, Cn, skip, C.c_float(-1.0 if threshold is None else float(threshold)),
                              cap, *dseg)

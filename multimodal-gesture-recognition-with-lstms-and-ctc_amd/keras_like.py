@@ -555,7 +555,8 @@ class Model:
         pad = lambda a: np.concatenate([np.asarray(a), np.zeros((B - n,) + np.asarray(a).shape[1:], np.asarray(a).dtype)], axis=0)
         return ({k: pad(v) for k, v in arrs.items()} if isinstance(arrs, dict) else pad(arrs)), n
 
-    def predict_generator(self, generator, steps, verbose=0, decode=None, beam_width=10, threshold=None, **kwargs):
+    def predict_generator(self, generator, steps, verbose=0, decode=None, beam_width=10, threshold=None, lm=None, lm_end=None,
+                          alpha=1.0, beta=0.0, top_paths=1, **kwargs):
         """keras Model.predict_generator (sequence_decoding.py:118-127): the batches of the run are pipelined through
         Engine.predict_stream - upload and encoder pass of batch n + 1 beside the fusion layer / head of batch n and the
         download of batch n - 1 - and give bit for bit what predict_on_batch gives one batch at a time.
@@ -563,7 +564,9 @@ class Model:
         the per-frame best label and its probability computed on the device (what decode_batch needs; the (N, T, C) posteriors
         never cross PCIe); decode="beam" returns (paths, log-probabilities) of mgr_ctc_beam_search(beam_width); decode="segments"
         returns per sample a list of (label, first_frame, last_frame, confidence) - decoding.greedy_segments(posteriors, threshold),
-        computed on the device where "argmax" computes the frame maxima."""
+        computed on the device where "argmax" computes the frame maxima; decode="beam_lm" returns (paths, score, logp_ctc) of
+        mgr_ctc_beam_search_lm - the beam search with the label bigram lm / lm_end (decoding.bigram_lm) weighted alpha, the per-label
+        bonus beta and top_paths hypotheses per sample: decoding.beam_search_lm_decode of the posteriors, computed on the device."""
         steps = int(steps)
         if steps <= 0:
             return np.zeros((0,))
@@ -583,15 +586,18 @@ class Model:
                 counts.append(n)
                 yield ins
 
-        output = {None: "posteriors", "argmax": "argmax", "beam": "beam", "segments": "segments"}[decode]
+        output = {None: "posteriors", "argmax": "argmax", "beam": "beam", "beam_lm": "beam_lm", "segments": "segments"}[decode]
+        lm_args = dict(lm=lm, lm_end=lm_end, alpha=alpha, beta=beta, top_paths=top_paths) if output == "beam_lm" else {}
         outs = []
         for i, r in enumerate(e.predict_stream(feed(), output=output, train_phase=bool(learning_phase()), beam_width=beam_width,
-                                               threshold=threshold)):
+                                               threshold=threshold, **lm_args)):
             n = counts[i]
             if output in ("posteriors", "segments"):
                 outs.append(r[:n])
             elif output == "argmax":
                 outs.append((r[0][:n], r[1][:n]))
+            elif output == "beam_lm":
+                outs.append((r[0][:n], r[1][:n], r[2][:n]))
             else:
                 outs.append((r[0][:n], r[1][:n]))
             if verbose:
@@ -602,6 +608,8 @@ class Model:
             return [sg for o in outs for sg in o]
         if output == "argmax":
             return np.concatenate([o[0] for o in outs], axis=0), np.concatenate([o[1] for o in outs], axis=0)
+        if output == "beam_lm":
+            return [p for o in outs for p in o[0]], np.concatenate([o[1] for o in outs], axis=0), np.concatenate([o[2] for o in outs], axis=0)
         return [p for o in outs for p in o[0]], np.concatenate([o[1] for o in outs], axis=0)
 
     def align_generator(self, generator, steps, return_path=False):

@@ -1,7 +1,7 @@
 """Decode for the fusion network (reference multimodal_fusion/sequence_decoding.py:21-69)."""
 import numpy as np
 
-from ..decoding import greedy_decode, greedy_decode_argmax, greedy_segments, write_mlf
+from ..decoding import decode_beam_mlf, greedy_decode, greedy_decode_argmax, greedy_segments, write_mlf
 
 # gesture code -> class name; the blank (21) is emitted as "sil" (reference :26-29)
 map_gest = {0: "oov", 1: "VA", 2: "VQ", 3: "PF", 4: "FU", 5: "CP", 6: "CV", 7: "DC", 8: "SP", 9: "CN", 10: "FN",
@@ -41,3 +41,12 @@ def decode_segments(pred_out, f_list, out_file="final_ctc_recout_timed.mlf"):
     if out_file is not None:
         write_mlf(out_file, ret, f_list, ignore_list, "Sample%05d", segments=segs)
     return ret, segs
+
+
+def decode_beam(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, beam_width=10, top_paths=1, out_file="final_ctc_recout_beam.mlf"):
+    """Beam search with a label bigram and an N-best list (decoding.beam_search_lm_decode): pred_out (N, T, C) softmax - or the
+    (paths, score, logp_ctc) that Model.predict_generator(decode="beam_lm", top_paths=top_paths, ...) computed on the device.  lm /
+    lm_end as decoding.bigram_lm returns them (None: no prior), weighted alpha, beta per label.  The 1-best path goes through the class
+    map into the MLF; returns (1-best name lists, (paths, score, logp_ctc)) - with top_paths > 1 the ranked N-best lists."""
+    return decode_beam_mlf(pred_out, f_list, map_gest, ignore_list, "Sample%05d", out_file, top_paths=top_paths, lm=lm, lm_end=lm_end,
+                           alpha=alpha, beta=beta, beam_width=beam_width)

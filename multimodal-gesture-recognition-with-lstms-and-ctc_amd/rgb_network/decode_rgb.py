@@ -3,7 +3,7 @@ the reference's confidence threshold is commented out, so none applies - over th
 MLF writer with the ten-file ignore list."""
 import numpy as np
 
-from ..decoding import confidence_filter_collapse, greedy_segments, write_mlf
+from ..decoding import confidence_filter_collapse, decode_beam_mlf, greedy_segments, write_mlf
 from ..keras_like import Model
 from ..multimodal_fusion.sequence_decoding import ignore_list, map_gest  # noqa: F401  (the same 22 names and ignore list)
 from .cnn_lstm import load_model as _load_model
@@ -39,3 +39,13 @@ def decode_segments(pred_out, f_list, out_file="ctc_recout_timed.mlf"):
     if out_file is not None:
         write_mlf(out_file, ret, nums, ignore_list, "Sample%05d", segments=segs)
     return ret, segs
+
+
+def decode_beam(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, beam_width=10, top_paths=1, out_file="ctc_recout_beam.mlf"):
+    """Beam search with a label bigram and an N-best list (decoding.beam_search_lm_decode): pred_out (N, T, C) softmax - or the
+    (paths, score, logp_ctc) that Model.predict_generator(decode="beam_lm", top_paths=top_paths, ...) computed on the device.  lm /
+    lm_end as decoding.bigram_lm returns them (None: no prior), weighted alpha, beta per label.  The 1-best path goes through the class
+    map into the MLF; returns (1-best name lists, (paths, score, logp_ctc)) - with top_paths > 1 the ranked N-best lists."""
+    f_list = [int(str(f)[6:11]) if not isinstance(f, (int, np.integer)) else int(f) for f in f_list]
+    return decode_beam_mlf(pred_out, f_list, map_gest, ignore_list, "Sample%05d", out_file, top_paths=top_paths, lm=lm, lm_end=lm_end,
+                           alpha=alpha, beta=beta, beam_width=beam_width)
