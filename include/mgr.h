@@ -563,6 +563,34 @@ int mgr_ctc_align(mgr_ctx* ctx, const float* P, const int32_t* labels, const int
 int mgr_greedy_segments(mgr_ctx* ctx, const float* P, int B, int T, int C, int skip, float thr, int cap, int32_t* n_runs, int32_t* lab,
                         int32_t* seg, float* conf);
 
+/* ---- K12: scoring decodes: the weighted edit distance of n_pairs pairs of label sequences, with the substitution /
+ * deletion / insertion split of HTK's HResults, in one launch.  All pointers are device memory.
+ * hyp [n_hyp,Lh], ref [n_ref,Lr] int32, rows padded with -1; hyp_len [n_hyp] / ref_len [n_ref] int32 or NULL: NULL = the whole row,
+ * otherwise clipped into [0, width].  Before comparing, a row loses every entry < 0 and every entry v < 64 whose bit is set in
+ * ignore_mask (so the -1 padded lab rows of mgr_greedy_segments and the out rows of the beam kernels feed it unchanged, and the
+ * blank / "sil" is stripped here); what remains is h with m labels and r with n labels.  Pair p compares h of row pair_h[p] with r of
+ * row pair_r[p]; both arrays NULL: pair p is (p, p) and n_hyp == n_ref == n_pairs.  The indices are device data: THE CALLER must
+ * keep them in [0, n_hyp) / [0, n_ref) (the kernel clamps what it reads, it cannot report).
+ * Result, whatever the traversal order: over all monotone alignments of h to r - a hit pairs equal labels at cost 0; a substitution
+ * pairs unequal labels, cost_sub, S + 1; a deletion is a ref label without partner, cost_del, D + 1; an insertion is a hyp label
+ * without partner, cost_ins, I + 1 - the lexicographically smallest tuple (cost, S, D, I).  dist [n_pairs] = cost, counts
+ * [n_pairs,4] = (H, S, D, I) with H = n - S - D, lens [n_pairs,2] = (m, n).  (Lexicographic order is compatible with addition, so
+ * the DP over tuples is exact.)
+ * ops [n_pairs,Lh+Lr] int8 and n_ops [n_pairs] may be NULL.  ops holds one alignment that attains the tuple, in forward order: 0 hit,
+ * 1 substitution, 2 deletion, 3 insertion, -1 behind the n_ops = H + S + D + I entries.  It is the walk back from (m, n) that takes
+ * at each cell the first of diagonal, deletion, insertion whose predecessor tuple plus the step's tuple equals the cell's tuple.
+ * The walk needs 2 bits per cell: ws >= the size query with want_ops = 1 when ops is given (written only then); without ops the
+ * query is 0 and ws may be NULL.
+ * Lh, Lr <= MGR_EDIT_MAX_LEN; costs in [1, MGR_EDIT_MAX_COST] (the cost stays below 2^27).  Integer arithmetic, no atomics:
+ * deterministic, and a pair's result does not depend on the other pairs. */
+#define MGR_EDIT_MAX_LEN  4095
+#define MGR_EDIT_MAX_COST 16384
+size_t mgr_edit_distance_ws_bytes(int n_pairs, int Lh, int Lr, int want_ops);
+int mgr_edit_distance(mgr_ctx* ctx, const int32_t* hyp, const int32_t* hyp_len, int n_hyp, int Lh, const int32_t* ref,
+                      const int32_t* ref_len, int n_ref, int Lr, const int32_t* pair_h, const int32_t* pair_r, int n_pairs, int cost_sub,
+                      int cost_del, int cost_ins, uint64_t ignore_mask, int32_t* dist, int32_t* counts, int32_t* lens, int8_t* ops,
+                      int32_t* n_ops, void* ws, size_t ws_bytes);
+
 /* ---- K10: TimeDistributed CNN front-end of the RGB network (rgb_network/cnn_lstm.py: conv_1 / conv_3 / conv_5, each followed by
  * MaxPooling2D) ------------------------------------------------------------------------------------------------------------------
  * Per frame of N = B*T frames, channels-last: X [N][Hin][Win][Cin] -> valid Conv2D (W [ks][ks][Cin][Cout], b [Cout]) -> ReLU ->

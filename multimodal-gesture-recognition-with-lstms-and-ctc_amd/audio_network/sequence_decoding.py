@@ -1,7 +1,7 @@
 """Decode for the audio network (reference audio_network/sequence_decoding.py:19-69): word-level classes, thr .75."""
 import numpy as np
 
-from ..decoding import decode_beam_mlf, greedy_decode, greedy_decode_argmax, greedy_segments, write_mlf
+from ..decoding import HTK_COSTS, decode_beam_mlf, decode_score_map, greedy_decode, greedy_decode_argmax, greedy_segments, write_mlf
 
 _words = ["oov", "Vattene", "Vieni", "qui", "Perfetto", "E'", "un", "furbo", "Che", "due", "palle", "vuoi", "Vanno",
           "d'accordo", "Sei", "Pazzo", "Cos'hai", "combinato", "Non", "me", "ne", "frega", "niente", "ok", "Cosa", "ti",
@@ -49,3 +49,9 @@ def decode_beam(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, bea
     map into the MLF; returns (1-best name lists, (paths, score, logp_ctc)) - with top_paths > 1 the ranked N-best lists."""
     return decode_beam_mlf(pred_out, f_list, map_gest, ignore_list, "Sample%05d_audio", out_file, top_paths=top_paths, lm=lm, lm_end=lm_end,
                            alpha=alpha, beta=beta, beam_width=beam_width)
+
+
+def decode_score(hyp_ids, ref_ids, costs=HTK_COSTS, confusion=True):
+    """HResults-style counts (H, S, D, I, corr, acc, confusion matrix) of decoded label ids against reference label ids on the device,
+    "sil" dropped from both (decoding.decode_score_map with this module's class map)."""
+    return decode_score_map(hyp_ids, ref_ids, map_gest, costs=costs, confusion=confusion)

@@ -371,3 +371,220 @@ def score_mlf(ref_path, rec_path, ignore=("sil",)):
     names = sorted(set(ref) & set(rec))
     strip = lambda seq: [x for x in seq if x not in ignore]
     return label_error_rate([strip(rec[n]) for n in names], [strip(ref[n]) for n in names]), len(names)
+
+
+# ---- scoring on the device (K12): mgr_edit_distance and what is built on it -----------------------------------------
+HTK_COSTS = (10, 7, 7)      # (substitution, deletion, insertion) of HTK's HResults (HTK book, 17.4 of the 3.4 edition)
+NIST_COSTS = (4, 3, 3)      # ... of its -n switch, the NIST scoring package's alignment
+EDIT_MAX_LEN, EDIT_MAX_COST = 4095, 16384       # MGR_EDIT_MAX_LEN / MGR_EDIT_MAX_COST of include/mgr.h
+
+
+def check_costs(costs):
+    """(sub, del, ins) as three ints in [1, EDIT_MAX_COST], or ValueError."""
+    c = tuple(costs)
+    if len(c) != 3 or any(int(v) != v for v in c) or not all(1 <= int(v) <= EDIT_MAX_COST for v in c):
+        raise ValueError("costs %r: three integers (sub, del, ins) in [1, %d]" % (costs, EDIT_MAX_COST))
+    return tuple(int(v) for v in c)
+
+
+def ignore_mask(ignore):
+    """Label ids (each in [0, 64)) -> the bit mask mgr_edit_distance takes."""
+    mask = 0
+    for v in ignore or ():
+        if not 0 <= int(v) < 64:
+            raise ValueError("ignored label %r is not in [0, 64)" % (v,))
+        mask |= 1 << int(v)
+    return mask
+
+
+def edit_distances(hyps, refs, pairs=None, costs=(1, 1, 1), ignore=(), return_ops=False, dev=None):
+    """Weighted edit distances of many pairs in one launch (mgr_edit_distance).  hyps / refs: whatever pack_labels takes (a padded
+    array or a list of label lists); pairs: None - pair p is (hyps[p], refs[p]) - or a (P, 2) array of (hyp row, ref row) indices,
+    range-checked here; costs = (sub, del, ins); ignore: label ids in [0, 64) that both sides lose before the comparison.
+    Returns dist (P,) int32, counts (P, 4) int32 = (H, S, D, I), lens (P, 2) int32 = (m, n) after the filter[, ops: a list of P int8
+    arrays, the alignment in forward order: 0 hit, 1 substitution, 2 deletion, 3 insertion].  The tuple (cost, S, D, I) is the
+    lexicographically smallest over all alignments (include/mgr.h)."""
+    cs, cd, ci = check_costs(costs)
+    mask = ignore_mask(ignore)
+    h, _ = pack_labels(hyps)
+    r, _ = pack_labels(refs)
+    if pairs is None:
+        if h.shape[0] != r.shape[0]:
+            raise ValueError("%d hypotheses for %d references" % (h.shape[0], r.shape[0]))
+        P, pr = h.shape[0], None
+    else:
+        pr = np.ascontiguousarray(np.asarray(pairs, np.int64).reshape(-1, 2))
+        P = pr.shape[0]
+        if P and (pr.min() < 0 or pr[:, 0].max() >= h.shape[0] or pr[:, 1].max() >= r.shape[0]):
+            raise IndexError("pair index out of range (%d hypotheses, %d references)" % (h.shape[0], r.shape[0]))
+    if h.shape[1] > EDIT_MAX_LEN or r.shape[1] > EDIT_MAX_LEN:
+        raise ValueError("rows of %d / %d labels: at most %d" % (h.shape[1], r.shape[1], EDIT_MAX_LEN))
+    if P == 0:
+        z = np.zeros((0,), np.int32), np.zeros((0, 4), np.int32), np.zeros((0, 2), np.int32)
+        return z + ([],) if return_ops else z
+    dev = dev or default_device()
+    Lh, Lr = h.shape[1], r.shape[1]
+    bufs = [dev.array(h), dev.array(r)]
+    try:
+        dph = dpr = None
+        if pr is not None:
+            bufs += [dev.array(pr[:, 0].astype(np.int32)), dev.array(pr[:, 1].astype(np.int32))]
+            dph, dpr = bufs[2], bufs[3]
+        ddist, dcnt, dlen = dev.empty((P,), np.int32), dev.empty((P, 4), np.int32), dev.empty((P, 2), np.int32)
+        bufs += [ddist, dcnt, dlen]
+        dops = dnops = ws = None
+        if return_ops:
+            dops, dnops = dev.empty((P, Lh + Lr), np.int8), dev.empty((P,), np.int32)
+            ws = dev.bytes(dev.lib.mgr_edit_distance_ws_bytes(P, Lh, Lr, 1))
+            bufs += [dops, dnops, ws]
+        dev.call("mgr_edit_distance", bufs[0], None, h.shape[0], Lh, bufs[1], None, r.shape[0], Lr, dph, dpr, P, cs, cd, ci, mask,
+                 ddist, dcnt, dlen, dops, dnops, ws, ws.nbytes if ws is not None else 0)
+        res = (ddist.download(), dcnt.download(), dlen.download())
+        if return_ops:
+            o, k = dops.download(), dnops.download()
+            res += ([o[p, :k[p]].copy() for p in range(P)],)
+    finally:
+        for a in bufs:
+            a.free()
+    return res
+
+
+def score_from_counts(counts, lens, loss=None):
+    """Sums of per-sample (H, S, D, I) / (m, n) -> the figures HResults prints: ler = (S + D + I) / N, corr = H / N, acc = (H - I) / N
+    (N = the number of reference labels; 0 -> N taken as 1)."""
+    counts = np.asarray(counts, np.int64).reshape(-1, 4)
+    H, S, D, I = (int(v) for v in counts.sum(axis=0))
+    N = int(np.asarray(lens, np.int64).reshape(-1, 2)[:, 1].sum())
+    den = max(1, N)
+    return {"H": H, "S": S, "D": D, "I": I, "N": N, "ler": (S + D + I) / den, "corr": H / den, "acc": (H - I) / den}
+
+
+def confusion_from_ops(hyps, refs, ops, n_classes, ignore=()):
+    """(C + 1, C + 1) int64 [ref label or C for "inserted", hyp label or C for "deleted"] from the alignments of edit_distances."""
+    Cn = int(n_classes)
+    conf = np.zeros((Cn + 1, Cn + 1), np.int64)
+    h, _ = pack_labels(hyps)
+    r, _ = pack_labels(refs)
+    drop = set(int(v) for v in ignore)
+    for p, o in enumerate(ops):
+        hs = [int(v) for v in h[p] if v >= 0 and int(v) not in drop]
+        rs = [int(v) for v in r[p] if v >= 0 and int(v) not in drop]
+        o = np.asarray(o)
+        if int((o != 2).sum()) != len(hs) or int((o != 3).sum()) != len(rs):
+            raise ValueError("pair %d: the alignment does not consume its %d / %d labels" % (p, len(hs), len(rs)))
+        # every step but a deletion consumes the next hyp label, every step but an insertion the next ref label
+        hl = np.where(o != 2, np.asarray(hs + [Cn], np.int64)[np.clip(np.cumsum(o != 2) - 1, 0, len(hs))], Cn)
+        rl = np.where(o != 3, np.asarray(rs + [Cn], np.int64)[np.clip(np.cumsum(o != 3) - 1, 0, len(rs))], Cn)
+        if hl.size and (hl.max() > Cn or rl.max() > Cn):
+            raise ValueError("a label is not below n_classes = %d" % Cn)
+        np.add.at(conf, (rl, hl), 1)
+    return conf
+
+
+def score_sequences(hyps, refs, costs=(1, 1, 1), ignore=(), confusion=False, n_classes=None, dev=None):
+    """Score hypotheses against references on the device: a dict with the summed H, S, D, I and N (reference labels), ler = (S + D +
+    I) / max(1, N), HResults' two figures corr = H / N and acc = (H - I) / N, dist_sum, per_sample = {"dist", "counts", "lens"} and,
+    with confusion, "confusion": a (C + 1, C + 1) int64 matrix [ref label or C for "inserted", hyp label or C for "deleted"] formed
+    from the alignments with numpy (n_classes = C; default: the largest label + 1)."""
+    res = edit_distances(hyps, refs, costs=costs, ignore=ignore, return_ops=confusion, dev=dev)
+    dist, counts, lens = res[:3]
+    out = score_from_counts(counts, lens)
+    out["dist_sum"] = int(dist.astype(np.int64).sum())
+    out["per_sample"] = {"dist": dist, "counts": counts, "lens": lens}
+    if confusion:
+        if n_classes is None:
+            h, _ = pack_labels(hyps)
+            r, _ = pack_labels(refs)
+            n_classes = int(max(h.max(initial=-1), r.max(initial=-1))) + 1
+        out["confusion"] = confusion_from_ops(hyps, refs, res[3], n_classes, ignore)
+    return out
+
+
+def score_mlf_counts(ref_path, rec_path, ignore=("sil",), costs=HTK_COSTS, dev=None):
+    """score_sequences over two HTK master label files, over the samples present in both: label names are mapped to ids (sorted names
+    of both files, the ignored ones left out beforehand).  The alignment costs default to HResults' (10, 7, 7), so H / S / D / I, corr
+    and acc are HResults' quantities by construction; parity with the HResults BINARY is unpinned - HTK is not available to this
+    project, no output of it has been compared.  Returns the score_sequences dict plus "n_samples" and "names" (id -> label name)."""
+    ref, rec = read_mlf(ref_path), read_mlf(rec_path)
+    names = sorted(set(ref) & set(rec))
+    strip = lambda seq: [x for x in seq if x not in ignore]
+    hyps, refs = [strip(rec[n]) for n in names], [strip(ref[n]) for n in names]
+    vocab = sorted(set(x for s in hyps + refs for x in s))
+    ids = {x: i for i, x in enumerate(vocab)}
+    out = score_sequences([[ids[x] for x in s] for s in hyps], [[ids[x] for x in s] for s in refs], costs=costs, dev=dev)
+    out["n_samples"], out["names"] = len(names), vocab
+    return out
+
+
+def _flatten_nbest(paths):
+    """Per sample a ranked list of label lists -> (flat list of hypotheses, first flat index per sample (N + 1,))."""
+    flat, off = [], [0]
+    for hyps in paths:
+        flat.extend(list(h) for h in hyps)
+        off.append(len(flat))
+    return flat, np.asarray(off, np.int64)
+
+
+def nbest_attainable(paths, refs, costs=(1, 1, 1), ignore=(), dev=None):
+    """What the best choice from N-best lists would score - the best attainable error rate of the lists, the bound a rescoring pass
+    is measured against: per sample the smallest distance to its reference over its hypotheses
+    (what beam_search_lm_decode returns with top_paths > 1) and the rank that attains it (ties: the better rank; no hypothesis: the
+    distance of the empty one, rank -1), in ONE launch over all pairs.  Returns (dist (N,) int64, rank (N,) int64, ler = sum dist /
+    max(1, sum n)) - with unit costs the label error rate no rescoring pass over these lists can beat."""
+    flat, off = _flatten_nbest(paths)
+    N = len(paths)
+    rlab, _ = pack_labels(refs)
+    if rlab.shape[0] != N:
+        raise ValueError("%d references for %d samples" % (rlab.shape[0], N))
+    flat.append([])                                     # the empty hypothesis: its distance stands in where a sample has none
+    pairs = [(k, b) for b in range(N) for k in range(off[b], off[b + 1])] + [(len(flat) - 1, b) for b in range(N)]
+    dist, _, lens = edit_distances(flat, rlab, pairs=pairs, costs=costs, ignore=ignore, dev=dev)
+    npairs = int(off[-1])
+    best, rank = dist[npairs:].astype(np.int64), -np.ones(N, np.int64)
+    for b in range(N):
+        if off[b + 1] > off[b]:
+            d = dist[off[b]:off[b + 1]]
+            rank[b] = int(np.argmin(d))                 # (the first minimum: ties go to the better rank)
+            best[b] = int(d[rank[b]])
+    return best, rank, float(best.sum()) / max(1, int(lens[npairs:, 1].sum()))
+
+
+def mbr_decode(paths, scores, scale=1.0, costs=(1, 1, 1), dev=None):
+    """Minimum-Bayes-risk pick from N-best lists: per sample with K surviving hypotheses, w = softmax(scale * score) over them (fp64,
+    host), risk_k = sum_j w_j * dist(hyp = h_k, ref = h_j), and the pick is the smallest risk, ties to the better rank.  All K x K
+    distances of all samples go to the device in one launch.  paths / scores as beam_search_lm_decode(top_paths > 1) returns them.
+    Returns (picked paths: a label list per sample, [] where none survives; picked ranks (N,) int64, -1 likewise; risk (N,
+    top_paths) float64, +inf where there is no hypothesis).  K = 1 returns the 1-best.  Whether this lowers an error rate on real
+    data is not measured here."""
+    flat, off = _flatten_nbest(paths)
+    N = len(paths)
+    scores = np.asarray(scores, np.float64).reshape(N, -1)
+    NP = scores.shape[1]
+    pairs = [(k, j) for b in range(N) for k in range(off[b], off[b + 1]) for j in range(off[b], off[b + 1])]
+    dist = edit_distances(flat, flat, pairs=pairs, costs=costs, dev=dev)[0] if pairs else np.zeros(0, np.int32)
+    risk = np.full((N, NP), np.inf)
+    picks, ranks, q = [], -np.ones(N, np.int64), 0
+    for b in range(N):
+        K = int(off[b + 1] - off[b])
+        if K == 0:
+            picks.append([])
+            continue
+        if K > NP:
+            raise ValueError("sample %d has %d hypotheses, scores hold %d" % (b, K, NP))
+        z = float(scale) * scores[b, :K]
+        w = np.exp(z - z.max())
+        w /= w.sum()
+        d = dist[q:q + K * K].reshape(K, K).astype(np.float64)
+        q += K * K
+        risk[b, :K] = d @ w
+        ranks[b] = int(np.argmin(risk[b, :K]))
+        picks.append(list(paths[b][ranks[b]]))
+    return picks, ranks, risk
+
+
+def decode_score_map(hyp_ids, ref_ids, map_gest, costs=HTK_COSTS, confusion=True, dev=None):
+    """What the networks' decode_score share: score_sequences of label-id sequences (what greedy_decode / the beam decoders return,
+    blank runs included) over a module's class map - every id whose name is "sil" is dropped from both sides, the confusion matrix
+    covers the map's classes, the alignment costs default to HResults'."""
+    sil = [k for k, v in map_gest.items() if v == "sil" and k >= 0]
+    return score_sequences(hyp_ids, ref_ids, costs=costs, ignore=sil, confusion=confusion, n_classes=1 + max(map_gest), dev=dev)

@@ -2,7 +2,7 @@
 0.97 confidence threshold, the list.remove quirk, collapse, MLF."""
 import numpy as np
 
-from ..decoding import decode_beam_mlf, greedy_decode, greedy_segments, write_mlf
+from ..decoding import HTK_COSTS, decode_beam_mlf, decode_score_map, greedy_decode, greedy_segments, write_mlf
 from ..multimodal_fusion.sequence_decoding import ignore_list, map_gest
 
 THRESHOLD = 0.97
@@ -34,3 +34,9 @@ def decode_beam(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, bea
     map into the MLF; returns (1-best name lists, (paths, score, logp_ctc)) - with top_paths > 1 the ranked N-best lists."""
     return decode_beam_mlf(pred_out, f_list, map_gest, ignore_list, "Sample%05d", out_file, top_paths=top_paths, lm=lm, lm_end=lm_end,
                            alpha=alpha, beta=beta, beam_width=beam_width)
+
+
+def decode_score(hyp_ids, ref_ids, costs=HTK_COSTS, confusion=True):
+    """HResults-style counts (H, S, D, I, corr, acc, confusion matrix) of decoded label ids against reference label ids on the device,
+    "sil" dropped from both (decoding.decode_score_map with this module's class map)."""
+    return decode_score_map(hyp_ids, ref_ids, map_gest, costs=costs, confusion=confusion)

@@ -1006,7 +1006,7 @@ class Engine:
     EV_D1S = (57, 58)     # the depth-1 scans that read depth-1 Z set 0 / 1 are done (stream ES)
 
     def predict_stream(self, batches, output="posteriors", train_phase=False, beam_width=10, merge_repeated=True, threshold=None,
-                       lm=None, lm_end=None, alpha=1.0, beta=0.0, top_paths=1):
+                       lm=None, lm_end=None, alpha=1.0, beta=0.0, top_paths=1, decode="greedy", ignore=None, costs=(1, 1, 1)):
         """Batches of an inference / validation run are independent of each other: this generator keeps two of them in flight.
         Batch n + 1 is uploaded (copy stream) and runs its encoder pass (stream ES, into the other FEAT buffer) beside batch n's
         fusion layer / head / decode kernels (stream 0) and beside the download of batch n - 1's result (its own stream, into
@@ -1014,7 +1014,7 @@ class Engine:
         predict_generator over the whole set (sequence_decoding.py:118-127) and with the validation loop of every epoch
         (multimodal.py:264-269), one blocking batch at a time.
 
-        batches: iterable of input dicts {stream name: (B, T, F)} - for output="loss" and "align" of tuples (inputs, labels,
+        batches: iterable of input dicts {stream name: (B, T, F)} - for output="loss", "align" and "score" of tuples (inputs, labels,
         input_length, label_length).  Yields, in order, per batch:
           "posteriors"  P (B, T, C) float32                  (learning phase 0 unless train_phase)
           "argmax"      (best (B, T - skip) int32, prob (B, T - skip) float32): mgr_frame_argmax on the device, the (B, T, C)
@@ -1028,16 +1028,24 @@ class Engine:
                         where "argmax" runs mgr_frame_argmax - the greedy decode with its frame positions (decoding.greedy_segments)
           "align"       (segments: list of B lists of (label, first_frame, last_frame, confidence), logp (B,) float64, path
                         (B, T - skip) int32): mgr_ctc_align of each sample's labels to its posteriors (a training engine, like "loss")
+          "score"       (loss (B,) float32, dist (B,) int32, counts (B, 4) int32 = (H, S, D, I), lens (B, 2) int32 = (m, n)): the CTC
+                        loss exactly as "loss" computes it and, on the output stream, the decode kernel of decode = "greedy"
+                        (mgr_greedy_segments with threshold) | "beam" | "beam_lm" (beam_width, lm, ... as above, one path) followed
+                        by mgr_edit_distance of its device output against the batch's labels with costs = (sub, del, ins), both
+                        sides without the labels in ignore (None: the blank, which the greedy decode keeps).  36 bytes per sample
+                        travel to the host, no label sequence does (a training engine, like "loss")
         Results are bit-identical to the one-batch-at-a-time calls (predict / loss_on_batch): same kernels, same order per batch."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         Cn, skip = sp.num_classes, int(sp.ctc["skip"])
-        if output not in ("posteriors", "argmax", "beam", "beam_lm", "loss", "segments", "align"):
+        if output not in ("posteriors", "argmax", "beam", "beam_lm", "loss", "segments", "align", "score"):
             raise ValueError("unknown output %r" % (output,))
         if output == "loss" and self.inference_only:
             raise ValueError("output='loss' needs a training engine (labels, CTC workspace)")
         if output == "align" and self.inference_only:
             raise ValueError("output='align' needs a training engine (labels)")
-        labelled = output in ("loss", "align")
+        if output == "score" and self.inference_only:
+            raise ValueError("output='score' needs a training engine (labels, CTC workspace)")
+        labelled = output in ("loss", "align", "score")
         self._bind()
         if self._prefetched is not None:     # a pipelined training encoder pass is in flight: let it finish, then discard it
             dev.wait(0, self.ES)
@@ -1106,6 +1114,48 @@ class Engine:
             pins = bufs("align", lambda: [(dev.pinned((B, T - skip), np.int32), dev.pinned((B, Lm, 2), np.int32),
                                            dev.pinned((B, Lm), np.float32), dev.pinned((B,), np.float64)) for _ in range(2)])
             host_labels = {}
+        elif output == "score":
+            from .decoding import EDIT_MAX_LEN, check_costs, ignore_mask, lm_tables
+            if decode not in ("greedy", "beam", "beam_lm"):
+                raise ValueError("unknown decode %r for output='score'" % (decode,))
+            if T - skip > EDIT_MAX_LEN or self.Lmax > EDIT_MAX_LEN:
+                raise ValueError("T - skip = %d or Lmax = %d above the %d labels mgr_edit_distance compares" % (T - skip, self.Lmax, EDIT_MAX_LEN))
+            ecosts = check_costs(costs)
+            emask = ignore_mask((Cn - 1,) if ignore is None else ignore)
+            # the decode kernels' device outputs: the buffers of the matching outputs above (one set: decode, comparison and copies of
+            # a batch are consecutive on the output stream); the losses in two slots, as below
+            if decode == "greedy":
+                cap = T - skip
+                dseg = bufs("dseg", lambda: (self.mem.empty((B,), np.int32), self.mem.empty((B, cap), np.int32),
+                                             self.mem.empty((B, cap, 2), np.int32), self.mem.empty((B, cap), np.float32)))
+                hyp_d, hyplen_d = dseg[1], dseg[0]
+            else:
+                dil = bufs("dil", lambda: self.mem.empty((B,), np.int32))
+                dil.upload(np.full(B, T - skip, np.int32))
+                if decode == "beam":
+                    dout = bufs("dout", lambda: self.mem.empty((B, T - skip), np.int32))
+                    dlen = bufs("dlen", lambda: self.mem.empty((B,), np.int32))
+                    dlogp = bufs("dlogp", lambda: self.mem.empty((B,), np.float64))
+                    wsb = bufs("wsb%d" % beam_width, lambda: self.mem.bytes(self.lib.mgr_ctc_beam_ws_bytes(B, T, Cn, int(beam_width))))
+                    hyp_d, hyplen_d = dout, dlen
+                else:
+                    NP = 1
+                    ext, fin = lm_tables(Cn, lm, lm_end, alpha, beta)
+                    dext = bufs("lm_ext", lambda: self.mem.empty((Cn + 1, Cn), np.float64))
+                    dext.upload(ext)
+                    dfin = None
+                    if fin is not None:
+                        dfin = bufs("lm_fin", lambda: self.mem.empty((Cn + 1,), np.float64))
+                        dfin.upload(fin)
+                    dnb = bufs("dnb%d" % NP, lambda: (self.mem.empty((B, NP, T - skip), np.int32), self.mem.empty((B, NP), np.int32),
+                                                      self.mem.empty((B, NP), np.float64), self.mem.empty((B, NP), np.float64)))
+                    wsb = bufs("wsl%d_%d" % (beam_width, NP),
+                               lambda: self.mem.bytes(self.lib.mgr_ctc_beam_lm_ws_bytes(B, T, Cn, int(beam_width), NP)))
+                    hyp_d, hyplen_d = dnb[0], dnb[1]      # (a length of -1 - no hypothesis - is clipped to 0 by the comparison)
+            dscore = bufs("dscore", lambda: (self.mem.empty((B,), np.int32), self.mem.empty((B, 4), np.int32), self.mem.empty((B, 2), np.int32)))
+            lring = bufs("lring", lambda: [self.loss_b, self.mem.empty((B,))])
+            pins = bufs("score", lambda: [(dev.pinned((B,), np.float32), dev.pinned((B,), np.int32), dev.pinned((B, 4), np.int32),
+                                           dev.pinned((B, 2), np.int32)) for _ in range(2)])
         else:
             pins = bufs("loss", lambda: [dev.pinned((B,), np.float32) for _ in range(2)])
             # one device buffer per output slot, like pring: batch i's copy (its own stream, behind EV_FUSED only) must not find
@@ -1135,6 +1185,8 @@ class Engine:
                 lab, ll = host_labels.pop(i)
                 ppath, pseg, pconf, plogp = pins[o]
                 r = (alignment_from_arrays(np.clip(lab, 0, Cn - 1), ll, pseg, pconf, plogp), plogp.copy(), ppath.copy())
+            elif output == "score":
+                r = tuple(a.copy() for a in pins[o])
             else:
                 r = pins[o].copy()
             # the status block of THIS batch's pass travels with its result (no extra synchronisation): the samples whose hidden
@@ -1254,6 +1306,10 @@ class Engine:
                              C.c_float(float(sp.ctc["eps"])), *aring[o], wsa, wsa.nbytes)
                     dev.record(self.EV_LAB[self._lab_slot])
                     self._lab_user[self._lab_slot] = 1 << 60
+                elif output == "score":
+                    dev.call("mgr_ctc_loss_grad", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1,
+                             float(sp.ctc["eps"]), 1.0, lring[o], 0, self.ws_ctc, self.ws_ctc.nbytes)
+                    ref_d, reflen_d, lab_slot = self.labels_d, self.llen_d, self._lab_slot     # (read again on the output stream below)
                 dev.record(self.EV_FUSED[f])
                 # ---- decode kernels and the way back to pinned host memory: their own stream, beside batch i + 1's fusion layer
                 dev.stream(OUT)
@@ -1283,6 +1339,23 @@ class Engine:
                 elif output == "align":
                     for k in range(4):
                         dev.d2h_async(pins[o][k], aring[o][k])
+                elif output == "score":
+                    if decode == "greedy":
+                        dev.call("mgr_greedy_segments", pring[o], B, T, Cn, skip, C.c_float(-1.0 if threshold is None else float(threshold)),
+                                 cap, *dseg)
+                    elif decode == "beam":
+                        dev.call("mgr_ctc_beam_search", pring[o], dil, B, T, Cn, skip, Cn - 1, int(beam_width), C.c_float(float(sp.ctc["eps"])),
+                                 1 if merge_repeated else 0, dout, dlen, dlogp, wsb, wsb.nbytes)
+                    else:
+                        dev.call("mgr_ctc_beam_search_lm", pring[o], dil, B, T, Cn, skip, Cn - 1, int(beam_width),
+                                 C.c_float(float(sp.ctc["eps"])), dext, dfin, NP, *dnb, wsb, wsb.nbytes)
+                    dev.call("mgr_edit_distance", hyp_d, hyplen_d, B, T - skip, ref_d, reflen_d, B, self.Lmax, None, None, B, ecosts[0],
+                             ecosts[1], ecosts[2], emask, dscore[0], dscore[1], dscore[2], None, None, None, 0)
+                    dev.record(self.EV_LAB[lab_slot])        # the labels' last reader of this batch is on this stream
+                    self._lab_user[lab_slot] = 1 << 60
+                    dev.d2h_async(pins[o][0], lring[o])
+                    for k in range(3):
+                        dev.d2h_async(pins[o][k + 1], dscore[k])
                 else:
                     dev.d2h_async(pins[o], lring[o])
                 dev.d2h_async(spin[o], self._pass_status[o])

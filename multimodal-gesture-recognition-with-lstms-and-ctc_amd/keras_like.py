@@ -484,7 +484,12 @@ class Model:
         return e.predict(ins)
 
     def fit_generator(self, generator, steps_per_epoch, epochs=1, verbose=1, callbacks=None, validation_data=None,
-                      validation_steps=None, initial_epoch=0, **kwargs):
+                      validation_steps=None, initial_epoch=0, val_score=None, **kwargs):
+        """val_score: None - validation logs val_loss (evaluate_generator), as before; True or a dict of score_generator arguments -
+        validation is ONE combined pass (score_generator) that logs val_loss, val_ler, val_corr and val_acc, so that
+        ModelCheckpoint(monitor="val_ler", save_best_only=True) / EarlyStopping(monitor="val_ler") select by the label error rate
+        the task is judged by ("acc" in the monitor's name selects max mode, val_ler falls to min).  The pass runs in whatever
+        learning phase is set, as evaluate_generator does (the reference leaves it at 1 during validation)."""
         self._require_trainable()
         callbacks = list(callbacks or [])
         hist = History()
@@ -531,7 +536,11 @@ class Model:
                               "hidden state or gave up): the weights are those of the last good step - Model.clear_scan_status() "
                               "after restoring a good state" % (self._engine.updates_skipped - skipped0))
             if validation_data is not None and validation_steps:
-                logs["val_loss"] = self.evaluate_generator(validation_data, validation_steps)
+                if val_score is None or val_score is False:
+                    logs["val_loss"] = self.evaluate_generator(validation_data, validation_steps)
+                else:
+                    sc = self.score_generator(validation_data, validation_steps, **(val_score if isinstance(val_score, dict) else {}))
+                    logs.update({"val_loss": sc["loss"], "val_ler": sc["ler"], "val_corr": sc["corr"], "val_acc": sc["acc"]})
             if verbose:
                 print("Epoch %d/%d - %.1fs - %s" % (epoch + 1, epochs, time.time() - t0,
                                                     " - ".join("%s: %.4f" % kv for kv in logs.items())))
@@ -674,6 +683,60 @@ class Model:
             # ModelCheckpoint(save_best_only) / EarlyStopping decide - is the mean over the global batches (one scalar all-reduce)
             v = self.comm.allreduce_sum_scalar(v) / self.world
         return v
+
+    def score_generator(self, generator, steps, decode="greedy", threshold=None, ignore=None, costs=(1, 1, 1), **decode_kwargs):
+        """Loss AND label error rate of `steps` batches of a training generator in one pipelined pass (Engine.predict_stream,
+        output="score"): per batch the CTC loss as evaluate_generator computes it, the decode kernel of decode = "greedy" (threshold:
+        the confidence filter) | "beam" | "beam_lm" (decode_kwargs: beam_width, lm, lm_end, alpha, beta) and mgr_edit_distance of its
+        device output against the_labels - what decoding.score_sequences gives for predict_generator(decode=...) of the same batches,
+        without a decoded sequence leaving the device.  ignore=None drops the blank (C - 1: the greedy decode keeps blank runs, the
+        labels never hold it); costs = (sub, del, ins).  Returns {"loss", "ler", "corr", "acc", "H", "S", "D", "I", "N", "per_sample":
+        {"loss", "dist", "counts", "lens"}}: ler = (S + D + I) / N, corr = H / N, acc = (H - I) / N over all samples (rows padded into
+        a short last batch are dropped), loss = the mean of the batch means.  Data parallel: the integer sums and the loss are
+        all-reduced, every rank logs the figures of the global batches.  Runs in whatever learning phase is set."""
+        from .decoding import score_from_counts
+        steps = int(steps)
+        if steps <= 0:
+            return dict(score_from_counts(np.zeros((0, 4)), np.zeros((0, 2))), loss=float("nan"), per_sample=None)
+        first = next(generator)
+        x0 = first[0]
+        f0 = next(iter(self._split_inputs(x0).values()))
+        B = f0.shape[0]
+        e = self._ensure_engine(B, f0.shape[1], np.asarray(x0["the_labels"]).shape[1])
+        rows = []
+
+        def feed():
+            for i in range(steps):
+                x = (first if i == 0 else next(generator))[0]
+                ins, n = self._pad_batch(self._split_inputs(x), B)
+                rows.append(n)
+                lab = np.asarray(x["the_labels"], np.float64)
+                il, ll = np.asarray(x["input_length"]).reshape(-1), np.asarray(x["label_length"]).reshape(-1)
+                if n < B:       # (padded rows: no labels, one frame)
+                    lab = np.concatenate([lab, -np.ones((B - n, lab.shape[1]))], axis=0)
+                    il, ll = np.concatenate([il, np.ones(B - n, il.dtype)]), np.concatenate([ll, np.zeros(B - n, ll.dtype)])
+                yield ins, lab, il, ll
+
+        per = [[], [], [], []]
+        means = []
+        for i, r in enumerate(e.predict_stream(feed(), output="score", train_phase=bool(learning_phase()), decode=decode,
+                                               threshold=threshold, ignore=ignore, costs=costs, **decode_kwargs)):
+            n = rows[i]
+            for k in range(4):
+                per[k].append(r[k][:n])
+            means.append(float(np.mean(r[0][:n])))
+        loss, dist, counts, lens = (np.concatenate(p, axis=0) for p in per)
+        v = float(np.mean(means))
+        tot = np.concatenate([counts.astype(np.int64).sum(axis=0), lens.astype(np.int64).sum(axis=0)])
+        if self.comm is not None and self.world > 1:
+            v = self.comm.allreduce_sum_scalar(v) / self.world
+            # (the communicator sums float32: 12-bit limbs keep every partial sum below 2^24, so the integer totals are exact)
+            tot = np.asarray([sum(int(round(self.comm.allreduce_sum_scalar(float((int(t) >> sh) & (0xFFF if sh < 24 else -1))))) << sh
+                                  for sh in (0, 12, 24)) for t in tot], np.int64)
+        out = score_from_counts(tot[None, :4], tot[None, 4:])
+        out["loss"] = v
+        out["per_sample"] = {"loss": loss, "dist": dist, "counts": counts, "lens": lens}
+        return out
 
 
 def model_from_json(text, device=0):

@@ -3,7 +3,7 @@ the reference's confidence threshold is commented out, so none applies - over th
 MLF writer with the ten-file ignore list."""
 import numpy as np
 
-from ..decoding import confidence_filter_collapse, decode_beam_mlf, greedy_segments, write_mlf
+from ..decoding import HTK_COSTS, confidence_filter_collapse, decode_beam_mlf, decode_score_map, greedy_segments, write_mlf
 from ..keras_like import Model
 from ..multimodal_fusion.sequence_decoding import ignore_list, map_gest  # noqa: F401  (the same 22 names and ignore list)
 from .cnn_lstm import load_model as _load_model
@@ -49,3 +49,9 @@ def decode_beam(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, bea
     f_list = [int(str(f)[6:11]) if not isinstance(f, (int, np.integer)) else int(f) for f in f_list]
     return decode_beam_mlf(pred_out, f_list, map_gest, ignore_list, "Sample%05d", out_file, top_paths=top_paths, lm=lm, lm_end=lm_end,
                            alpha=alpha, beta=beta, beam_width=beam_width)
+
+
+def decode_score(hyp_ids, ref_ids, costs=HTK_COSTS, confusion=True):
+    """HResults-style counts (H, S, D, I, corr, acc, confusion matrix) of decoded label ids against reference label ids on the device,
+    "sil" dropped from both (decoding.decode_score_map with this module's class map)."""
+    return decode_score_map(hyp_ids, ref_ids, map_gest, costs=costs, confusion=confusion)
