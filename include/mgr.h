@@ -475,7 +475,10 @@ int mgr_head_fwd_bwd(mgr_ctx* ctx, const float* A, int lda, const float* dmask, 
  * reference.  loss[B] = -log p(l|x).  dLogits[B,T,C] (may be NULL) = gscale * dloss_b/d(Dense logits),
  * zero on dropped / out-of-length frames.  Edge cases: label_len 0 is accepted (the single state is the blank, as in
  * tf.nn.ctc_loss); a label sequence that does not fit its input length (tf.nn.ctc_loss raises "Not enough time for target
- * transition sequence") yields loss = +inf and a ZERO gradient for that sample, the other samples of the batch are unaffected. */
+ * transition sequence") yields loss = +inf and a ZERO gradient for that sample, the other samples of the batch are unaffected.
+ * Out-of-range arguments are clipped, not rejected: input_len into [0, T - skip], label_len into [0, Lmax], label values into
+ * [0, C - 1]; the results are those of the call with the clipped arguments, bit for bit.  input_len 0 (no frames) yields loss = +inf
+ * and a zero gradient as well. */
 size_t mgr_ctc_ws_bytes(int B, int T, int C, int Lmax);
 int mgr_ctc_loss_grad(mgr_ctx* ctx, const float* P, const int32_t* labels, const int32_t* input_len,
                       const int32_t* label_len, int B, int T, int C, int Lmax, int skip, int blank, float eps,

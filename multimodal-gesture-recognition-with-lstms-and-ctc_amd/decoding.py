@@ -194,8 +194,9 @@ def forced_align(pred_out, labels, label_length=None, input_length=None, skip=2,
     return (segs, logp, path) if return_path else (segs, logp)
 
 
-def beam_search_decode(pred_out, input_length=None, beam_width=10, skip=2, merge_repeated=True, dev=None):
-    """K.ctc_decode(greedy=False, beam_width) equivalent on the GPU (BASELINE.json config 5)."""
+def beam_search_decode(pred_out, input_length=None, beam_width=10, skip=2, merge_repeated=True, dev=None, blank=None):
+    """K.ctc_decode(greedy=False, beam_width) equivalent on the GPU (BASELINE.json config 5).  blank: the blank's class, the last
+    one (Keras') by default."""
     dev = dev or default_device()
     P = np.ascontiguousarray(pred_out, dtype=np.float32)
     N, T, Cn = P.shape
@@ -207,7 +208,7 @@ def beam_search_decode(pred_out, input_length=None, beam_width=10, skip=2, merge
     olen = dev.empty((N,), np.int32)
     logp = dev.empty((N,), np.float64)
     ws = dev.bytes(dev.lib.mgr_ctc_beam_ws_bytes(N, T, Cn, beam_width))
-    dev.call("mgr_ctc_beam_search", dP, dil, N, T, Cn, skip, Cn - 1, int(beam_width), C.c_float(1e-8),
+    dev.call("mgr_ctc_beam_search", dP, dil, N, T, Cn, skip, Cn - 1 if blank is None else int(blank), int(beam_width), C.c_float(1e-8),
              1 if merge_repeated else 0, out, olen, logp, ws, ws.nbytes)
     o, l, s = out.download(), olen.download(), logp.download()
     for a in (dP, dil, out, olen, logp, ws):

@@ -75,6 +75,43 @@ def test_beam_search_golden_and_random(device):
         assert np.allclose(gs, rs, rtol=1e-12)
 
 
+@pytest.mark.parametrize("merge_repeated", [True, False])
+@pytest.mark.parametrize("N,T,Cn,W", [(2, 30, 44, 32), (2, 24, 64, 20)])
+def test_beam_search_with_more_than_12_candidates_per_lane(device, N, T, Cn, W, merge_repeated):
+    """beam * (C + 1) > 768: the 34-candidates-per-lane form of the kernel (the one that spills to scratch).  44 classes at the beam
+    limit of 32, and the class limit of 64, where the merge mask of a beam uses its bits up to 62 (bit 63 is the blank's with the
+    reference's blank = C - 1: test_beam_search_merge_mask_bit_63 moves the blank)."""
+    from mgr_amd import decoding
+    assert W * (Cn + 1) > 768
+    rng = np.random.default_rng(N * 100 + Cn + W)
+    P = rng.random((N, T, Cn)) ** 6
+    P = (P / P.sum(-1, keepdims=True)).astype(np.float32)
+    il = np.full(N, T - 2)
+    il[0] = (T - 2) // 2
+    ref, rs = kr.ctc_beam_search(P, il, beam_width=W, merge_repeated=merge_repeated)
+    got, gs = decoding.beam_search_decode(P, il, beam_width=W, merge_repeated=merge_repeated, dev=device)
+    assert got == ref, (N, T, Cn, W)
+    assert np.allclose(gs, rs, rtol=1e-12)
+
+
+@pytest.mark.parametrize("merge_repeated", [True, False])
+def test_beam_search_merge_mask_bit_63(device, merge_repeated):
+    """64 classes with blank = 0: class 63 is a label, and an extension by it that lands on a live beam sets bit 63 of the merge
+    mask.  Few classes carry the mass, 63 among them, so such merges happen at nearly every step."""
+    from mgr_amd import decoding
+    N, T, Cn, W, skip, blank = 2, 24, 64, 20, 2, 0
+    rng = np.random.default_rng(63)
+    P = rng.random((N, T, Cn)) ** 6 * 1e-3
+    P[:, :, [0, 5, 63]] = rng.random((N, T, 3)) + 0.2
+    P = (P / P.sum(-1, keepdims=True)).astype(np.float32)
+    il = np.array([T - skip, T - skip - 3])
+    ref, rs = kr.ctc_beam_search(P, il, beam_width=W, skip=skip, blank=blank, merge_repeated=merge_repeated)
+    assert any(63 in r for r in ref)
+    got, gs = decoding.beam_search_decode(P, il, beam_width=W, skip=skip, merge_repeated=merge_repeated, dev=device, blank=blank)
+    assert got == ref
+    assert np.allclose(gs, rs, rtol=1e-12)
+
+
 def test_beam_search_prefix_reentering_the_beam(device):
     """Few classes and a narrow beam: a prefix p drops out of the beam while p+c stays, and p is found again later.  The
     extension p -> p+c must then still merge into the live beam p+c (the kernel keys trie nodes by (parent, label) so a

@@ -853,3 +853,48 @@ def test_head_fwd_bwd_matches_the_oracle(device, B, T, D, Cn, Lmax, p):
     assert rel_err(got["dL"], ref_dz / B) < 5e-4
     for name, a, b in (("dA", got["gA"], dAref), ("dWd", got["gW"], dWref), ("dbd", got["gb"], dbref)):
         assert rel_err(a, b) < 5e-4, (name, rel_err(a, b))     # (the bound of the CTC gradient they are products of)
+
+
+def test_head_fwd_bwd_at_two_pairs_per_lane_equals_its_parts(device):
+    """mgr_head_fwd_bwd at Lmax = 70 (the CTC recursions hold two (blank, label) pairs per lane; one sample has all 70 labels, its
+    states cross the lane boundaries): the bounds of test_head_fwd_bwd_matches_the_oracle against the fp64 oracle, and the header's
+    promise - bit for bit the results of mgr_dense_softmax_fwd followed by mgr_ctc_loss_grad with the same arguments."""
+    dev = device
+    B, T, D, Cn, Lmax = 3, 150, 64, 22, 70
+    rng = np.random.default_rng(B * 7 + D + Lmax)
+    A = rng.standard_normal((B, T, D)).astype(np.float32)
+    Wd = (rng.standard_normal((D, Cn)) * (2.0 / np.sqrt(D))).astype(np.float32)
+    bd = (rng.standard_normal(Cn) * 0.1).astype(np.float32)
+    skip, eps, blank = 2, 1e-8, Cn - 1
+    ll = np.array([70, 33, 5])
+    labels = -np.ones((B, Lmax), np.int64)
+    for b in range(B):
+        labels[b, :ll[b]] = rng.integers(0, Cn - 1, size=ll[b])
+    il = np.array([T - skip, T - skip - 1, 40])
+    dA_, dW_, db_ = dev.array(A), dev.array(Wd), dev.array(bd)
+    dlab, dil, dll = dev.array(labels.astype(np.int32)), dev.array(il.astype(np.int32)), dev.array(ll.astype(np.int32))
+    f = dict(P=dev.empty((B, T, Cn)), loss=dev.empty((B,)), mean=dev.empty((4,)), dL=dev.empty((B, T, Cn)),
+             gW=dev.empty((D, Cn)), gb=dev.empty((Cn,)), gA=dev.empty((B, T, D)))
+    ws = dev.bytes(dev.lib.mgr_head_ws_bytes(B, T, D, Cn, Lmax))
+    dev.call("mgr_head_fwd_bwd", dA_, D, 0, 0.0, C.c_uint64(0), dW_, db_, dlab, dil, dll, B, T, D, Cn, Lmax, skip, blank, eps,
+             1.0 / B, f["P"], f["loss"], f["mean"], f["dL"], f["gW"], f["gb"], f["gA"], D, ws, ws.nbytes)
+    got = {k: v.download() for k, v in f.items()}
+    Pref, cache = kr.dense_softmax_forward(A.astype(np.float64), None, Wd.astype(np.float64), bd.astype(np.float64))
+    ref_loss, ref_dz = kr.ctc_loss_grad(Pref, labels, il, ll, skip=skip, eps=eps)
+    dAref, dWref, dbref = kr.dense_backward(ref_dz / B, cache)
+    assert np.isfinite(ref_loss).all()
+    assert rel_err(got["P"], Pref) < 1e-5
+    assert np.allclose(got["loss"], ref_loss, rtol=1e-4), np.abs(got["loss"] / ref_loss - 1).max()
+    assert abs(got["mean"][0] / ref_loss.mean() - 1) < 1e-4
+    assert rel_err(got["dL"], ref_dz / B) < 5e-4
+    for name, a, b in (("dA", got["gA"], dAref), ("dWd", got["gW"], dWref), ("dbd", got["gb"], dbref)):
+        assert rel_err(a, b) < 5e-4, (name, rel_err(a, b))
+    # the parts, on their own buffers
+    P2, loss2, dL2 = dev.empty((B, T, Cn)), dev.empty((B,)), dev.empty((B, T, Cn))
+    ws2 = dev.bytes(dev.lib.mgr_ctc_ws_bytes(B, T, Cn, Lmax))
+    dev.call("mgr_dense_softmax_fwd", dA_, D, 0, 0.0, C.c_uint64(0), dW_, db_, P2, B, T, D, Cn)
+    dev.call("mgr_ctc_loss_grad", P2, dlab, dil, dll, B, T, Cn, Lmax, skip, blank, eps, 1.0 / B, loss2, dL2, ws2, ws2.nbytes)
+    for name, a, b in (("P", got["P"], P2.download()), ("loss", got["loss"], loss2.download()), ("dLogits", got["dL"], dL2.download())):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), name
+    for a in (dA_, dW_, db_, dlab, dil, dll, ws, P2, loss2, dL2, ws2) + tuple(f.values()):
+        a.free()
