@@ -418,12 +418,13 @@ constexpr size_t kLdsMax = 160 * 1024;
 
 extern "C" {
 
-size_t mgr_ctc_align_ws_bytes(int B, int T, int C, int Lmax) {
-  const size_t To = (size_t)(T > 0 ? T : 1);   // sized with T (>= T - skip) to keep the query simple
-  const size_t e = mgr_align_up((size_t)B * C * align_ts((int)To) * sizeof(float), 256);
-  const size_t bp = mgr_align_up((size_t)B * align_nb((int)To) * (Lmax + 1) * sizeof(uint32_t), 256);
-  return e + bp;
+// emissions | back-pointer words; laid out for T frames (the kernels use rows of T - skip: both fit) to keep the query simple
+struct AlignWs { float* E; uint32_t* BPg; size_t bytes; };
+static AlignWs align_ws_layout(void* ws, int B, int T, int C, int Lmax) {
+  mgr_ws_carver w(ws);
+  return {w.take<float>((size_t)B * C * align_ts(T)), w.take<uint32_t>((size_t)B * align_nb(T) * (Lmax + 1)), w.off};
 }
+size_t mgr_ctc_align_ws_bytes(int B, int T, int C, int Lmax) { return align_ws_layout(nullptr, B, T > 0 ? T : 1, C, Lmax).bytes; }
 
 int mgr_ctc_align(mgr_ctx* c, const float* P, const int32_t* labels, const int32_t* input_len, const int32_t* label_len, int B, int T, int C,
                   int Lmax, int skip, int blank, float eps, int32_t* path, int32_t* seg, float* conf, double* logp, void* ws, size_t ws_bytes) {
@@ -434,15 +435,12 @@ int mgr_ctc_align(mgr_ctx* c, const float* P, const int32_t* labels, const int32
   MGR_REQUIRE(Lmax + 1 <= 256, "Lmax %d too large (max 255)", Lmax);
   MGR_REQUIRE(ws && ws_bytes >= mgr_ctc_align_ws_bytes(B, T, C, Lmax), "workspace too small");
   const int To = T - skip, NP = Lmax + 1;
-  // (the workspace is laid out for T frames, the kernels use rows of T - skip: both fit)
-  const size_t e = mgr_align_up((size_t)B * C * align_ts(T) * sizeof(float), 256);
-  float* E = reinterpret_cast<float*>(ws);
-  uint32_t* BPg = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws) + e);
+  const AlignWs L = align_ws_layout(ws, B, T, C, Lmax);
   const size_t lds_small = ((size_t)3 * NP + align_state_words(To)) * sizeof(int);
   const size_t lds_full = lds_small + (size_t)align_nb(To) * NP * sizeof(uint32_t);
   const bool in_lds = lds_full <= kLdsMax;
   MGR_REQUIRE(lds_small <= kLdsMax, "T - skip = %d too large for the LDS frame states", To);
-  if (!(c->attr_done & 512u)) {
+  if (!(c->attr_done & MGR_ATTR_ALIGN)) {
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_align<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_align<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_align<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
@@ -451,20 +449,20 @@ int mgr_ctc_align(mgr_ctx* c, const float* P, const int32_t* labels, const int32
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_align<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_align<3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_align<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
-    c->attr_done |= 512u;
+    c->attr_done |= MGR_ATTR_ALIGN;
   }
   const int ppl = (NP + 63) / 64;
   hipStream_t s = mgr_stream(c);
   mgr_prof_begin(c, MGR_K_CTC);
-  hipLaunchKernelGGL(k_align_emissions, dim3((unsigned)((align_ts(To) + 255) / 256), B), dim3(256), 0, s, P, input_len, T, C, skip, eps, E);
+  hipLaunchKernelGGL(k_align_emissions, dim3((unsigned)((align_ts(To) + 255) / 256), B), dim3(256), 0, s, P, input_len, T, C, skip, eps, L.E);
 #define MGR_ALIGN_LAUNCH(N)                                                                                                                \
   do {                                                                                                                                     \
     if (in_lds)                                                                                                                            \
       hipLaunchKernelGGL((k_ctc_align<N, true>), dim3(B), dim3(64), lds_full, s, P, labels, input_len, label_len, T, C, Lmax, skip, blank, \
-                         E, BPg, path, seg, conf, logp);                                                                                   \
+                         L.E, L.BPg, path, seg, conf, logp);                                                                               \
     else                                                                                                                                   \
       hipLaunchKernelGGL((k_ctc_align<N, false>), dim3(B), dim3(64), lds_small, s, P, labels, input_len, label_len, T, C, Lmax, skip,      \
-                         blank, E, BPg, path, seg, conf, logp);                                                                            \
+                         blank, L.E, L.BPg, path, seg, conf, logp);                                                                        \
   } while (0)
   switch (ppl) {
     case 1: MGR_ALIGN_LAUNCH(1); break;
@@ -485,9 +483,9 @@ int mgr_greedy_segments(mgr_ctx* c, const float* P, int B, int T, int C, int ski
   MGR_REQUIRE(T - skip <= MGR_SEGMENTS_MAX_FRAMES && C <= 1024, "T - skip = %d (max %d) or C = %d (max 1024) too large for the LDS frame arrays",
               T - skip, MGR_SEGMENTS_MAX_FRAMES, C);
   const size_t lds = ((size_t)4 * (T - skip) + 2 * (size_t)C + 256) * sizeof(int);
-  if (!(c->attr_done & 1024u)) {
+  if (!(c->attr_done & MGR_ATTR_SEGMENTS)) {
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_greedy_segments), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
-    c->attr_done |= 1024u;
+    c->attr_done |= MGR_ATTR_SEGMENTS;
   }
   mgr_prof_begin(c, MGR_K_MISC);
   hipLaunchKernelGGL(k_greedy_segments, dim3(B), dim3(256), lds, mgr_stream(c), P, T, C, skip, thr, cap, n_runs, lab, seg, conf);

@@ -250,16 +250,9 @@ __global__ __launch_bounds__(64) void k_beam(const float* __restrict__ P, const 
 
 extern "C" {
 
-static int beam_table_bits(size_t nodes) {
-  int bits = 6;
-  while (((size_t)1 << bits) < 2 * nodes) ++bits;
-  return bits;
-}
-
 size_t mgr_ctc_beam_ws_bytes(int B, int T, int C, int beam) {
   (void)C;
-  size_t nodes = (size_t)T * (beam > 0 ? beam : 1) + 2;
-  return mgr_align_up((size_t)B * nodes * sizeof(int32_t), 256) * 2 + ((size_t)B << beam_table_bits(nodes)) * sizeof(unsigned long long);
+  return mgr_beam_ws_layout(nullptr, B, (size_t)T * (beam > 0 ? beam : 1) + 2).bytes;
 }
 
 int mgr_ctc_beam_search(mgr_ctx* c, const float* P, const int32_t* input_len, int B, int T, int C, int skip, int blank,
@@ -274,15 +267,12 @@ int mgr_ctc_beam_search(mgr_ctx* c, const float* P, const int32_t* input_len, in
   MGR_REQUIRE(ws && ws_bytes >= mgr_ctc_beam_ws_bytes(B, T, C, beam), "workspace too small");
   int nodes = T * beam + 2;
   MGR_REQUIRE((size_t)nodes < ((size_t)1 << 25), "T*beam too large for the prefix table");
-  int32_t* parent = reinterpret_cast<int32_t*>(ws);
-  int32_t* label = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ws) + mgr_align_up((size_t)B * nodes * sizeof(int32_t), 256));
-  unsigned long long* table =
-      reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + 2 * mgr_align_up((size_t)B * nodes * sizeof(int32_t), 256));
+  const mgr_beam_ws L = mgr_beam_ws_layout(ws, B, (size_t)nodes);
   mgr_prof_begin(c, MGR_K_MISC);
   const int per_lane = (beam * (C + 1) + 63) / 64;
 #define MGR_BEAM_LAUNCH(KM)                                                                                        \
   hipLaunchKernelGGL(k_beam<KM>, dim3(B), dim3(64), 0, mgr_stream(c), P, input_len, B, T, C, skip, blank, beam, eps, \
-                     merge_repeated, out, out_len, logp, parent, label, nodes, table, beam_table_bits(nodes))
+                     merge_repeated, out, out_len, logp, L.parent, L.label, nodes, L.table, L.bits)
   if (per_lane <= 4)
     MGR_BEAM_LAUNCH(4);
   else if (per_lane <= 12)

@@ -295,18 +295,13 @@ int mgr_ctc_beam_search_lm(mgr_ctx* c, const float* P, const int32_t* input_len,
   MGR_REQUIRE(ws && ws_bytes >= mgr_ctc_beam_lm_ws_bytes(B, T, C, beam, top_paths), "workspace too small");
   int nodes = T * beam + 2;
   MGR_REQUIRE((size_t)nodes < ((size_t)1 << 25), "T*beam too large for the prefix table");
-  int bits = 6;   // as mgr_ctc_beam_ws_bytes sizes the table: the first power of two >= 2 * nodes
-  while (((size_t)1 << bits) < 2 * (size_t)nodes) ++bits;
-  const size_t plane = mgr_align_up((size_t)B * nodes * sizeof(int32_t), 256);
-  int32_t* parent = reinterpret_cast<int32_t*>(ws);
-  int32_t* label = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ws) + plane);
-  unsigned long long* table = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + 2 * plane);
+  const mgr_beam_ws L = mgr_beam_ws_layout(ws, B, (size_t)nodes);   // (the workspace of mgr_ctc_beam_search)
   const size_t lds = (size_t)(C + 1) * C * sizeof(double);
   mgr_prof_begin(c, MGR_K_MISC);
   const int per_lane = (beam * (C + 1) + 63) / 64;
 #define MGR_BEAM_LM_LAUNCH(KM)                                                                                                  \
   hipLaunchKernelGGL(k_beam_lm<KM>, dim3(B), dim3(64), lds, mgr_stream(c), P, input_len, T, C, skip, blank, beam, eps, ext, fin, \
-                     top_paths, out, out_len, score, logp_ctc, parent, label, nodes, table, bits)
+                     top_paths, out, out_len, score, logp_ctc, L.parent, L.label, nodes, L.table, L.bits)
   if (per_lane <= 4)
     MGR_BEAM_LM_LAUNCH(4);
   else if (per_lane <= 12)

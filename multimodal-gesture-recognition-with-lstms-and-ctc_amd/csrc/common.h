@@ -7,11 +7,19 @@
 #include <string.h>
 
 #include "../../include/mgr.h"
+#include "ws_layout.h"
 
 constexpr int MGR_MAX_PERSIST = 8;
 constexpr int MGR_MAX_FROZEN = 32;
 
 constexpr size_t MGR_SMALL_D2H = 4096;
+
+// bits of mgr_ctx::attr_done: one per kernel family whose function attributes (dynamic LDS limit) are set once per context
+enum : unsigned {
+  MGR_ATTR_SCAN_CLUSTER = 1u, MGR_ATTR_SCAN_CLUSTER_BWD = 2u, MGR_ATTR_SCAN_CLUSTER_FUSED = 64u,   // lstm_cluster.hip, lstm_cluster_bwd.hip
+  MGR_ATTR_PROJ_SPLIT = 16u, MGR_ATTR_DW_SPLIT = 32u, MGR_ATTR_PROJ_NARROW = 2048u,                // gemm_split.hip (two), gemm.hip
+  MGR_ATTR_CTC = 128u, MGR_ATTR_ALIGN = 512u, MGR_ATTR_SEGMENTS = 1024u, MGR_ATTR_ROI = 256u,      // ctc.hip, align.hip (two), roi.hip
+};
 
 struct mgr_ctx {
   int device;
@@ -48,7 +56,7 @@ struct mgr_ctx {
   Persist persist[MGR_MAX_PERSIST];
   unsigned persist_seq;     // sequence number of the last persistent launch of this context
   int persist_serialised;   // launches that had to be ordered behind another stream's persistent launch
-  unsigned attr_done;       // bit k: function attributes of kernel family k have been set on this context's device
+  unsigned attr_done;       // MGR_ATTR_* bits: function attributes of that kernel family have been set on this context's device
   // split weight planes of FROZEN weights (gemm_split.hip, mgr_weight_planes_cache): weights the caller promised not to rewrite, and
   // the workspaces that hold their planes as of that promise.  Key (Wp, ws, B, F, H): B and F place the planes inside ws, F and H
   // size them; [region, region + region_bytes) are the bytes of ws the entry relies on (the largest-|W| word block and the planes)
@@ -100,6 +108,8 @@ int mgr_prof_begin(mgr_ctx* c, int family);
 int mgr_prof_end(mgr_ctx* c, int family);
 
 static inline size_t mgr_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// 1-D grid of 256-thread workgroups over n elements (grid-stride kernels), at most cap of them
+static inline int mgr_grid256(size_t n, size_t cap) { return (int)((n + 255) / 256 < cap ? (n + 255) / 256 : cap); }
 
 // ---- device-side RNG: one 64-bit mix per element index (splitmix64 finaliser); stateless ---------------
 __host__ __device__ static inline uint64_t mgr_mix64(uint64_t z) {

@@ -478,12 +478,14 @@ __global__ __launch_bounds__(256) void k_ctc_grad(const float* __restrict__ P, c
 
 extern "C" {
 
-size_t mgr_ctc_ws_bytes(int B, int T, int C, int Lmax) {
-  size_t To = (size_t)(T > 0 ? T : 1);
-  size_t ly = mgr_align_up((size_t)B * 2 * C * ctc_ts((int)To) * sizeof(float), 256);   // class-major emissions, forward + reversed
-  size_t ab = mgr_align_up((size_t)B * (To + 1) * 2 * (Lmax + 1) * sizeof(float), 256);
-  return ly + 2 * ab;
+// class-major emissions (forward + reversed) | alpha | beta; sized with T (>= T - skip) to keep the query simple
+struct CtcWs { float *LY, *AL, *BE; size_t bytes; };
+static CtcWs ctc_ws_layout(void* ws, int B, size_t To, int C, int Lmax) {
+  mgr_ws_carver w(ws);
+  const size_t ab = (size_t)B * (To + 1) * 2 * (Lmax + 1);
+  return {w.take<float>((size_t)B * 2 * C * ctc_ts((int)To)), w.take<float>(ab), w.take<float>(ab), w.off};
 }
+size_t mgr_ctc_ws_bytes(int B, int T, int C, int Lmax) { return ctc_ws_layout(nullptr, B, (size_t)(T > 0 ? T : 1), C, Lmax).bytes; }
 
 int mgr_ctc_loss_grad(mgr_ctx* c, const float* P, const int32_t* labels, const int32_t* input_len,
                       const int32_t* label_len, int B, int T, int C, int Lmax, int skip, int blank, float eps,
@@ -494,12 +496,9 @@ int mgr_ctc_loss_grad(mgr_ctx* c, const float* P, const int32_t* labels, const i
   MGR_REQUIRE(blank >= 0 && blank < C, "blank %d out of range", blank);
   MGR_REQUIRE(Lmax + 1 <= 256, "Lmax %d too large (max 255)", Lmax);
   MGR_REQUIRE(ws && ws_bytes >= mgr_ctc_ws_bytes(B, T, C, Lmax), "workspace too small");
-  size_t To = (size_t)T;  // sized with T (>= T-skip) to keep the query simple
-  size_t ly = mgr_align_up((size_t)B * 2 * C * ctc_ts((int)To) * sizeof(float), 256);
-  size_t ab = mgr_align_up((size_t)B * (To + 1) * 2 * (Lmax + 1) * sizeof(float), 256);
-  float* LY = reinterpret_cast<float*>(ws);
-  float* AL = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + ly);
-  float* BE = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + ly + ab);
+  const size_t To = (size_t)T;
+  const CtcWs L = ctc_ws_layout(ws, B, To, C, Lmax);
+  float *LY = L.LY, *AL = L.AL, *BE = L.BE;
   // two samples per workgroup (one chain per SIMD) from B = 2 on; MGR_TUNE_CTC_ONE_SAMPLE = 1: one sample per workgroup (rounds 1 - 5)
   const int spw = (B >= 2 && c->tune[MGR_TUNE_CTC_ONE_SAMPLE] == 0) ? 2 : 1;
   size_t lds_grad = (size_t)256 * (C + 1) * sizeof(float) + (size_t)(Lmax + 1) * sizeof(int);
@@ -514,7 +513,7 @@ int mgr_ctc_loss_grad(mgr_ctx* c, const float* P, const int32_t* labels, const i
     if (lds_grad < (size_t)frame_kib * 1024) lds_grad = (size_t)frame_kib * 1024;
     lds_emis = (size_t)frame_kib * 1024;
   }
-  if (!(c->attr_done & 128u)) {
+  if (!(c->attr_done & MGR_ATTR_CTC)) {
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_emissions), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_grad), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_chains<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -525,7 +524,7 @@ int mgr_ctc_loss_grad(mgr_ctx* c, const float* P, const int32_t* labels, const i
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_chains<3, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_chains<4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_chains<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    c->attr_done |= 128u;
+    c->attr_done |= MGR_ATTR_CTC;
   }
   int npairs = Lmax + 1;
   int ppl = (npairs + 63) / 64;

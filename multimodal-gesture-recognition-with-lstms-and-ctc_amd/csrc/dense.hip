@@ -414,11 +414,14 @@ int mgr_dense_softmax_fwd(mgr_ctx* c, const float* A, int lda, const float* dmas
   return 0;
 }
 
-size_t mgr_dense_bwd_ws_bytes(int B, int T, int D, int C) {
-  size_t nframes = (size_t)B * T;
-  int nwg = dense_bwd_wgs(nframes);
-  return mgr_align_up((size_t)nwg * D * C * sizeof(float), 256) + mgr_align_up((size_t)nwg * C * sizeof(float), 256);
+// one partial dWd / dbd slab per workgroup
+struct DenseBwdWs { float *slabW, *slabB; size_t bytes; };
+static DenseBwdWs dense_bwd_ws_layout(void* ws, int B, int T, int D, int C) {
+  const size_t nwg = (size_t)dense_bwd_wgs((size_t)B * T);
+  mgr_ws_carver w(ws);
+  return {w.take<float>(nwg * D * C), w.take<float>(nwg * C), w.off};
 }
+size_t mgr_dense_bwd_ws_bytes(int B, int T, int D, int C) { return dense_bwd_ws_layout(nullptr, B, T, D, C).bytes; }
 
 int mgr_dense_bwd(mgr_ctx* c, const float* A, int lda, const float* dmask, float p, uint64_t seed,
                   const float* dLogits, const float* Wd, float* dWd, float* dbd, float* dA, int ldda, int B, int T,
@@ -433,8 +436,8 @@ int mgr_dense_bwd(mgr_ctx* c, const float* A, int lda, const float* dmask, float
   int fpw = (int)((nframes + nwg - 1) / nwg);
   fpw = (fpw + FR - 1) / FR * FR;
   nwg = (int)((nframes + fpw - 1) / fpw);
-  float* slabW = reinterpret_cast<float*>(ws);
-  float* slabB = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + mgr_align_up((size_t)dense_bwd_wgs(nframes) * D * C * sizeof(float), 256));
+  const DenseBwdWs L = dense_bwd_ws_layout(ws, B, T, D, C);
+  float *slabW = L.slabW, *slabB = L.slabB;
   float inv_keep = 1.f / (1.f - p);
   mgr_prof_begin(c, MGR_K_DENSE_BWD);
   if (dense_mfma_ok(c, A, lda, ldda, D, C, nframes, 1024, 48)) {
@@ -460,9 +463,13 @@ int mgr_dense_bwd(mgr_ctx* c, const float* A, int lda, const float* dmask, float
   return 0;
 }
 
-size_t mgr_head_ws_bytes(int B, int T, int D, int C, int Lmax) {
-  return mgr_align_up(mgr_ctc_ws_bytes(B, T, C, Lmax), 256) + mgr_dense_bwd_ws_bytes(B, T, D, C);
+// the workspace of mgr_ctc_loss_grad, then that of mgr_dense_bwd
+struct HeadWs { char* ctc; size_t dense_off; char* dense; size_t bytes; };
+static HeadWs head_ws_layout(void* ws, int B, int T, int D, int C, int Lmax) {
+  mgr_ws_carver w(ws);
+  return {w.take<char>(mgr_ctc_ws_bytes(B, T, C, Lmax)), w.off, w.take<char>(mgr_dense_bwd_ws_bytes(B, T, D, C)), w.off};
 }
+size_t mgr_head_ws_bytes(int B, int T, int D, int C, int Lmax) { return head_ws_layout(nullptr, B, T, D, C, Lmax).bytes; }
 
 // The whole head of a training step in one call (reference multimodal_fusion/multimodal.py:171-179 + losses.py:4-15 and their
 // backward pass): Dropout -> Dense -> softmax (P is written: the predict path and the tests read it), CTC loss + dLogits, Dense
@@ -476,14 +483,14 @@ int mgr_head_fwd_bwd(mgr_ctx* c, const float* A, int lda, const float* dmask, fl
   mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   int r = mgr_dense_softmax_fwd(c, A, lda, dmask, p, seed, Wd, bd, P, B, T, D, C);
   if (r) return r;
-  const size_t wc = mgr_align_up(mgr_ctc_ws_bytes(B, T, C, Lmax), 256);
-  r = mgr_ctc_loss_grad(c, P, labels, input_len, label_len, B, T, C, Lmax, skip, blank, eps, gscale, loss, dLogits, ws, wc);
+  const HeadWs L = head_ws_layout(ws, B, T, D, C, Lmax);
+  r = mgr_ctc_loss_grad(c, P, labels, input_len, label_len, B, T, C, Lmax, skip, blank, eps, gscale, loss, dLogits, L.ctc, L.dense_off);
   if (r) return r;
   if (loss_mean) {
     r = mgr_mean(c, loss, B, loss_mean);
     if (r) return r;
   }
-  return mgr_dense_bwd(c, A, lda, dmask, p, seed, dLogits, Wd, dWd, dbd, dA, ldda, B, T, D, C, reinterpret_cast<char*>(ws) + wc, ws_bytes - wc);
+  return mgr_dense_bwd(c, A, lda, dmask, p, seed, dLogits, Wd, dWd, dbd, dA, ldda, B, T, D, C, L.dense, ws_bytes - L.dense_off);
 }
 
 }  // extern "C"

@@ -1607,11 +1607,17 @@ int mgr_lstm_input_proj_pair(mgr_ctx* c, const float* X, int ldx, const float* m
   return 0;
 }
 
-size_t mgr_lstm_input_proj_dropout_ws_bytes(int B, int F, int H) {
-  const size_t Fp = (size_t)(F + SP_SK - 1) / SP_SK * SP_SK;
-  return 2 * mgr_align_up((size_t)4 * B * Fp * sizeof(int), 256) + mgr_align_up((size_t)4 * B * sizeof(int), 256) + 256 +
-         mgr_align_up((size_t)F * 4 * H * sizeof(float), 256);   // (+256: the max |W| word of the split-f16 kernel)
+static size_t sp_fp(int F) { return (size_t)(F + SP_SK - 1) / SP_SK * SP_SK; }   // list rows: F padded to whole K stages
+
+// kept-feature lists (index, factor) [4B][Fp] | counts [4B] | words ([0] the max |W| of the split-f16 kernel, [1] its gate) |
+// gate-major weights [F][4H]
+struct ProjDropWs { int* kidx; float* kval; int* kcnt; unsigned* wmax; float* Wg; size_t bytes; };
+static ProjDropWs proj_dropout_ws_layout(void* ws, int B, int F, int H) {
+  mgr_ws_carver w(ws);
+  const size_t nl = (size_t)4 * B * sp_fp(F);
+  return {w.take<int>(nl), w.take<float>(nl), w.take<int>((size_t)4 * B), w.take<unsigned>(64), w.take<float>((size_t)F * 4 * H), w.off};
 }
+size_t mgr_lstm_input_proj_dropout_ws_bytes(int B, int F, int H) { return proj_dropout_ws_layout(nullptr, B, F, H).bytes; }
 
 static bool sparse_proj_shape(const mgr_ctx* c, float drop_rate, int F) {
   // the per-gate K loops pay when enough features are dropped; at small F (depth-1 layers, F = 39 / 20) the GEMM is bound
@@ -1627,14 +1633,11 @@ int mgr_lstm_input_proj_dropout_wants_transposed(mgr_ctx* c, float drop_rate, in
 static int input_proj_dropout_impl(mgr_ctx* c, const float* X, int ldx, bool transposed, const float* mask4, float drop_rate,
                                    const float* Wp, const float* bp, float* Z, int B, int T, int F, int H, void* ws, size_t ws_bytes,
                                    float x_absmax = 0.f) {
-  const int Fp = (F + SP_SK - 1) / SP_SK * SP_SK;
-  const size_t lbytes = mgr_align_up((size_t)4 * B * Fp * sizeof(int), 256);
-  char* w = reinterpret_cast<char*>(ws);
-  int* kidx = reinterpret_cast<int*>(w);
-  float* kval = reinterpret_cast<float*>(w + lbytes);
-  int* kcnt = reinterpret_cast<int*>(w + 2 * lbytes);
-  unsigned* wmax = reinterpret_cast<unsigned*>(w + 2 * lbytes + mgr_align_up((size_t)4 * B * sizeof(int), 256));
-  float* Wg = reinterpret_cast<float*>(w + 2 * lbytes + mgr_align_up((size_t)4 * B * sizeof(int), 256) + 256);
+  const int Fp = (int)sp_fp(F);
+  const ProjDropWs L = proj_dropout_ws_layout(ws, B, F, H);
+  int *kidx = L.kidx, *kcnt = L.kcnt;
+  float *kval = L.kval, *Wg = L.Wg;
+  unsigned* wmax = L.wmax;
   hipStream_t s = mgr_stream(c);
   // x_absmax > 0: a bound the CALLER states - checked on the device (k_absmax_gate), f32 kernel if violated; < 0: |x_absmax| is a bound
   // the PRODUCER of XT guarantees (mgr.h): no check
@@ -1654,9 +1657,9 @@ static int input_proj_dropout_impl(mgr_ctx* c, const float* X, int ldx, bool tra
   // MFMA stage is 16 list positions), F > 64 (a mask row is one ballot, the X tile and the weight slice fit LDS twice per CU up to
   // F = 40 and once up to 64), and MGR_TUNE_PROJ_WIDE_TILES = 2, which keeps selecting the generic kernel for tests and A/Bs.
   if (!transposed && mask4 && F >= 16 && F <= NP_MAXF && c->tune[MGR_TUNE_PROJ_WIDE_TILES] != 2) {
-    if (!(c->attr_done & 2048u)) {
+    if (!(c->attr_done & MGR_ATTR_PROJ_NARROW)) {
       MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_narrow<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)np_lds_bytes(NP_MAXF)));
-      c->attr_done |= 2048u;
+      c->attr_done |= MGR_ATTR_PROJ_NARROW;
     }
     const int nchunk = ((T + SP_TM - 1) / SP_TM + NP_RPW - 1) / NP_RPW;
     const int nwg = ((H + NP_TU - 1) / NP_TU) * ((nchunk * B + 7) / 8) * 8;
@@ -1678,7 +1681,7 @@ static int input_proj_dropout_impl(mgr_ctx* c, const float* X, int ldx, bool tra
     MGR_HIP(hipMemsetAsync(wmax, 0, sizeof(unsigned), s));
   {
     const size_t n = (size_t)F * H;
-    const int wgs = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    const int wgs = mgr_grid256(n, 2048);
     hipLaunchKernelGGL(k_gate_major, dim3(wgs), dim3(256), 0, s, Wp, Wg, F, H, wmax);
   }
   // 128-unit tiles (MGR_TUNE_PROJ_WIDE_TILES = 2) are faster alone (audio L2 2.77 against 3.03 ms) but slower in the training step
@@ -1694,7 +1697,7 @@ static int input_proj_dropout_impl(mgr_ctx* c, const float* X, int ldx, bool tra
     if (gate) {   // what |X| the f16 range holds at this scale: beyond it the split would carry Inf (ldx is the padded row length)
       MGR_HIP(hipMemsetAsync(gate, 0, sizeof(unsigned), s));
       const size_t n4 = (size_t)B * F * ldx / 4;
-      hipLaunchKernelGGL(k_absmax_gate, dim3((int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096)), dim3(256), 0, s, X, n4, 65000.f / sx, gate);
+      hipLaunchKernelGGL(k_absmax_gate, dim3(mgr_grid256(n4, 4096)), dim3(256), 0, s, X, n4, 65000.f / sx, gate);
     }
     if (dense)
       hipLaunchKernelGGL(k_gemm_nn_dense16, dim3(ntiles), dim3(256), 0, s, X, ldx, mask4, Wg, bp, Z, B, T, F, H, wmax,
@@ -1783,25 +1786,23 @@ int mgr_transpose_bt(mgr_ctx* c, const float* X, int ldx, float* XT, int ldt, in
   return 0;
 }
 
-size_t mgr_lstm_param_grads_ws_bytes(int B, int T, int F, int H) {
-  int N = 4 * H;
-  size_t a = mgr_align_up((size_t)tn_groups(B, F, N) * F * N * sizeof(float), 256);
-  size_t b = mgr_align_up((size_t)tn_groups(B, H, N) * H * N * sizeof(float), 256);
-  size_t d = mgr_align_up((size_t)colsum_wgs((size_t)B * T) * N * sizeof(float), 256);
-  return a + b + d;
+// partial dW slabs [sgW][F][4H] | partial dU slabs [sgU][H][4H] | partial column sums of dZ
+struct PgWs { float *slabW, *slabU, *slabB; size_t bytes; };
+static PgWs pg_ws_layout(void* ws, int B, int T, int F, int H) {
+  const int N = 4 * H;
+  mgr_ws_carver w(ws);
+  return {w.take<float>((size_t)tn_groups(B, F, N) * F * N), w.take<float>((size_t)tn_groups(B, H, N) * H * N),
+          w.take<float>((size_t)colsum_wgs((size_t)B * T) * N), w.off};
 }
+size_t mgr_lstm_param_grads_ws_bytes(int B, int T, int F, int H) { return pg_ws_layout(nullptr, B, T, F, H).bytes; }
 
 static int param_grads_impl(mgr_ctx* c, const float* X, int ldx, const float* mask4, const float* Hs, int ldh, const float* dZ,
                             float* dWp, float* dUp, float* dbp, int B, int T, int F, int H, int reverse, void* ws, bool with_dW,
                             const float* dbsum = nullptr) {
   int N = 4 * H;
   int sgW = tn_groups(B, F, N), sgU = tn_groups(B, H, N);
-  char* w = reinterpret_cast<char*>(ws);
-  float* slabW = reinterpret_cast<float*>(w);
-  w += mgr_align_up((size_t)sgW * F * N * sizeof(float), 256);
-  float* slabU = reinterpret_cast<float*>(w);
-  w += mgr_align_up((size_t)sgU * H * N * sizeof(float), 256);
-  float* slabB = reinterpret_cast<float*>(w);
+  const PgWs L = pg_ws_layout(ws, B, T, F, H);
+  float *slabW = L.slabW, *slabU = L.slabU, *slabB = L.slabB;
   hipStream_t s = mgr_stream(c);
   if (with_dW) {
     int vecA = (ldx % 4 == 0) && (F % 4 == 0) && aligned16(X);
@@ -1846,15 +1847,16 @@ int mgr_lstm_param_grads(mgr_ctx* c, const float* X, int ldx, const float* mask4
   return 0;
 }
 
-static size_t pg_dropout_extra(int B, int F, int H) {
-  const size_t Fp = (size_t)(F + SP_SK - 1) / SP_SK * SP_SK;
-  return 2 * mgr_align_up((size_t)4 * B * Fp * sizeof(int), 256) + mgr_align_up((size_t)4 * B * sizeof(int), 256) +
-         mgr_align_up((size_t)4 * B * F * sizeof(int), 256) + mgr_align_up((size_t)4 * B * Fp * H * sizeof(float), 256);
+// the workspace of mgr_lstm_param_grads, then: kept-feature lists (index, factor) [4B][Fp] | counts [4B] | list positions [4B][F] |
+// partial tiles [4B][Fp][H]; with ldt >= 0 (the _t form) also dZT [B][4H][ldt] | the row maxima of dZT [B][4H] + the bound-violation word
+struct PgDropWs { int* kidx; float* kval; int *kcnt, *kpos; float *P, *dZT; unsigned* zmax; size_t bytes; };
+static PgDropWs pg_dropout_ws_layout(void* ws, int B, int T, int F, int H, int ldt) {
+  mgr_ws_carver w(ws, pg_ws_layout(nullptr, B, T, F, H).bytes);
+  const size_t nl = (size_t)4 * B * sp_fp(F), nz = (size_t)B * 4 * H;
+  return {w.take<int>(nl), w.take<float>(nl), w.take<int>((size_t)4 * B), w.take<int>((size_t)4 * B * F), w.take<float>(nl * H),
+          ldt >= 0 ? w.take<float>(nz * ldt) : nullptr, ldt >= 0 ? w.take<unsigned>(nz + 1) : nullptr, w.off};
 }
-
-size_t mgr_lstm_param_grads_dropout_ws_bytes(int B, int T, int F, int H) {
-  return mgr_lstm_param_grads_ws_bytes(B, T, F, H) + pg_dropout_extra(B, F, H);
-}
+size_t mgr_lstm_param_grads_dropout_ws_bytes(int B, int T, int F, int H) { return pg_dropout_ws_layout(nullptr, B, T, F, H, -1).bytes; }
 
 // dU / db (and the dense dW when the shape is not sparse) + the dropout-aware dW; XT / ldt != 0: operands of the dW product
 // from transposed copies (XT given by the caller, dZT made here)
@@ -1866,29 +1868,21 @@ static int param_grads_dropout_impl(mgr_ctx* c, const float* X, int ldx, const f
   // runs these under an encoder scan; what is left over after the scan is exposed)
   param_grads_impl(c, X, ldx, mask4, Hs, ldh, dZ, dWp, dUp, dbp, B, T, F, H, reverse, ws, !sparse);
   if (sparse) {
-    const int Fp = (F + SP_SK - 1) / SP_SK * SP_SK;
-    const size_t lbytes = mgr_align_up((size_t)4 * B * Fp * sizeof(int), 256);
-    char* w = reinterpret_cast<char*>(ws) + mgr_lstm_param_grads_ws_bytes(B, T, F, H);
-    int* kidx = reinterpret_cast<int*>(w);
-    float* kval = reinterpret_cast<float*>(w + lbytes);
-    int* kcnt = reinterpret_cast<int*>(w + 2 * lbytes);
-    w += 2 * lbytes + mgr_align_up((size_t)4 * B * sizeof(int), 256);
-    int* kpos = reinterpret_cast<int*>(w);
-    w += mgr_align_up((size_t)4 * B * F * sizeof(int), 256);
-    float* P = reinterpret_cast<float*>(w);
-    w += mgr_align_up((size_t)4 * B * Fp * H * sizeof(float), 256);
+    const int Fp = (int)sp_fp(F);
+    const PgDropWs L = pg_dropout_ws_layout(ws, B, T, F, H, XT ? ldt : -1);
+    int *kidx = L.kidx, *kcnt = L.kcnt, *kpos = L.kpos;
+    float *kval = L.kval, *P = L.P;
     hipStream_t s = mgr_stream(c);
     hipLaunchKernelGGL(k_mask_compact, dim3(4 * B), dim3(64), 0, s, mask4, F, Fp, kidx, kval, kcnt, kpos, (unsigned*)nullptr);
     const int grid = 8 * ((B + 7) / 8) * 4 * ((Fp + BM - 1) / BM) * ((H + BN - 1) / BN);
     if (XT) {
-      float* dZT = reinterpret_cast<float*>(w);   // [B][4H][ldt]
-      w += mgr_align_up((size_t)B * 4 * H * ldt * sizeof(float), 256);
       // split-f16 kernel (MGR_TUNE_GEMM_F32 = 1: never): a bound on |X| (stated: checked on the device, f32 kernel if violated; negative:
       // guaranteed by the producer of XT), whole stages of 32 time steps in the padded rows
       const bool trusted = x_absmax < 0.f;
       const float xb = fabsf(x_absmax);
       const bool f16 = xb > 0.f && xb < 1.0e30f && c->tune[MGR_TUNE_GEMM_F32] == 0 && ldt >= (T + 31) / 32 * 32;
-      unsigned* zmax = reinterpret_cast<unsigned*>(w);   // [B][4H] largest |dZ| of a (sample, gate column), + the gate word
+      float* dZT = L.dZT;
+      unsigned* zmax = L.zmax;   // [B][4H] largest |dZ| of a (sample, gate column), + the gate word
       unsigned* gate = (f16 && !trusted) ? zmax + (size_t)B * 4 * H : nullptr;
       if (f16) MGR_HIP(hipMemsetAsync(zmax, 0, ((size_t)B * 4 * H + 1) * sizeof(unsigned), s));
       hipLaunchKernelGGL(k_transpose_bt, dim3((ldt + 63) / 64, (4 * H + 63) / 64, B), dim3(256), 0, s, dZ, 4 * H, dZT, ldt, T, 4 * H, 0LL, ldt,
@@ -1899,7 +1893,7 @@ static int param_grads_dropout_impl(mgr_ctx* c, const float* X, int ldx, const f
         const float sx = ldexpf(1.f, 15 - ex);
         if (gate) {
           const size_t n4 = (size_t)B * F * ldt / 4;
-          hipLaunchKernelGGL(k_absmax_gate, dim3((int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096)), dim3(256), 0, s, XT, n4, 65000.f / sx, gate);
+          hipLaunchKernelGGL(k_absmax_gate, dim3(mgr_grid256(n4, 4096)), dim3(256), 0, s, XT, n4, 65000.f / sx, gate);
         }
         hipLaunchKernelGGL(k_gemm_tn_sparse16, dim3(grid), dim3(256), 0, s, XT, ldt, kidx, kval, kcnt, dZT, ldt, zmax, P, B, T, Fp, F, H, sx, gate);
         if (gate)
@@ -1911,7 +1905,7 @@ static int param_grads_dropout_impl(mgr_ctx* c, const float* X, int ldx, const f
       hipLaunchKernelGGL((k_gemm_tn_sparse<false>), dim3(grid), dim3(256), 0, s, X, ldx, kidx, kval, kcnt, dZ, 0, P, B, T, Fp, F, H, (const unsigned*)nullptr);
     }
     const size_t n = (size_t)4 * F * H;
-    hipLaunchKernelGGL(k_dw_gather, dim3((int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)), dim3(256), 0, s, P, kpos, dWp, B, F, Fp, H);
+    hipLaunchKernelGGL(k_dw_gather, dim3(mgr_grid256(n, 4096)), dim3(256), 0, s, P, kpos, dWp, B, F, Fp, H);
   }
   MGR_LAUNCH_CHECK();
   mgr_prof_end(c, MGR_K_GEMM_TN);
@@ -1939,10 +1933,7 @@ int mgr_lstm_param_grads_dropout_wants_transposed(mgr_ctx* c, float drop_rate, i
   return (c && drop_rate >= 0.3f && F >= 128 && c->tune[MGR_TUNE_PROJ_DENSE] == 0) ? 1 : 0;
 }
 
-size_t mgr_lstm_param_grads_dropout_t_ws_bytes(int B, int T, int F, int H, int ldt) {
-  return mgr_lstm_param_grads_dropout_ws_bytes(B, T, F, H) + mgr_align_up((size_t)B * 4 * H * ldt * sizeof(float), 256) +
-         mgr_align_up(((size_t)B * 4 * H + 1) * sizeof(unsigned), 256);   // (dZT, the row maxima of dZT + the bound-violation word)
-}
+size_t mgr_lstm_param_grads_dropout_t_ws_bytes(int B, int T, int F, int H, int ldt) { return pg_dropout_ws_layout(nullptr, B, T, F, H, ldt).bytes; }
 
 int mgr_lstm_param_grads_dropout_t(mgr_ctx* c, const float* XT, int ldt, const float* mask4, float drop_rate, const float* Hs, int ldh,
                                    const float* dZ, float* dWp, float* dUp, float* dbp, int B, int T, int F, int H, int reverse,

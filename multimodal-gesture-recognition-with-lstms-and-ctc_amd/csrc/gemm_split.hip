@@ -705,11 +705,13 @@ extern "C" {
 
 // workspace of the projection: kept lists [4B][Fp32] | counts [4B] | words | weight planes | list positions [4B][F] (the last for
 // mgr_lstm_param_grads_dropout_ts, which may take its lists from the projection of the same mask instead of building them again)
-static size_t proj_ts_planes_bytes(int F, int H) { return mgr_align_up((size_t)4 * (F + 1) * 2 * hp_of(H) * sizeof(_Float16), 256); }
-size_t mgr_lstm_input_proj_dropout_ts_ws_bytes(int B, int F, int H) {
-  return mgr_align_up((size_t)4 * B * fp32_of(F) * sizeof(int), 256) + mgr_align_up((size_t)4 * B * sizeof(int), 256) + 256 +
-         proj_ts_planes_bytes(F, H) + mgr_align_up((size_t)4 * B * F * sizeof(int), 256);
+struct ProjTsWs { int *lists, *kcnt; unsigned* words /* [0] largest |W|, [1] the mask factor */; _Float16* WSp; int* kpos; size_t bytes; };
+static ProjTsWs proj_ts_ws_layout(const void* ws, int B, int F, int H) {
+  mgr_ws_carver w(ws);
+  return {w.take<int>((size_t)4 * B * fp32_of(F)), w.take<int>((size_t)4 * B), w.take<unsigned>(64),
+          w.take<_Float16>((size_t)4 * (F + 1) * 2 * hp_of(H)), w.take<int>((size_t)4 * B * F), w.off};
 }
+size_t mgr_lstm_input_proj_dropout_ts_ws_bytes(int B, int F, int H) { return proj_ts_ws_layout(nullptr, B, F, H).bytes; }
 
 int mgr_lstm_input_proj_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const float* mask4, float drop_rate, const float* Wp,
                                    const float* bp, float* Z, int B, int T, int F, int H, void* ws, size_t ws_bytes) {
@@ -718,31 +720,26 @@ int mgr_lstm_input_proj_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const f
   MGR_REQUIRE(ldt % PS_TM == 0 && ldt >= T, "the split copy must be padded to whole row tiles of %d (ldt %d, T %d)", PS_TM, ldt, T);
   MGR_REQUIRE(aligned16(XS) && aligned16(bp) && aligned16(Z) && aligned16(Wp), "XS / bp / Z / Wp must be 16-byte aligned");
   MGR_REQUIRE((size_t)F * ldt * 4 < (1ull << 32), "sample block too large");
-  MGR_REQUIRE(ws && ws_bytes >= mgr_lstm_input_proj_dropout_ts_ws_bytes(B, F, H), "workspace too small");
+  const ProjTsWs L = proj_ts_ws_layout(ws, B, F, H);
+  const size_t need = L.bytes;
+  MGR_REQUIRE(ws && ws_bytes >= need, "workspace too small");
   (void)drop_rate;
   const int Fp32 = fp32_of(F), Hp = hp_of(H);
-  char* w = reinterpret_cast<char*>(ws);
-  int* lists = reinterpret_cast<int*>(w);
-  w += mgr_align_up((size_t)4 * B * Fp32 * sizeof(int), 256);
-  int* kcnt = reinterpret_cast<int*>(w);
-  w += mgr_align_up((size_t)4 * B * sizeof(int), 256);
-  unsigned* words = reinterpret_cast<unsigned*>(w);   // [0] largest |W|, [1] the mask factor
-  w += 256;
-  _Float16* WSp = reinterpret_cast<_Float16*>(w);
-  w += proj_ts_planes_bytes(F, H);
-  int* kpos = reinterpret_cast<int*>(w);
+  int *lists = L.lists, *kcnt = L.kcnt, *kpos = L.kpos;
+  unsigned* words = L.words;
+  _Float16* WSp = L.WSp;
   hipStream_t s = mgr_stream(c);
-  if (!(c->attr_done & 16u)) {
+  if (!(c->attr_done & MGR_ATTR_PROJ_SPLIT)) {
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_split<2>), hipFuncAttributeMaxDynamicSharedMemorySize, PsCfg<2>::LDS));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_split<4>), hipFuncAttributeMaxDynamicSharedMemorySize, PsCfg<4>::LDS));
-    c->attr_done |= 16u;
+    c->attr_done |= MGR_ATTR_PROJ_SPLIT;
   }
   mgr_prof_begin(c, MGR_K_GEMM_NN);
   // Frozen weights (mgr_weight_planes_cache): the planes this workspace holds from an earlier call with the same (Wp, ws, B, F, H) are
   // still those of Wp - the largest |W| (words[0]) and the (hi, lo) planes are not rebuilt, only the mask factor word is reset (4 of
   // the 6 conversions of a config-F step)
   const char* region = reinterpret_cast<const char*>(words);   // (what an entry relies on: the word block and the planes)
-  const size_t region_bytes = 256 + proj_ts_planes_bytes(F, H);
+  const size_t region_bytes = (size_t)(reinterpret_cast<const char*>(kpos) - region);
   bool frozen = false;
   int hit = -1;
   for (int i = 0; i < MGR_MAX_FROZEN; ++i) frozen = frozen || (c->frozen_w[i] == Wp);
@@ -754,7 +751,6 @@ int mgr_lstm_input_proj_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const f
   }
   // this call writes [ws, ws + its size) - all of it but the hit entry's own bytes: every other entry that lies there is forgotten,
   // frozen Wp or not
-  const size_t need = mgr_lstm_input_proj_dropout_ts_ws_bytes(B, F, H);
   for (int i = 0; i < MGR_MAX_FROZEN; ++i)
     if (i != hit && mgr_planes_overlap(c->planes[i], ws, need)) c->planes[i] = mgr_ctx::PlaneEntry{};
   const bool cached = hit >= 0;
@@ -762,9 +758,9 @@ int mgr_lstm_input_proj_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const f
   hipLaunchKernelGGL(k_lists32, dim3(4 * B), dim3(64), 0, s, mask4, F, Fp32, lists, kcnt, kpos, words + 1);
   if (!cached) {
     const size_t n4 = (size_t)F * H;
-    hipLaunchKernelGGL(k_wmax, dim3((int)((n4 + 255) / 256 < 256 ? (n4 + 255) / 256 : 256)), dim3(256), 0, s, Wp, n4, words);
+    hipLaunchKernelGGL(k_wmax, dim3(mgr_grid256(n4, 256)), dim3(256), 0, s, Wp, n4, words);
     const size_t n = (size_t)(F + 1) * Hp;
-    hipLaunchKernelGGL(k_wplanes, dim3((int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, s, Wp, WSp, F, H, Hp, words);
+    hipLaunchKernelGGL(k_wplanes, dim3(mgr_grid256(n, 2048)), dim3(256), 0, s, Wp, WSp, F, H, Hp, words);
     if (frozen) {   // (a full table forgets its oldest entry: forgetting is always safe)
       int slot = -1;
       for (int i = 0; i < MGR_MAX_FROZEN && slot < 0; ++i)
@@ -791,19 +787,19 @@ int mgr_lstm_input_proj_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const f
 }
 
 // lists | counts | words | list positions | partial tiles of a dW-shaped product with F input rows
-static size_t dw_ts_lists_and_tiles(int B, int F, int H) {
-  const size_t Fp32 = (size_t)fp32_of(F);
-  return mgr_align_up((size_t)4 * B * Fp32 * sizeof(int), 256) + mgr_align_up((size_t)4 * B * sizeof(int), 256) + 256 +
-         mgr_align_up((size_t)4 * B * F * sizeof(int), 256) + mgr_align_up((size_t)4 * B * Fp32 * H * sizeof(float), 256);
+struct DwTsGroup { int *lists, *kcnt; unsigned* words /* [1] the mask factor */; int* kpos; float* P; };
+static DwTsGroup dw_ts_group(mgr_ws_carver& w, int B, int F, int H) {
+  const size_t nl = (size_t)4 * B * fp32_of(F);
+  return {w.take<int>(nl), w.take<int>((size_t)4 * B), w.take<unsigned>(64), w.take<int>((size_t)4 * B * F), w.take<float>(nl * H)};
 }
-static size_t dw_ts_extra(int B, int F, int H, int ldt) {
-  return dw_ts_lists_and_tiles(B, F, H) + mgr_align_up((size_t)B * 4 * H * ldt * sizeof(float), 256) +
-         mgr_align_up((size_t)B * 4 * H * sizeof(unsigned), 256) + dw_ts_lists_and_tiles(B, H, H);   // (the last: dU from HsT, F = H rows)
+// the workspace of mgr_lstm_param_grads, then: the dW group | split dZ^T [B][4H][ldt] | its row maxima [B][4H] | the group of dU
+// from HsT (F = H rows; its list positions are the rows themselves: the block stays, nothing writes or reads it)
+struct DwTsWs { DwTsGroup dW; float* dZS; unsigned* zmax; DwTsGroup dU; size_t bytes; };
+static DwTsWs dw_ts_ws_layout(void* ws, int B, int T, int F, int H, int ldt) {
+  mgr_ws_carver w(ws, mgr_lstm_param_grads_ws_bytes(B, T, F, H));
+  return {dw_ts_group(w, B, F, H), w.take<float>((size_t)B * 4 * H * ldt), w.take<unsigned>((size_t)B * 4 * H), dw_ts_group(w, B, H, H), w.off};
 }
-
-size_t mgr_lstm_param_grads_dropout_ts_ws_bytes(int B, int T, int F, int H, int ldt) {
-  return mgr_lstm_param_grads_ws_bytes(B, T, F, H) + dw_ts_extra(B, F, H, ldt);
-}
+size_t mgr_lstm_param_grads_dropout_ts_ws_bytes(int B, int T, int F, int H, int ldt) { return dw_ts_ws_layout(nullptr, B, T, F, H, ldt).bytes; }
 
 int mgr_lstm_param_grads_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const float* mask4, float drop_rate, const float* Hs, int ldh,
                                     const float* dZ, float* dWp, float* dUp, float* dbp, int B, int T, int F, int H, int reverse,
@@ -815,7 +811,8 @@ int mgr_lstm_param_grads_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const 
   MGR_REQUIRE(ldt % 32 == 0 && ldt >= (T + DW_TK - 1) / DW_TK * DW_TK, "the split copy must be padded to whole stages of %d time steps (ldt %d, T %d)", DW_TK, ldt, T);
   MGR_REQUIRE(aligned16(dZ) && aligned16(XS), "dZ / XS must be 16-byte aligned");
   MGR_REQUIRE((size_t)F * ldt * 4 < (1ull << 32) && (size_t)4 * H * ldt * 4 < (1ull << 32), "sample block too large");
-  MGR_REQUIRE(ws && ws_bytes >= mgr_lstm_param_grads_dropout_ts_ws_bytes(B, T, F, H, ldt), "workspace too small");
+  const DwTsWs L = dw_ts_ws_layout(ws, B, T, F, H, ldt);
+  MGR_REQUIRE(ws && ws_bytes >= L.bytes, "workspace too small");
   (void)drop_rate;
   mgr_prof_begin(c, MGR_K_GEMM_TN);
   // dU / db first: they are short, and in the training step the long dW kernel then ends this direction's work (gemm.hip)
@@ -823,49 +820,25 @@ int mgr_lstm_param_grads_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const 
   int r = mgr_param_grads_du_db(c, Hs, ldh, dZ, HsT ? nullptr : dUp, dbp, B, T, F, H, reverse, ws, dbsum);
   if (r) return r;
   const int Fp32 = fp32_of(F), N = 4 * H;
-  char* w = reinterpret_cast<char*>(ws) + mgr_lstm_param_grads_ws_bytes(B, T, F, H);
-  int* lists = reinterpret_cast<int*>(w);
-  w += mgr_align_up((size_t)4 * B * Fp32 * sizeof(int), 256);
-  int* kcnt = reinterpret_cast<int*>(w);
-  w += mgr_align_up((size_t)4 * B * sizeof(int), 256);
-  unsigned* words = reinterpret_cast<unsigned*>(w);   // [1] the mask factor
-  w += 256;
-  int* kpos = reinterpret_cast<int*>(w);
-  w += mgr_align_up((size_t)4 * B * F * sizeof(int), 256);
-  float* P = reinterpret_cast<float*>(w);
-  w += mgr_align_up((size_t)4 * B * Fp32 * H * sizeof(float), 256);
-  float* dZS = reinterpret_cast<float*>(w);
-  w += mgr_align_up((size_t)B * N * ldt * sizeof(float), 256);
-  const unsigned* zmax = dzmax ? dzmax : reinterpret_cast<unsigned*>(w);   // (the BPTT's own row maxima, or found here)
-  w += mgr_align_up((size_t)B * N * sizeof(unsigned), 256);
+  int *lists = L.dW.lists, *kcnt = L.dW.kcnt, *kpos = L.dW.kpos;
+  unsigned* words = L.dW.words;
+  float *P = L.dW.P, *dZS = L.dZS;
+  const unsigned* zmax = dzmax ? dzmax : L.zmax;   // (the BPTT's own row maxima, or found here)
   // dU from HsT: the same product with the H rows h_prev in place of the kept input features (every row kept, factor 1)
   const int Hp32 = fp32_of(H);
-  int* lists2 = reinterpret_cast<int*>(w);
-  w += mgr_align_up((size_t)4 * B * Hp32 * sizeof(int), 256);
-  int* kcnt2 = reinterpret_cast<int*>(w);
-  w += mgr_align_up((size_t)4 * B * sizeof(int), 256);
-  unsigned* words2 = reinterpret_cast<unsigned*>(w);
-  w += 256;
-  // (the list positions of this product are the rows themselves: their block of the layout stays, nothing writes or reads it)
-  w +=mgr_align_up((size_t)4 * B * H * sizeof(int), 256);
-  float* P2 = reinterpret_cast<float*>(w);
+  int *lists2 = L.dU.lists, *kcnt2 = L.dU.kcnt;
+  unsigned* words2 = L.dU.words;
+  float* P2 = L.dU.P;
   hipStream_t s = mgr_stream(c);
-  if (!(c->attr_done & 32u)) {
+  if (!(c->attr_done & MGR_ATTR_DW_SPLIT)) {
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dw_split<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * DW_STAGE));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dw_split<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * DW_STAGE));
-    c->attr_done |= 32u;
+    c->attr_done |= MGR_ATTR_DW_SPLIT;
   }
   if (proj_ws) {
-    // the lists, counts, list positions and the mask factor the projection of the SAME mask left in its workspace (the layout of
-    // mgr_lstm_input_proj_dropout_ts above): nothing to build
-    char* pw = reinterpret_cast<char*>(const_cast<void*>(proj_ws));
-    lists = reinterpret_cast<int*>(pw);
-    pw += mgr_align_up((size_t)4 * B * Fp32 * sizeof(int), 256);
-    kcnt = reinterpret_cast<int*>(pw);
-    pw += mgr_align_up((size_t)4 * B * sizeof(int), 256);
-    words = reinterpret_cast<unsigned*>(pw);
-    pw += 256 + proj_ts_planes_bytes(F, H);
-    kpos = reinterpret_cast<int*>(pw);
+    // the lists, counts, list positions and the mask factor the projection of the SAME mask left in its workspace: nothing to build
+    const ProjTsWs Lp = proj_ts_ws_layout(proj_ws, B, F, H);
+    lists = Lp.lists, kcnt = Lp.kcnt, words = Lp.words, kpos = Lp.kpos;
   } else {
     MGR_HIP(hipMemsetAsync(words, 0, 2 * sizeof(unsigned), s));
     hipLaunchKernelGGL(k_lists32, dim3(4 * B), dim3(64), 0, s, mask4, F, Fp32, lists, kcnt, kpos, words + 1);
@@ -884,7 +857,7 @@ int mgr_lstm_param_grads_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const 
       hipLaunchKernelGGL(k_dw_split<8>, dim3(grid2), dim3(512), 4 * DW_STAGE, s, reinterpret_cast<const char*>(HsT), ldt, lists2, kcnt2, words2 + 1,
                          reinterpret_cast<const char*>(dZS), zmax, P2, B, T, Hp32, H, H);
     const size_t n2 = (size_t)H * H;
-    hipLaunchKernelGGL(k_dw_gather32, dim3((int)((n2 + 255) / 256 < 4096 ? (n2 + 255) / 256 : 4096)), dim3(256), 0, s, P2, (const int*)nullptr, dUp, B, H,
+    hipLaunchKernelGGL(k_dw_gather32, dim3(mgr_grid256(n2, 4096)), dim3(256), 0, s, P2, (const int*)nullptr, dUp, B, H,
                        Hp32, H, (int)aligned16(dUp));   // (every row kept at its own position: no position table)
   }
   const int grid = 8 * ((B + 7) / 8) * 4 * ((Fp32 + DW_BM - 1) / DW_BM) * ((H + DW_BN - 1) / DW_BN);
@@ -897,7 +870,7 @@ int mgr_lstm_param_grads_dropout_ts(mgr_ctx* c, const float* XS, int ldt, const 
     hipLaunchKernelGGL(k_dw_split<8>, dim3(grid), dim3(512), 4 * DW_STAGE, s, reinterpret_cast<const char*>(XS), ldt, lists, kcnt, words + 1,
                        reinterpret_cast<const char*>(dZS), zmax, P, B, T, Fp32, F, H);
   const size_t n = (size_t)F * H;
-  hipLaunchKernelGGL(k_dw_gather32, dim3((int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)), dim3(256), 0, s, P, kpos, dWp, B, F, Fp32, H,
+  hipLaunchKernelGGL(k_dw_gather32, dim3(mgr_grid256(n, 4096)), dim3(256), 0, s, P, kpos, dWp, B, F, Fp32, H,
                      (int)aligned16(dWp));
   MGR_LAUNCH_CHECK();
   mgr_prof_end(c, MGR_K_GEMM_TN);

@@ -1188,21 +1188,21 @@ int mgr_cluster_launch(mgr_ctx* c, const ClusterLaunch& L, int total_wgs, bool a
     MGR_REQUIRE(live <= per_cu * c->cu_count, "cluster scan needs %d co-resident workgroups but the device holds %d", live,
                 per_cu * c->cu_count);
   }
-  if (!(c->attr_done & 1u)) {   // (function attributes are per device, hence per context)
+  if (!(c->attr_done & MGR_ATTR_SCAN_CLUSTER)) {   // (function attributes are per device, hence per context)
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_ks), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_ks_s), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_k16), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_k16_s), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    c->attr_done |= 1u;
+    c->attr_done |= MGR_ATTR_SCAN_CLUSTER;
   }
   const bool fused = L.fused && L.split16 && ks_eligible(L, any_exchange, 4);
   MGR_REQUIRE(!L.xcd_local || fused || ks_eligible(L, any_exchange, waves), "XCD-local layout is only understood by the K-split kernel");
   if (fused) {
     MGR_REQUIRE(L.xcd_local, "the fused form is laid out in octets");
-    if (!(c->attr_done & 64u)) {   // (per device, hence per context - like the block above)
+    if (!(c->attr_done & MGR_ATTR_SCAN_CLUSTER_FUSED)) {   // (per device, hence per context - like the block above)
       MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_k16fs), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      c->attr_done |= 64u;
+      c->attr_done |= MGR_ATTR_SCAN_CLUSTER_FUSED;
     }
     hipLaunchKernelGGL(k_scan_cluster_k16fs, dim3(total_wgs), dim3(512), K16FS_LDS_BYTES, mgr_stream(c), L);
   } else if (ks_eligible(L, any_exchange, waves)) {

@@ -1005,7 +1005,7 @@ void mgr_cluster_bwd_geometry(const mgr_ctx* c, const ClusterBwdLaunch& L, int t
 int mgr_cluster_bwd_launch(mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs, int form16) {
   const bool alone = form16 == 0;
   MGR_REQUIRE(total_wgs <= 2 * c->cu_count, "cluster BPTT needs %d co-resident workgroups", total_wgs);
-  if (!(c->attr_done & 2u)) {
+  if (!(c->attr_done & MGR_ATTR_SCAN_CLUSTER_BWD)) {
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_bwd_split), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_bwd_s), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1016,7 +1016,7 @@ int mgr_cluster_bwd_launch(mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs,
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_bwd16_sd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_bwd16_f), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_bwd16_fd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    c->attr_done |= 2u;
+    c->attr_done |= MGR_ATTR_SCAN_CLUSTER_BWD;
   }
   const bool f16 = c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0;   // split-f16 operands (MGR_TUNE_SCAN_F32_MFMA = 1: f32 MFMA)
   if (L.fused) {

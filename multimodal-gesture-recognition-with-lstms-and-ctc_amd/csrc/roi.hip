@@ -167,9 +167,9 @@ extern "C" int mgr_roi_crop(mgr_ctx* c, const uint8_t* frames, int n, int H, int
   MGR_REQUIRE(frames && boxes && out, "null argument");
   MGR_REQUIRE(((uintptr_t)frames & 3) == 0 && ((uintptr_t)out & 3) == 0, "frames and out must be 4-byte aligned");
   const size_t lds = sizeof(int) * (size_t)(4 * img_dim * img_dim) + sizeof(uint32_t) * (size_t)(ROI_WAVES * roi_raw_dwords(W));
-  if (!(c->attr_done & 256u)) {
+  if (!(c->attr_done & MGR_ATTR_ROI)) {
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_roi_crop), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    c->attr_done |= 256u;
+    c->attr_done |= MGR_ATTR_ROI;
   }
   hipStream_t st = mgr_stream(c);
   mgr_prof_begin(c, MGR_K_MISC);

@@ -1,0 +1,31 @@
+// Workspace layouts (plain host C++17, no HIP types).  A workspace is a sequence of blocks, each padded to 256 bytes, and has ONE layout
+// function next to its entry point: (base, dims) -> a struct of named block pointers + bytes.  The mgr_*_ws_bytes query is that
+// function with a null base.  The functions fill their struct from a braced list, which C++ evaluates left to right: the blocks in
+// member order, then bytes (the carver's running offset).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+// bump carver: only offsets are computed, and applied when a base is given (null base: null blocks, off is the total).  A const
+// base is the workspace of another call that is only read.
+struct mgr_ws_carver {
+  char* base;
+  size_t off;
+  explicit mgr_ws_carver(const void* b, size_t start = 0) : base(static_cast<char*>(const_cast<void*>(b))), off(start) {}
+  template <class T>
+  T* take(size_t n) {   // n elements of T, padded to 256 bytes
+    const size_t at = off;
+    off += (n * sizeof(T) + 255) / 256 * 256;
+    return base ? reinterpret_cast<T*>(base + at) : nullptr;
+  }
+};
+
+// beam.hip / beam_lm.hip: the trie (parent, label: [B][nodes]) and the (parent, label) hash table of [B] << bits entries, 1 << bits
+// the first power of two >= 2 * nodes (and >= 64: the table is whole 256-byte lines as it is)
+struct mgr_beam_ws { int bits; int32_t *parent, *label; unsigned long long* table; size_t bytes; };
+static inline mgr_beam_ws mgr_beam_ws_layout(void* ws, int B, size_t nodes) {
+  int bits = 6;
+  while (((size_t)1 << bits) < 2 * nodes) ++bits;
+  mgr_ws_carver w(ws);
+  return {bits, w.take<int32_t>((size_t)B * nodes), w.take<int32_t>((size_t)B * nodes), w.take<unsigned long long>((size_t)B << bits), w.off};
+}
