@@ -566,6 +566,49 @@ int mgr_ctc_align(mgr_ctx* ctx, const float* P, const int32_t* labels, const int
 int mgr_greedy_segments(mgr_ctx* ctx, const float* P, int B, int T, int C, int skip, float thr, int cap, int32_t* n_runs, int32_t* lab,
                         int32_t* seg, float* conf);
 
+/* ---- K13: lexicon-constrained CTC decode: the best PHRASE sequence whose word expansion the posteriors support - HTK
+ * HVite's token pass over a phrase lexicon composed with the CTC topology, with an optional prior over phrase sequences.  The audio
+ * network's classes are words, its gestures phrases of words (audio_network/data_generator.py: class_2_words).
+ * The lexicon is G phrases; phrase g is the word sequence phrase_words[phrase_off[g] .. phrase_off[g+1]-1] (n_g >= 1 words, each a class
+ * in [0, C) other than blank).  phrase_off [G+1] and phrase_words [phrase_off[G]] are HOST memory - the one pair of pointers of this
+ * call that is: they are checked entry by entry on every call and travel to the kernel as arguments.  Everything else is device memory.
+ * Emissions are the loss's and the aligner's: frames skip .., ln y = ln softmax(log(P + eps)).  For a phrase sequence Q = (g_1 .. g_m),
+ * m = 0 allowed,
+ *     score(Q) = A(words(Q)) + sum_i ext[prev_i + 1][g_i] + fin[g_m + 1]
+ * where A is the Viterbi forced-alignment log-probability of the concatenated words - exactly mgr_ctc_align's logp: the step over a
+ * blank only between different words, within and across phrases -, ext [(G+1)*G] double has row 0 = "start of sequence" (prev_1 = -1),
+ * fin [G+1] double or NULL has index 0 = "empty sequence" (g_0 = -1).  The table conventions are mgr_ctc_beam_search_lm's: entries are
+ * finite or -inf, -inf forbids the transition (a hard grammar and a soft bigram are the same table), THE CALLER refuses NaN and +inf.
+ * The call returns argmax_Q score(Q), computed exactly as one Viterbi pass over this state graph:
+ *   INIT     blank, before any phrase          W(g,k)   emits word k of phrase g
+ *   B(g,k)   k < n_g - 1: blank inside g       Z(g)     blank behind phrase g (per phrase: a bigram keeps its history)
+ * Into frame t every state may stay; W(g,k>0) is entered from B(g,k-1), and from W(g,k-1) if the two words differ; B(g,k) from W(g,k);
+ * Z(g) from W(g,n_g-1); W(g,0) from INIT + ext[0][g] (also applied at t = 0), from Z(g') + ext[g'+1][g], and from W(g',n_g'-1) +
+ * ext[g'+1][g] if that word differs from w[g][0].  The final score is the maximum of INIT + fin[0], W(g,n_g-1) + fin[g+1] and Z(g) +
+ * fin[g+1].  1 + 2 * n_words states; the lexicon need not be uniquely decodable.  The search compares f32 values (the tables rounded
+ * to f32); what it reports is summed again in fp64 over the path and the fp64 tables.  Finite table entries must therefore lie within
+ * the f32 range, |x| <= FLT_MAX: a larger negative one would round to -inf and forbid what the definition allows, a larger positive
+ * one to +inf.  THE CALLER checks that too (decoding.phrase_lm_tables does).
+ * Outputs: n_phr [B] the TRUE number of phrases, also when it exceeds cap (as mgr_greedy_segments); phr [B,cap] padded -1; seg
+ * [B,cap,2] the original frame indices (t + skip) of the phrase's first word's first frame and its last word's last frame; conf [B,cap]
+ * the mean of P[t, emitted word] over the phrase's non-blank frames (0 where phr = -1); path [B,T-skip] or NULL: the class emitted per
+ * frame, -1 from input_len on; logp [B] the network's part of the score (the fp64 sum of ln y over the path), score [B] = logp + the
+ * table terms.  input_len 0 gives the empty sequence, logp = 0, score = fin[0] (0 without fin).  A sample for which no sequence has a
+ * finite score gets n_phr = -1, score = logp = -inf, phr / seg / path rows -1, conf 0; the other samples are unaffected.
+ * Ties: the smaller back-pointer wins - stay, then from the state before, then the step over a blank; for W(g,0): stay, INIT, then the
+ * phrases g' in order, Z(g') before W(g',n_g'-1) - and among equal final scores the first state in lexicon order (INIT, then per word
+ * the word before its blank).  Deterministic; a sample's result does not depend on the rest of the batch.
+ * G <= MGR_LEXICON_MAX_PHRASES, n_words <= MGR_LEXICON_MAX_WORDS (511 states), C <= 64, T - skip <= MGR_SEGMENTS_MAX_FRAMES, cap >= 1.
+ * Parity with HVite itself is unpinned: HTK is not available to this project. */
+#define MGR_LEXICON_MAX_PHRASES 64
+#define MGR_LEXICON_MAX_WORDS   255
+/* The workspace for a lexicon of G phrases: phrase_off [G+1] is the HOST array the decode call takes (its last entry is n_words). */
+size_t mgr_ctc_lexicon_ws_bytes(int B, int T, int C, int G, const int32_t* phrase_off);
+int mgr_ctc_lexicon_decode(mgr_ctx* ctx, const float* P, const int32_t* input_len, int B, int T, int C, int skip, int blank, float eps,
+                           const int32_t* phrase_off, const int32_t* phrase_words, int G, const double* ext, const double* fin, int cap,
+                           int32_t* n_phr, int32_t* phr, int32_t* seg, float* conf, int32_t* path, double* score, double* logp, void* ws,
+                           size_t ws_bytes);
+
 /* ---- K12: scoring decodes: the weighted edit distance of n_pairs pairs of label sequences, with the substitution /
  * deletion / insertion split of HTK's HResults, in one launch.  All pointers are device memory.
  * hyp [n_hyp,Lh], ref [n_ref,Lr] int32, rows padded with -1; hyp_len [n_hyp] / ref_len [n_ref] int32 or NULL: NULL = the whole row,

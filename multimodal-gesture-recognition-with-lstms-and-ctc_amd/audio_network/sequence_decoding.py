@@ -1,7 +1,9 @@
 """Decode for the audio network (reference audio_network/sequence_decoding.py:19-69): word-level classes, thr .75."""
 import numpy as np
 
-from ..decoding import HTK_COSTS, decode_beam_mlf, decode_score_map, greedy_decode, greedy_decode_argmax, greedy_segments, write_mlf
+from ..decoding import (HTK_COSTS, decode_beam_mlf, decode_lexicon_mlf, decode_score_map, greedy_decode, greedy_decode_argmax,
+                        greedy_segments, write_mlf)
+from .data_generator import class_2_words
 
 _words = ["oov", "Vattene", "Vieni", "qui", "Perfetto", "E'", "un", "furbo", "Che", "due", "palle", "vuoi", "Vanno",
           "d'accordo", "Sei", "Pazzo", "Cos'hai", "combinato", "Non", "me", "ne", "frega", "niente", "ok", "Cosa", "ti",
@@ -11,6 +13,11 @@ map_gest = dict(enumerate(_words))
 map_gest[-1] = "sil"
 ignore_list = [228, 298, 299, 300, 303, 304, 334, 343, 373, 375]
 THRESHOLD = 0.75
+# The gestures behind the words: gesture class g is spoken as the words GESTURE_LEXICON[g] (what DataGenerator.sent_2_words expands
+# the labels with); class 21 is the blank itself and no phrase.  Names: the ChaLearn 2013 gesture codes listed in the reference
+# (audio_network/data_generator.py:126-128).
+GESTURE_LEXICON = [list(class_2_words[g]) for g in range(21)]
+gesture_names = ["oov", "VA", "VQ", "PF", "FU", "CP", "CV", "DC", "SP", "CN", "FN", "OK", "CF", "BS", "PR", "NU", "FM", "TT", "BN", "MC", "ST"]
 
 
 def decode_batch(pred_out, f_list, out_file="ctc_recout.mlf"):
@@ -49,6 +56,16 @@ def decode_beam(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, bea
     map into the MLF; returns (1-best name lists, (paths, score, logp_ctc)) - with top_paths > 1 the ranked N-best lists."""
     return decode_beam_mlf(pred_out, f_list, map_gest, ignore_list, "Sample%05d_audio", out_file, top_paths=top_paths, lm=lm, lm_end=lm_end,
                            alpha=alpha, beta=beta, beam_width=beam_width)
+
+
+def decode_lexicon(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, out_file="ctc_recout_gestures.mlf"):
+    """Gestures from the word posteriors (decoding.lexicon_decode over GESTURE_LEXICON): pred_out (N, T, C) softmax - or the
+    (segments, score, logp) that Model.predict_generator(decode="lexicon", lexicon=GESTURE_LEXICON, ...) computed on the device.  lm /
+    lm_end: a bigram over gestures as decoding.phrase_lm_tables takes it (None: no prior).  Every MLF line reads "start end gesture" in
+    HTK's 100 ns units, from the first frame of the gesture's first word to the last frame of its last word.  Returns (gesture-name
+    lists, segment lists of (gesture id, first_frame, last_frame, confidence))."""
+    return decode_lexicon_mlf(pred_out, f_list, GESTURE_LEXICON, gesture_names, ignore_list, "Sample%05d_audio", out_file, lm=lm,
+                              lm_end=lm_end, alpha=alpha, beta=beta)
 
 
 def decode_score(hyp_ids, ref_ids, costs=HTK_COSTS, confusion=True):

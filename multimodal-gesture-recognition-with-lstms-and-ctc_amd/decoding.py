@@ -252,22 +252,26 @@ def lm_tables(n_classes, lm=None, lm_end=None, alpha=1.0, beta=0.0):
     alpha * lm_end, or None.  -inf stays -inf whatever alpha is; NaN and +inf are refused here - the kernel reads device memory and
     cannot say so."""
     Cn = int(n_classes)
-
-    def scaled(t, shape, shift, what):
-        t = np.asarray(t, np.float64)
-        if t.shape != shape:
-            raise ValueError("%s has shape %s, the decoder needs %s" % (what, t.shape, shape))
-        if np.isnan(t).any() or np.isposinf(t).any():
-            raise ValueError("%s holds NaN or +inf: entries must be finite or -inf" % what)
-        ninf = np.isneginf(t)
-        out = np.where(ninf, -np.inf, float(alpha) * np.where(ninf, 0.0, t) + shift)
-        if not np.all(np.isfinite(out) | ninf):
-            raise ValueError("alpha / beta make %s NaN or infinite" % what)
-        return np.ascontiguousarray(out)
-
-    ext = scaled(np.zeros((Cn + 1, Cn)) if lm is None else lm, (Cn + 1, Cn), float(beta), "lm")
-    fin = None if lm_end is None else scaled(lm_end, (Cn + 1,), 0.0, "lm_end")
+    ext = _scaled_table(np.zeros((Cn + 1, Cn)) if lm is None else lm, (Cn + 1, Cn), alpha, float(beta), "lm")
+    fin = None if lm_end is None else _scaled_table(lm_end, (Cn + 1,), alpha, 0.0, "lm_end")
     return ext, fin
+
+
+def _scaled_table(t, shape, alpha, shift, what, f32_range=False):
+    """alpha * t + shift in fp64 with -inf kept, or ValueError: a wrong shape, NaN, +inf, or a weight that makes an entry so.
+    f32_range: also refuse a finite result beyond the float32 range (for a kernel that searches on the tables rounded to f32)."""
+    t = np.asarray(t, np.float64)
+    if t.shape != shape:
+        raise ValueError("%s has shape %s, the decoder needs %s" % (what, t.shape, shape))
+    if np.isnan(t).any() or np.isposinf(t).any():
+        raise ValueError("%s holds NaN or +inf: entries must be finite or -inf" % what)
+    ninf = np.isneginf(t)
+    out = np.where(ninf, -np.inf, float(alpha) * np.where(ninf, 0.0, t) + shift)
+    if not np.all(np.isfinite(out) | ninf):
+        raise ValueError("alpha / beta make %s NaN or infinite" % what)
+    if f32_range and np.any(np.abs(out[~ninf]) > np.finfo(np.float32).max):
+        raise ValueError("%s holds a finite entry beyond the float32 range: the decoder searches on the table rounded to float32" % what)
+    return np.ascontiguousarray(out)
 
 
 def nbest_from_arrays(out, out_len, score, logp_ctc, top_paths):
@@ -312,6 +316,122 @@ def beam_search_lm_decode(pred_out, lm=None, lm_end=None, alpha=1.0, beta=0.0, i
         for a in bufs:
             a.free()
     return res
+
+
+# ---- lexicon-constrained decode (K13): phrase sequences from word posteriors -----------------------------------------
+LEXICON_MAX_PHRASES, LEXICON_MAX_WORDS, LEXICON_MAX_CLASSES = 64, 255, 64       # MGR_LEXICON_MAX_* of include/mgr.h, and its C <= 64
+
+
+def compile_lexicon(lexicon, n_classes, blank=None):
+    """A phrase lexicon - a list of word lists, or a dict with the keys 0 .. G - 1 - in the layout mgr_ctc_lexicon_decode reads:
+    (phrase_off (G + 1,) int32, phrase_words (n_words,) int32), phrase g = phrase_words[phrase_off[g]:phrase_off[g + 1]].  Refuses an
+    empty lexicon or phrase, the blank (default: the last class) as a word, a word outside [0, n_classes) and a lexicon above the
+    kernel's limits (64 phrases, 255 words, 64 classes).  Phrases may share words and need not be uniquely decodable."""
+    Cn = int(n_classes)
+    blank = Cn - 1 if blank is None else int(blank)
+    if isinstance(lexicon, dict):
+        if sorted(lexicon) != list(range(len(lexicon))):
+            raise ValueError("a lexicon dict needs the keys 0 .. G - 1, got %r" % (sorted(lexicon),))
+        lexicon = [lexicon[g] for g in range(len(lexicon))]
+    lexicon = [[int(w) for w in p] for p in lexicon]
+    if not 1 <= len(lexicon) <= LEXICON_MAX_PHRASES:
+        raise ValueError("%d phrases: the decoder takes 1 .. %d" % (len(lexicon), LEXICON_MAX_PHRASES))
+    if not 2 <= Cn <= LEXICON_MAX_CLASSES or not 0 <= blank < Cn:
+        raise ValueError("n_classes = %d (2 .. %d) / blank = %d" % (Cn, LEXICON_MAX_CLASSES, blank))
+    for g, p in enumerate(lexicon):
+        if not p:
+            raise ValueError("phrase %d is empty" % g)
+        for w in p:
+            if w == blank:
+                raise ValueError("phrase %d holds the blank (%d) as a word" % (g, blank))
+            if not 0 <= w < Cn:
+                raise ValueError("phrase %d: word %d is outside [0, %d)" % (g, w, Cn))
+    off = np.concatenate([[0], np.cumsum([len(p) for p in lexicon])]).astype(np.int32)
+    if int(off[-1]) > LEXICON_MAX_WORDS:
+        raise ValueError("%d words in the lexicon: the decoder takes %d" % (int(off[-1]), LEXICON_MAX_WORDS))
+    return np.ascontiguousarray(off), np.ascontiguousarray(np.asarray([w for p in lexicon for w in p], np.int32))
+
+
+def phrase_lm_tables(G, lm=None, lm_end=None, alpha=1.0, beta=0.0):
+    """lm_tables for a prior over PHRASES - the two tables mgr_ctc_lexicon_decode reads, without a blank column: ext (G + 1, G) =
+    alpha * lm + beta (lm=None: zeros; row 0 = start of sequence) and fin (G + 1,) = alpha * lm_end (index 0 = the empty sequence), or
+    None.  -inf stays -inf; NaN, +inf and finite entries beyond the float32 range (the kernel searches on the tables rounded to
+    float32: -1e300 would become "forbidden") are refused.  bigram_lm counts the right thing when the phrase ids stand in for its labels
+    and one more id for its blank: lm, lm_end = bigram_lm(gesture_seqs, G + 1, blank=G) gives (G + 2, G + 1) / (G + 2,), of which the
+    decoder's tables are lm[:G + 1, :G] and lm_end[:G + 1] (the last row is "after the blank", the last column the blank's: neither
+    ever holds a count).  Pass those slices here."""
+    G = int(G)
+    if not 1 <= G <= LEXICON_MAX_PHRASES:
+        raise ValueError("G = %d phrases: the decoder takes 1 .. %d" % (G, LEXICON_MAX_PHRASES))
+    ext = _scaled_table(np.zeros((G + 1, G)) if lm is None else lm, (G + 1, G), alpha, float(beta), "lm", f32_range=True)
+    fin = None if lm_end is None else _scaled_table(lm_end, (G + 1,), alpha, 0.0, "lm_end", f32_range=True)
+    return ext, fin
+
+
+def lexicon_from_arrays(n, phr, seg, conf):
+    """mgr_ctc_lexicon_decode's (count, phrase, [first, last], confidence) arrays -> per sample a list of (phrase, first, last, conf);
+    a sample without a finite-scoring sequence (count -1) has none.  Raises when a sample has more phrases than the arrays hold."""
+    return segments_from_arrays(np.maximum(np.asarray(n), 0), phr, seg, conf)
+
+
+def lexicon_decode(pred_out, lexicon, lm=None, lm_end=None, alpha=1.0, beta=0.0, input_length=None, skip=2, dev=None, return_path=False,
+                   eps=1e-8, max_phrases=256):
+    """Lexicon-constrained CTC decode on the GPU (mgr_ctc_lexicon_decode): the best PHRASE sequence whose word expansion
+    the word posteriors pred_out (N, T, C) support - one Viterbi pass over the lexicon composed with the CTC topology (blank = C - 1),
+    with an optional phrase bigram lm (G + 1, G) / lm_end (G + 1,) weighted alpha, plus beta per phrase (phrase_lm_tables; -inf
+    forbids a transition).  lexicon: whatever compile_lexicon takes.
+    Returns (segments, score, logp[, path]): per sample a list of (phrase, first_frame, last_frame, confidence) - what write_mlf's
+    segments= takes; the frames, indices of the ORIGINAL sequence, run from the first frame of the phrase's first word to the last frame
+    of its last word, the confidence is the mean of P[t, emitted word] over its non-blank frames -, score (N,) float64 = logp + the
+    table terms, logp (N,) float64 the network's part, path (N, T - skip) int32 the class emitted per frame (-1 past input_length).
+    A sample for which no sequence has a finite score has no segments and -inf scores.  max_phrases sizes the first download; a sample
+    with more phrases (the device reports the true count) makes the call run again with room for T - skip."""
+    dev = dev or default_device()
+    P = np.ascontiguousarray(pred_out, dtype=np.float32)
+    N, T, Cn = P.shape
+    off, words = compile_lexicon(lexicon, Cn)
+    G = len(off) - 1
+    ext, fin = phrase_lm_tables(G, lm, lm_end, alpha, beta)
+    il = np.full(N, T - skip, np.int32) if input_length is None else np.asarray(input_length).reshape(N).astype(np.int32)
+    bufs = [dev.array(P), dev.array(il), dev.array(ext)]
+    try:
+        dfin = None
+        if fin is not None:
+            dfin = dev.array(fin)
+            bufs.append(dfin)
+        dn, dscore, dlogp = dev.empty((N,), np.int32), dev.empty((N,), np.float64), dev.empty((N,), np.float64)
+        dpath = dev.empty((N, T - skip), np.int32) if return_path else None
+        ws = dev.bytes(dev.lib.mgr_ctc_lexicon_ws_bytes(N, T, Cn, G, off.ctypes.data))
+        bufs += [dn, dscore, dlogp, ws] + ([dpath] if return_path else [])
+        cap = max(1, min(T - skip, int(max_phrases)))
+        while True:
+            dp, ds, dc = dev.empty((N, cap), np.int32), dev.empty((N, cap, 2), np.int32), dev.empty((N, cap), np.float32)
+            bufs += [dp, ds, dc]
+            dev.call("mgr_ctc_lexicon_decode", bufs[0], bufs[1], N, T, Cn, skip, Cn - 1, C.c_float(eps), off.ctypes.data, words.ctypes.data,
+                     G, bufs[2], dfin, cap, dn, dp, ds, dc, dpath, dscore, dlogp, ws, ws.nbytes)
+            n = dn.download()
+            if int(n.max()) <= cap:
+                break
+            cap = T - skip
+        segs = lexicon_from_arrays(n, dp.download(), ds.download(), dc.download())
+        res = (segs, dscore.download(), dlogp.download())
+        if return_path:
+            res += (dpath.download(),)
+    finally:
+        for a in bufs:
+            a.free()
+    return res
+
+
+def decode_lexicon_mlf(pred_out, f_list, lexicon, names, ignore_list, name_fmt, out_file, **kwargs):
+    """What a network's decode_lexicon does: pred_out (N, T, C) softmax - decoded with lexicon_decode(lexicon, **kwargs) - or the
+    (segments, score, logp) that Model.predict_generator(decode="lexicon", ...) computed on the device.  The phrases go through `names`
+    into the unchanged write_mlf with their times; returns (phrase-name lists, segments)."""
+    segs = pred_out[0] if isinstance(pred_out, tuple) else lexicon_decode(np.asarray(pred_out), lexicon, **kwargs)[0]
+    ret = [[names[s[0]] for s in sg] for sg in segs]
+    if out_file is not None:
+        write_mlf(out_file, ret, f_list, ignore_list, name_fmt, segments=segs)
+    return ret, segs
 
 
 def decode_beam_mlf(pred_out, f_list, map_gest, ignore_list, name_fmt, out_file, top_paths=1, **kwargs):

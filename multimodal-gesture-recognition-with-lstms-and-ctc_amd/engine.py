@@ -1006,7 +1006,7 @@ class Engine:
     EV_D1S = (57, 58)     # the depth-1 scans that read depth-1 Z set 0 / 1 are done (stream ES)
 
     def predict_stream(self, batches, output="posteriors", train_phase=False, beam_width=10, merge_repeated=True, threshold=None,
-                       lm=None, lm_end=None, alpha=1.0, beta=0.0, top_paths=1, decode="greedy", ignore=None, costs=(1, 1, 1)):
+                       lm=None, lm_end=None, alpha=1.0, beta=0.0, top_paths=1, decode="greedy", ignore=None, costs=(1, 1, 1), lexicon=None):
         """Batches of an inference / validation run are independent of each other: this generator keeps two of them in flight.
         Batch n + 1 is uploaded (copy stream) and runs its encoder pass (stream ES, into the other FEAT buffer) beside batch n's
         fusion layer / head / decode kernels (stream 0) and beside the download of batch n - 1's result (its own stream, into
@@ -1023,6 +1023,11 @@ class Engine:
           "beam_lm"     (paths, score (B,) or (B, top_paths) float64, logp_ctc likewise): mgr_ctc_beam_search_lm on the device - the
                         beam search with the label bigram lm / lm_end (weights alpha, beta) and top_paths hypotheses per sample, shaped
                         as decoding.beam_search_lm_decode returns them; the two tables are uploaded once per call, not per batch
+          "lexicon"     (segments: list of B lists of (phrase, first_frame, last_frame, confidence), score (B,) float64, logp (B,)
+                        float64): mgr_ctc_lexicon_decode on the device - the best phrase sequence over `lexicon` (whatever
+                        decoding.compile_lexicon takes) with the phrase bigram lm (G + 1, G) / lm_end (G + 1,) weighted alpha, beta,
+                        shaped as decoding.lexicon_decode returns them; the tables are uploaded once per call, and the per-sample
+                        result arrays are all that travels back
           "loss"        per-sample CTC losses (B,) float32  (a training engine; learning phase as train_phase)
           "segments"    list of B lists of (label, first_frame, last_frame, confidence): mgr_greedy_segments(threshold) on the device
                         where "argmax" runs mgr_frame_argmax - the greedy decode with its frame positions (decoding.greedy_segments)
@@ -1037,7 +1042,7 @@ class Engine:
         Results are bit-identical to the one-batch-at-a-time calls (predict / loss_on_batch): same kernels, same order per batch."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         Cn, skip = sp.num_classes, int(sp.ctc["skip"])
-        if output not in ("posteriors", "argmax", "beam", "beam_lm", "loss", "segments", "align", "score"):
+        if output not in ("posteriors", "argmax", "beam", "beam_lm", "lexicon", "loss", "segments", "align", "score"):
             raise ValueError("unknown output %r" % (output,))
         if output == "loss" and self.inference_only:
             raise ValueError("output='loss' needs a training engine (labels, CTC workspace)")
@@ -1098,6 +1103,28 @@ class Engine:
                        lambda: self.mem.bytes(self.lib.mgr_ctc_beam_lm_ws_bytes(B, T, Cn, int(beam_width), NP)))
             pins = bufs("beam_lm%d" % NP, lambda: [(dev.pinned((B, NP, T - skip), np.int32), dev.pinned((B, NP), np.int32),
                                                     dev.pinned((B, NP), np.float64), dev.pinned((B, NP), np.float64)) for _ in range(2)])
+        elif output == "lexicon":
+            from .decoding import compile_lexicon, phrase_lm_tables
+            if lexicon is None:
+                raise ValueError("output='lexicon' needs a lexicon")
+            loff, lwords = compile_lexicon(lexicon, Cn)        # (host arrays: the library reads and checks them at every call)
+            G = len(loff) - 1
+            ext, fin = phrase_lm_tables(G, lm, lm_end, alpha, beta)
+            dil = bufs("dil", lambda: self.mem.empty((B,), np.int32))
+            dil.upload(np.full(B, T - skip, np.int32))
+            dext = bufs("lex_ext%d" % G, lambda: self.mem.empty((G + 1, G), np.float64))
+            dext.upload(ext)
+            dfin = None
+            if fin is not None:
+                dfin = bufs("lex_fin%d" % G, lambda: self.mem.empty((G + 1,), np.float64))
+                dfin.upload(fin)
+            cap = T - skip      # a phrase takes a frame at least: the count the kernel reports never exceeds what is downloaded
+            dlex = bufs("dlex", lambda: (self.mem.empty((B,), np.int32), self.mem.empty((B, cap), np.int32), self.mem.empty((B, cap, 2), np.int32),
+                                         self.mem.empty((B, cap), np.float32), self.mem.empty((B,), np.float64), self.mem.empty((B,), np.float64)))
+            wsx = bufs("wslex%d_%d" % (G, len(lwords)), lambda: self.mem.bytes(self.lib.mgr_ctc_lexicon_ws_bytes(B, T, Cn, G, loff.ctypes.data)))
+            pins = bufs("lexicon", lambda: [(dev.pinned((B,), np.int32), dev.pinned((B, cap), np.int32), dev.pinned((B, cap, 2), np.int32),
+                                             dev.pinned((B, cap), np.float32), dev.pinned((B,), np.float64), dev.pinned((B,), np.float64))
+                                            for _ in range(2)])
         elif output == "segments":
             # room for T - skip runs per sample, the most there can be: the count the kernel reports never exceeds what is downloaded
             cap = T - skip
@@ -1177,6 +1204,9 @@ class Engine:
             elif output == "beam_lm":
                 from .decoding import nbest_from_arrays
                 r = nbest_from_arrays(*pins[o], NP)
+            elif output == "lexicon":
+                from .decoding import lexicon_from_arrays
+                r = (lexicon_from_arrays(*pins[o][:4]), pins[o][4].copy(), pins[o][5].copy())
             elif output == "segments":
                 from .decoding import segments_from_arrays
                 r = segments_from_arrays(*pins[o])
@@ -1331,6 +1361,11 @@ class Engine:
                              dext, dfin, NP, *dnb, wsb, wsb.nbytes)
                     for k in range(4):
                         dev.d2h_async(pins[o][k], dnb[k])
+                elif output == "lexicon":
+                    dev.call("mgr_ctc_lexicon_decode", pring[o], dil, B, T, Cn, skip, Cn - 1, C.c_float(float(sp.ctc["eps"])),
+                             loff.ctypes.data, lwords.ctypes.data, G, dext, dfin, cap, *dlex[:4], None, dlex[4], dlex[5], wsx, wsx.nbytes)
+                    for k in range(6):
+                        dev.d2h_async(pins[o][k], dlex[k])
                 elif output == "segments":
                     dev.call("mgr_greedy_segments", pring[o], B, T, Cn, skip, C.c_float(-1.0 if threshold is None else float(threshold)),
                              cap, *dseg)

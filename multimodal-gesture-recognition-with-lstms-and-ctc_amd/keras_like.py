@@ -565,7 +565,7 @@ class Model:
         return ({k: pad(v) for k, v in arrs.items()} if isinstance(arrs, dict) else pad(arrs)), n
 
     def predict_generator(self, generator, steps, verbose=0, decode=None, beam_width=10, threshold=None, lm=None, lm_end=None,
-                          alpha=1.0, beta=0.0, top_paths=1, **kwargs):
+                          alpha=1.0, beta=0.0, top_paths=1, lexicon=None, **kwargs):
         """keras Model.predict_generator (sequence_decoding.py:118-127): the batches of the run are pipelined through
         Engine.predict_stream - upload and encoder pass of batch n + 1 beside the fusion layer / head of batch n and the
         download of batch n - 1 - and give bit for bit what predict_on_batch gives one batch at a time.
@@ -575,7 +575,10 @@ class Model:
         returns per sample a list of (label, first_frame, last_frame, confidence) - decoding.greedy_segments(posteriors, threshold),
         computed on the device where "argmax" computes the frame maxima; decode="beam_lm" returns (paths, score, logp_ctc) of
         mgr_ctc_beam_search_lm - the beam search with the label bigram lm / lm_end (decoding.bigram_lm) weighted alpha, the per-label
-        bonus beta and top_paths hypotheses per sample: decoding.beam_search_lm_decode of the posteriors, computed on the device."""
+        bonus beta and top_paths hypotheses per sample: decoding.beam_search_lm_decode of the posteriors, computed on the device;
+        decode="lexicon" returns (segments, score, logp) of mgr_ctc_lexicon_decode - per sample the best sequence of the phrases of
+        `lexicon` as (phrase, first_frame, last_frame, confidence), with the phrase bigram lm / lm_end (decoding.phrase_lm_tables)
+        weighted alpha and the per-phrase bonus beta: decoding.lexicon_decode of the posteriors, computed on the device."""
         steps = int(steps)
         if steps <= 0:
             return np.zeros((0,))
@@ -595,8 +598,11 @@ class Model:
                 counts.append(n)
                 yield ins
 
-        output = {None: "posteriors", "argmax": "argmax", "beam": "beam", "beam_lm": "beam_lm", "segments": "segments"}[decode]
+        output = {None: "posteriors", "argmax": "argmax", "beam": "beam", "beam_lm": "beam_lm", "segments": "segments",
+                  "lexicon": "lexicon"}[decode]
         lm_args = dict(lm=lm, lm_end=lm_end, alpha=alpha, beta=beta, top_paths=top_paths) if output == "beam_lm" else {}
+        if output == "lexicon":
+            lm_args = dict(lm=lm, lm_end=lm_end, alpha=alpha, beta=beta, lexicon=lexicon)
         outs = []
         for i, r in enumerate(e.predict_stream(feed(), output=output, train_phase=bool(learning_phase()), beam_width=beam_width,
                                                threshold=threshold, **lm_args)):
@@ -605,7 +611,7 @@ class Model:
                 outs.append(r[:n])
             elif output == "argmax":
                 outs.append((r[0][:n], r[1][:n]))
-            elif output == "beam_lm":
+            elif output in ("beam_lm", "lexicon"):
                 outs.append((r[0][:n], r[1][:n], r[2][:n]))
             else:
                 outs.append((r[0][:n], r[1][:n]))
@@ -617,7 +623,7 @@ class Model:
             return [sg for o in outs for sg in o]
         if output == "argmax":
             return np.concatenate([o[0] for o in outs], axis=0), np.concatenate([o[1] for o in outs], axis=0)
-        if output == "beam_lm":
+        if output in ("beam_lm", "lexicon"):
             return [p for o in outs for p in o[0]], np.concatenate([o[1] for o in outs], axis=0), np.concatenate([o[2] for o in outs], axis=0)
         return [p for o in outs for p in o[0]], np.concatenate([o[1] for o in outs], axis=0)
 
