@@ -6,6 +6,7 @@ repeat collapse run on the host (greedy_decode) or, with the frame positions kep
 not the visited one): for every label s, the first k_s occurrences of s are dropped, where k_s is the number
 of frames whose best label is s with probability below the threshold.  Blanks are kept (they decode to "sil").
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -21,19 +22,158 @@ def default_device():
     return _DEV[0]
 
 
+# ---- one description per device decode: what the host wrappers below and Engine.predict_stream both read --------------
+DecodeOp = collections.namedtuple("DecodeOp", "name outputs launch result tables ws_bytes hyp uses_len", defaults=((), None, None, False))
+DecodeOp.__doc__ = """What there is to know about one decode kernel with its parameters set (built by the *_op factories, which validate):
+  outputs   (N, T, Lmax=None) -> one (shape, dtype) per device output, in the kernel's order; None = not asked for (null pointer)
+  launch    (dev, P, input_len, outs, tables, ws[, labels, label_len]): the one place the entry point's argument list is written;
+            arguments that are HOST memory (the lexicon's phrase_off / phrase_words) are kept by the op
+  result    (the outputs that are not None, as host arrays[, labels, label_len]) -> what the public function returns; it may hand an
+            array through as it came (Engine.predict_stream, which passes pinned buffers it reuses, copies every array it gets back)
+  tables    host arrays to upload once, in the kernel's order; None = absent, the kernel gets a null pointer
+  ws_bytes  (lib, N, T, Lmax=None) -> bytes of workspace, or None: the kernel takes none
+  hyp       (index of the output with the hypothesis labels [N, width] padded -1, index of their lengths), what mgr_edit_distance
+            takes from it for output="score" - or None
+  uses_len  whether the kernel reads input_len (launch gets None where it does not)
+Buffers are cached under what sizes them: the op's name with these shapes and byte counts."""
+
+
+def _i32(*shape):
+    return shape, np.int32
+
+
+def _f32(*shape):
+    return shape, np.float32
+
+
+def _f64(*shape):
+    return shape, np.float64
+
+
+def argmax_op(n_classes, skip):
+    Cn = int(n_classes)
+
+    def launch(dev, P, input_len, outs, tables, ws):
+        dev.call("mgr_frame_argmax", P, P.shape[0], P.shape[1], Cn, skip, *outs)
+    return DecodeOp("argmax", lambda N, T, Lmax=None: (_i32(N, T - skip), _f32(N, T - skip)), launch, lambda best, prob: (best, prob))
+
+
+def segments_op(n_classes, skip, threshold, cap):
+    Cn, thr, cap = int(n_classes), C.c_float(-1.0 if threshold is None else float(threshold)), int(cap)
+
+    def launch(dev, P, input_len, outs, tables, ws):
+        dev.call("mgr_greedy_segments", P, P.shape[0], P.shape[1], Cn, skip, thr, cap, *outs)
+    return DecodeOp("segments", lambda N, T, Lmax=None: (_i32(N), _i32(N, cap), _i32(N, cap, 2), _f32(N, cap)), launch,
+                    segments_from_arrays, hyp=(1, 0))
+
+
+def beam_op(n_classes, skip, beam_width=10, merge_repeated=True, blank=None, eps=1e-8):
+    Cn, W = int(n_classes), int(beam_width)
+    blank = Cn - 1 if blank is None else int(blank)
+
+    def launch(dev, P, input_len, outs, tables, ws):
+        dev.call("mgr_ctc_beam_search", P, input_len, P.shape[0], P.shape[1], Cn, skip, blank, W, C.c_float(eps),
+                 1 if merge_repeated else 0, *outs, ws, ws.nbytes)
+
+    def result(out, out_len, logp):
+        return [[int(v) for v in out[i, :out_len[i]]] for i in range(len(out_len))], logp
+    return DecodeOp("beam", lambda N, T, Lmax=None: (_i32(N, T - skip), _i32(N), _f64(N)), launch, result,
+                    ws_bytes=lambda lib, N, T, Lmax=None: lib.mgr_ctc_beam_ws_bytes(N, T, Cn, W), hyp=(0, 1), uses_len=True)
+
+
+def beam_lm_op(n_classes, skip, lm=None, lm_end=None, alpha=1.0, beta=0.0, beam_width=10, top_paths=1, eps=1e-8):
+    Cn, W, NP = int(n_classes), int(beam_width), int(top_paths)
+
+    def launch(dev, P, input_len, outs, tables, ws):
+        dev.call("mgr_ctc_beam_search_lm", P, input_len, P.shape[0], P.shape[1], Cn, skip, Cn - 1, W, C.c_float(eps), tables[0], tables[1],
+                 NP, *outs, ws, ws.nbytes)
+    return DecodeOp("beam_lm", lambda N, T, Lmax=None: (_i32(N, NP, T - skip), _i32(N, NP), _f64(N, NP), _f64(N, NP)), launch,
+                    lambda *arrays: nbest_from_arrays(*arrays, NP), tables=lm_tables(Cn, lm, lm_end, alpha, beta),
+                    ws_bytes=lambda lib, N, T, Lmax=None: lib.mgr_ctc_beam_lm_ws_bytes(N, T, Cn, W, NP),
+                    hyp=(0, 1), uses_len=True)         # (a length of -1 - no hypothesis - counts as 0 in mgr_edit_distance)
+
+
+def lexicon_op(n_classes, skip, lexicon, lm=None, lm_end=None, alpha=1.0, beta=0.0, cap=256, return_path=False, eps=1e-8):
+    Cn, cap = int(n_classes), int(cap)
+    off, words = compile_lexicon(lexicon, Cn)        # (host arrays: the library reads and checks them at every call)
+    G = len(off) - 1
+
+    def outputs(N, T, Lmax=None):
+        return (_i32(N), _i32(N, cap), _i32(N, cap, 2), _f32(N, cap), _i32(N, T - skip) if return_path else None, _f64(N), _f64(N))
+
+    def launch(dev, P, input_len, outs, tables, ws):
+        dev.call("mgr_ctc_lexicon_decode", P, input_len, P.shape[0], P.shape[1], Cn, skip, Cn - 1, C.c_float(eps), off.ctypes.data,
+                 words.ctypes.data, G, tables[0], tables[1], cap, *outs, ws, ws.nbytes)
+
+    def result(n, phr, seg, conf, *rest):           # (rest: [path, ]score, logp)
+        return (lexicon_from_arrays(n, phr, seg, conf), rest[-2], rest[-1]) + rest[:-2]
+    return DecodeOp("lexicon", outputs, launch, result, tables=phrase_lm_tables(G, lm, lm_end, alpha, beta),
+                    ws_bytes=lambda lib, N, T, Lmax=None: lib.mgr_ctc_lexicon_ws_bytes(N, T, Cn, G, off.ctypes.data), uses_len=True)
+
+
+def align_op(n_classes, skip, return_path=False, eps=1e-8):
+    Cn = int(n_classes)
+
+    def launch(dev, P, input_len, outs, tables, ws, labels, label_len):
+        dev.call("mgr_ctc_align", P, labels, input_len, label_len, P.shape[0], P.shape[1], Cn, labels.shape[1], skip, Cn - 1, C.c_float(eps),
+                 *outs, ws, ws.nbytes)
+
+    def result(path, seg, conf, logp, lab, ll):
+        clipped = np.clip(lab, 0, Cn - 1)     # (what the kernels align: out-of-range values clipped into the class range, as the loss)
+        return (alignment_from_arrays(clipped, ll, seg, conf, logp), logp) + ((path,) if return_path else ())
+    return DecodeOp("align", lambda N, T, Lmax: (_i32(N, T - skip), _i32(N, Lmax, 2), _f32(N, Lmax), _f64(N)), launch, result,
+                    ws_bytes=lambda lib, N, T, Lmax: lib.mgr_ctc_align_ws_bytes(N, T, Cn, Lmax), uses_len=True)
+
+
+def _posteriors(pred_out):
+    return np.ascontiguousarray(pred_out, dtype=np.float32)
+
+
+def _run(op, P, skip, dev, input_length=None, labels=()):
+    """One decode op on host posteriors P (N, T, C) float32: upload, allocate what the description says, launch, download, shape -
+    and free all of it, whatever happens.  labels: () or the (labels (N, Lmax), lengths (N,)) of pack_labels."""
+    dev = dev or default_device()
+    N, T = P.shape[:2]
+    Lmax = labels[0].shape[1] if labels else None
+    held = []
+
+    def keep(a):
+        held.append(a)
+        return a
+    try:
+        dP, dil = keep(dev.array(P)), None
+        if op.uses_len:
+            dil = keep(dev.array(np.full(N, T - skip, np.int32) if input_length is None else np.asarray(input_length).reshape(N).astype(np.int32)))
+        dlab = [keep(dev.array(a)) for a in labels]
+        tables = [t if t is None else keep(dev.array(t)) for t in op.tables]
+        outs = [o if o is None else keep(dev.empty(*o)) for o in op.outputs(N, T, Lmax)]
+        ws = keep(dev.bytes(op.ws_bytes(dev.lib, N, T, Lmax))) if op.ws_bytes else None
+        op.launch(dev, dP, dil, outs, tables, ws, *dlab)
+        return op.result(*[o.download() for o in outs if o is not None], *labels)
+    finally:
+        for a in held:
+            a.free()
+
+
+def _run_with_room(make_op, first, P, skip, dev, **kwargs):
+    """_run of make_op(cap) with room for `first` entries per sample, and again with room for T - skip - the most there can be - when a
+    sample has more: the device always reports the true count, and the op's *_from_arrays refuses it with OverflowError (any OverflowError
+    out of _run is taken for that one; what the second run raises is raised).  The second run is a whole _run - P uploaded, the lexicon
+    compiled, every buffer allocated again: more than reallocating the outputs would cost, but rare (more than `first` in a sample)."""
+    room = P.shape[1] - skip
+    cap = max(1, min(room, int(first)))
+    try:
+        return _run(make_op(cap), P, skip, dev, **kwargs)
+    except OverflowError:
+        if cap >= room:
+            raise
+        return _run(make_op(room), P, skip, dev, **kwargs)
+
+
 def frame_argmax(pred_out, skip=2, dev=None):
     """(N,T,C) float32 softmax -> best (N,T-skip) int32, prob (N,T-skip) float32, computed on the GPU."""
-    dev = dev or default_device()
-    P = np.ascontiguousarray(pred_out, dtype=np.float32)
-    N, T, Cn = P.shape
-    dP = dev.array(P)
-    best = dev.empty((N, T - skip), np.int32)
-    prob = dev.empty((N, T - skip), np.float32)
-    dev.call("mgr_frame_argmax", dP, N, T, Cn, skip, best, prob)
-    out = best.download(), prob.download()
-    for a in (dP, best, prob):
-        a.free()
-    return out
+    P = _posteriors(pred_out)
+    return _run(argmax_op(P.shape[2], skip), P, skip, dev)
 
 
 def confidence_filter_collapse(best, prob, thr):
@@ -102,28 +242,8 @@ def greedy_segments(pred_out, thr, skip=2, dev=None, max_segments=256):
     first and last surviving frame, and the mean of the frame maxima over its surviving frames.  The labels are those of
     greedy_decode(pred_out, thr, skip).  max_segments sizes the first download; a sample with more runs (the device always reports the
     true count) makes the call run again with room for T - skip."""
-    dev = dev or default_device()
-    P = np.ascontiguousarray(pred_out, dtype=np.float32)
-    N, T, Cn = P.shape
-    dP = dev.array(P)
-    dn = dev.empty((N,), np.int32)
-    try:
-        cap = max(1, min(T - skip, int(max_segments)))
-        while True:
-            dl, ds, dc = dev.empty((N, cap), np.int32), dev.empty((N, cap, 2), np.int32), dev.empty((N, cap), np.float32)
-            dev.call("mgr_greedy_segments", dP, N, T, Cn, skip, C.c_float(-1.0 if thr is None else float(thr)), cap, dn, dl, ds, dc)
-            n = dn.download()
-            if int(n.max()) <= cap:
-                lab, seg, conf = dl.download(), ds.download(), dc.download()
-            for a in (dl, ds, dc):
-                a.free()
-            if int(n.max()) <= cap:
-                break
-            cap = T - skip
-    finally:
-        dP.free()
-        dn.free()
-    return segments_from_arrays(n, lab, seg, conf)
+    P = _posteriors(pred_out)
+    return _run_with_room(lambda cap: segments_op(P.shape[2], skip, thr, cap), max_segments, P, skip, dev)
 
 
 def segments_from_arrays(n, lab, seg, conf):
@@ -170,50 +290,18 @@ def forced_align(pred_out, labels, label_length=None, input_length=None, skip=2,
     probability of the path (-inf and no segments where the labels do not fit the input length); path (N, T - skip) int32, the class
     emitted at every frame (-1 past the input length).  A CTC-trained network emits short spikes: the frames are where the network
     commits to the gesture, not the extent of the movement."""
-    dev = dev or default_device()
-    P = np.ascontiguousarray(pred_out, dtype=np.float32)
-    N, T, Cn = P.shape
+    P = _posteriors(pred_out)
     lab, ll = pack_labels(labels, label_length)
-    if lab.shape[0] != N:
-        raise ValueError("%d label rows for %d samples" % (lab.shape[0], N))
-    il = np.full(N, T - skip, np.int32) if input_length is None else np.asarray(input_length).reshape(N).astype(np.int32)
-    Lmax = lab.shape[1]
-    dP, dlab, dil, dll = dev.array(P), dev.array(lab), dev.array(il), dev.array(ll)
-    dpath, dseg = dev.empty((N, T - skip), np.int32), dev.empty((N, Lmax, 2), np.int32)
-    dconf, dlogp = dev.empty((N, Lmax), np.float32), dev.empty((N,), np.float64)
-    ws = dev.bytes(dev.lib.mgr_ctc_align_ws_bytes(N, T, Cn, Lmax))
-    try:
-        dev.call("mgr_ctc_align", dP, dlab, dil, dll, N, T, Cn, Lmax, skip, Cn - 1, C.c_float(eps), dpath, dseg, dconf, dlogp, ws, ws.nbytes)
-        seg, conf, logp = dseg.download(), dconf.download(), dlogp.download()
-        path = dpath.download() if return_path else None
-    finally:
-        for a in (dP, dlab, dil, dll, dpath, dseg, dconf, dlogp, ws):
-            a.free()
-    clipped = np.clip(lab, 0, Cn - 1)     # (what the kernels align: out-of-range values clipped into the class range, as the loss)
-    segs = alignment_from_arrays(clipped, ll, seg, conf, logp)
-    return (segs, logp, path) if return_path else (segs, logp)
+    if lab.shape[0] != P.shape[0]:
+        raise ValueError("%d label rows for %d samples" % (lab.shape[0], P.shape[0]))
+    return _run(align_op(P.shape[2], skip, return_path, eps), P, skip, dev, input_length, (lab, ll))
 
 
 def beam_search_decode(pred_out, input_length=None, beam_width=10, skip=2, merge_repeated=True, dev=None, blank=None):
     """K.ctc_decode(greedy=False, beam_width) equivalent on the GPU (BASELINE.json config 5).  blank: the blank's class, the last
     one (Keras') by default."""
-    dev = dev or default_device()
-    P = np.ascontiguousarray(pred_out, dtype=np.float32)
-    N, T, Cn = P.shape
-    if input_length is None:
-        input_length = np.full(N, T - skip)
-    il = np.asarray(input_length).reshape(N).astype(np.int32)
-    dP, dil = dev.array(P), dev.array(il)
-    out = dev.empty((N, T - skip), np.int32)
-    olen = dev.empty((N,), np.int32)
-    logp = dev.empty((N,), np.float64)
-    ws = dev.bytes(dev.lib.mgr_ctc_beam_ws_bytes(N, T, Cn, beam_width))
-    dev.call("mgr_ctc_beam_search", dP, dil, N, T, Cn, skip, Cn - 1 if blank is None else int(blank), int(beam_width), C.c_float(1e-8),
-             1 if merge_repeated else 0, out, olen, logp, ws, ws.nbytes)
-    o, l, s = out.download(), olen.download(), logp.download()
-    for a in (dP, dil, out, olen, logp, ws):
-        a.free()
-    return [[int(v) for v in o[i, :l[i]]] for i in range(N)], s
+    P = _posteriors(pred_out)
+    return _run(beam_op(P.shape[2], skip, beam_width, merge_repeated, blank), P, skip, dev, input_length)
 
 
 def bigram_lm(label_seqs, n_classes, blank=None, add_k=1.0):
@@ -293,29 +381,8 @@ def beam_search_lm_decode(pred_out, lm=None, lm_end=None, alpha=1.0, beta=0.0, i
     them; -inf entries forbid a transition.  Returns (paths, score, logp_ctc): with top_paths = 1 a label list per sample and two (N,)
     float64 arrays - the ranking score and the network's part of it -, otherwise per sample the ranked list of its at most top_paths
     hypotheses and (N, top_paths) arrays, -inf where fewer survive."""
-    dev = dev or default_device()
-    P = np.ascontiguousarray(pred_out, dtype=np.float32)
-    N, T, Cn = P.shape
-    ext, fin = lm_tables(Cn, lm, lm_end, alpha, beta)
-    W, NP = int(beam_width), int(top_paths)
-    il = np.full(N, T - skip, np.int32) if input_length is None else np.asarray(input_length).reshape(N).astype(np.int32)
-    bufs = [dev.array(P), dev.array(il), dev.array(ext)]
-    try:
-        if fin is not None:
-            bufs.append(dev.array(fin))
-        dfin = bufs[3] if fin is not None else None
-        out, olen = dev.empty((N, NP, T - skip), np.int32), dev.empty((N, NP), np.int32)
-        score, logp = dev.empty((N, NP), np.float64), dev.empty((N, NP), np.float64)
-        bufs += [out, olen, score, logp]
-        ws = dev.bytes(dev.lib.mgr_ctc_beam_lm_ws_bytes(N, T, Cn, W, NP))
-        bufs.append(ws)
-        dev.call("mgr_ctc_beam_search_lm", bufs[0], bufs[1], N, T, Cn, skip, Cn - 1, W, C.c_float(1e-8), bufs[2], dfin, NP, out, olen,
-                 score, logp, ws, ws.nbytes)
-        res = nbest_from_arrays(out.download(), olen.download(), score.download(), logp.download(), NP)
-    finally:
-        for a in bufs:
-            a.free()
-    return res
+    P = _posteriors(pred_out)
+    return _run(beam_lm_op(P.shape[2], skip, lm, lm_end, alpha, beta, beam_width, top_paths), P, skip, dev, input_length)
 
 
 # ---- lexicon-constrained decode (K13, DESIGN 9i): phrase sequences from word posteriors -----------------------------------------
@@ -386,41 +453,9 @@ def lexicon_decode(pred_out, lexicon, lm=None, lm_end=None, alpha=1.0, beta=0.0,
     table terms, logp (N,) float64 the network's part, path (N, T - skip) int32 the class emitted per frame (-1 past input_length).
     A sample for which no sequence has a finite score has no segments and -inf scores.  max_phrases sizes the first download; a sample
     with more phrases (the device reports the true count) makes the call run again with room for T - skip."""
-    dev = dev or default_device()
-    P = np.ascontiguousarray(pred_out, dtype=np.float32)
-    N, T, Cn = P.shape
-    off, words = compile_lexicon(lexicon, Cn)
-    G = len(off) - 1
-    ext, fin = phrase_lm_tables(G, lm, lm_end, alpha, beta)
-    il = np.full(N, T - skip, np.int32) if input_length is None else np.asarray(input_length).reshape(N).astype(np.int32)
-    bufs = [dev.array(P), dev.array(il), dev.array(ext)]
-    try:
-        dfin = None
-        if fin is not None:
-            dfin = dev.array(fin)
-            bufs.append(dfin)
-        dn, dscore, dlogp = dev.empty((N,), np.int32), dev.empty((N,), np.float64), dev.empty((N,), np.float64)
-        dpath = dev.empty((N, T - skip), np.int32) if return_path else None
-        ws = dev.bytes(dev.lib.mgr_ctc_lexicon_ws_bytes(N, T, Cn, G, off.ctypes.data))
-        bufs += [dn, dscore, dlogp, ws] + ([dpath] if return_path else [])
-        cap = max(1, min(T - skip, int(max_phrases)))
-        while True:
-            dp, ds, dc = dev.empty((N, cap), np.int32), dev.empty((N, cap, 2), np.int32), dev.empty((N, cap), np.float32)
-            bufs += [dp, ds, dc]
-            dev.call("mgr_ctc_lexicon_decode", bufs[0], bufs[1], N, T, Cn, skip, Cn - 1, C.c_float(eps), off.ctypes.data, words.ctypes.data,
-                     G, bufs[2], dfin, cap, dn, dp, ds, dc, dpath, dscore, dlogp, ws, ws.nbytes)
-            n = dn.download()
-            if int(n.max()) <= cap:
-                break
-            cap = T - skip
-        segs = lexicon_from_arrays(n, dp.download(), ds.download(), dc.download())
-        res = (segs, dscore.download(), dlogp.download())
-        if return_path:
-            res += (dpath.download(),)
-    finally:
-        for a in bufs:
-            a.free()
-    return res
+    P = _posteriors(pred_out)
+    make = lambda cap: lexicon_op(P.shape[2], skip, lexicon, lm, lm_end, alpha, beta, cap, return_path, eps)
+    return _run_with_room(make, max_phrases, P, skip, dev, input_length=input_length)
 
 
 def decode_lexicon_mlf(pred_out, f_list, lexicon, names, ignore_list, name_fmt, out_file, **kwargs):

@@ -12,7 +12,7 @@ import math
 
 import numpy as np
 
-from . import _capi
+from . import _capi, decoding
 from ._capi import Device, DeviceArray
 from .spec import frontend_layers, input_width
 
@@ -1004,6 +1004,20 @@ class Engine:
     EV_OUT = (50, 51)     # the result of the batch in output slot 0 / 1 has reached its pinned host buffer
     EV_D1P = (55, 56)     # the depth-1 projections into depth-1 Z set 0 / 1 are done (stream 0)
     EV_D1S = (57, 58)     # the depth-1 scans that read depth-1 Z set 0 / 1 are done (stream ES)
+    LABELLED = ("loss", "align", "score")     # the predict_stream outputs whose batches come with labels (a training engine)
+
+    def decode_ops(self, beam_width=10, merge_repeated=True, threshold=None, top_paths=1, lexicon=None, **lm_args):
+        """predict_stream's decode outputs: name -> what builds decoding's description of its kernel with this engine's classes, frames
+        and eps (nothing is validated before that is called).  Room for T - skip runs / phrases per sample, the most there can be: the
+        count the kernel reports never exceeds what is downloaded."""
+        Cn, skip, eps = self.spec.num_classes, int(self.spec.ctc["skip"]), float(self.spec.ctc["eps"])
+        room = self.T - skip
+        return {"argmax": lambda: decoding.argmax_op(Cn, skip),
+                "segments": lambda: decoding.segments_op(Cn, skip, threshold, room),
+                "beam": lambda: decoding.beam_op(Cn, skip, beam_width, merge_repeated, eps=eps),
+                "beam_lm": lambda: decoding.beam_lm_op(Cn, skip, beam_width=beam_width, top_paths=top_paths, eps=eps, **lm_args),
+                "lexicon": lambda: decoding.lexicon_op(Cn, skip, lexicon, cap=room, eps=eps, **lm_args),
+                "align": lambda: decoding.align_op(Cn, skip, return_path=True, eps=eps)}
 
     def predict_stream(self, batches, output="posteriors", train_phase=False, beam_width=10, merge_repeated=True, threshold=None,
                        lm=None, lm_end=None, alpha=1.0, beta=0.0, top_paths=1, decode="greedy", ignore=None, costs=(1, 1, 1), lexicon=None):
@@ -1041,16 +1055,15 @@ class Engine:
                         travel to the host, no label sequence does (a training engine, like "loss")
         Results are bit-identical to the one-batch-at-a-time calls (predict / loss_on_batch): same kernels, same order per batch."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
-        Cn, skip = sp.num_classes, int(sp.ctc["skip"])
-        if output not in ("posteriors", "argmax", "beam", "beam_lm", "lexicon", "loss", "segments", "align", "score"):
+        Cn, skip, eps = sp.num_classes, int(sp.ctc["skip"]), float(sp.ctc["eps"])
+        # ("score" decodes one path; top_paths is read for "beam_lm" alone)
+        ops = self.decode_ops(beam_width, merge_repeated, threshold, top_paths if output == "beam_lm" else 1, lexicon,
+                               lm=lm, lm_end=lm_end, alpha=alpha, beta=beta)
+        if output not in ("posteriors", "loss", "score") + tuple(ops):
             raise ValueError("unknown output %r" % (output,))
-        if output == "loss" and self.inference_only:
-            raise ValueError("output='loss' needs a training engine (labels, CTC workspace)")
-        if output == "align" and self.inference_only:
-            raise ValueError("output='align' needs a training engine (labels)")
-        if output == "score" and self.inference_only:
-            raise ValueError("output='score' needs a training engine (labels, CTC workspace)")
-        labelled = output in ("loss", "align", "score")
+        labelled = output in self.LABELLED
+        if labelled and self.inference_only:
+            raise ValueError("output=%r needs a training engine (labels%s)" % (output, "" if output == "align" else ", CTC workspace"))
         self._bind()
         if self._prefetched is not None:     # a pipelined training encoder pass is in flight: let it finish, then discard it
             dev.wait(0, self.ES)
@@ -1065,160 +1078,70 @@ class Engine:
                 st[key] = make()
             return st[key]
 
+        def sets(n, make, shapes):
+            return [tuple(make(*s) for s in shapes) for _ in range(n)]
+
         # two P buffers: the decode kernels / the download of batch n read one on their own stream while the head of batch n + 1
         # writes the other
         pring = bufs("pring", lambda: [self.P, self.mem.empty((B, T, Cn))])
-        if output == "posteriors":
-            pins = bufs("P", lambda: [dev.pinned((B, T, Cn), np.float32) for _ in range(2)])
-        elif output == "argmax":
-            dbest = bufs("dbest", lambda: self.mem.empty((B, T - skip), np.int32))
-            dprob = bufs("dprob", lambda: self.mem.empty((B, T - skip), np.float32))
-            pins = bufs("am", lambda: [(dev.pinned((B, T - skip), np.int32), dev.pinned((B, T - skip), np.float32)) for _ in range(2)])
-        elif output == "beam":
-            dil = bufs("dil", lambda: self.mem.empty((B,), np.int32))
-            dil.upload(np.full(B, T - skip, np.int32))
-            dout = bufs("dout", lambda: self.mem.empty((B, T - skip), np.int32))
-            dlen = bufs("dlen", lambda: self.mem.empty((B,), np.int32))
-            dlogp = bufs("dlogp", lambda: self.mem.empty((B,), np.float64))
-            wsb = bufs("wsb%d" % beam_width, lambda: self.mem.bytes(self.lib.mgr_ctc_beam_ws_bytes(B, T, Cn, int(beam_width))))
-            pins = bufs("beam", lambda: [(dev.pinned((B, T - skip), np.int32), dev.pinned((B,), np.int32), dev.pinned((B,), np.float64))
-                                         for _ in range(2)])
-        elif output == "beam_lm":
-            from .decoding import lm_tables
-            NP = int(top_paths)
-            if not 1 <= NP <= int(beam_width):          # (before anything is allocated for it; the library checks again)
-                raise ValueError("top_paths %d out of [1, beam_width = %d]" % (NP, int(beam_width)))
-            ext, fin = lm_tables(Cn, lm, lm_end, alpha, beta)
-            dil = bufs("dil", lambda: self.mem.empty((B,), np.int32))
-            dil.upload(np.full(B, T - skip, np.int32))
-            dext = bufs("lm_ext", lambda: self.mem.empty((Cn + 1, Cn), np.float64))
-            dext.upload(ext)
-            dfin = None
-            if fin is not None:
-                dfin = bufs("lm_fin", lambda: self.mem.empty((Cn + 1,), np.float64))
-                dfin.upload(fin)
-            dnb = bufs("dnb%d" % NP, lambda: (self.mem.empty((B, NP, T - skip), np.int32), self.mem.empty((B, NP), np.int32),
-                                              self.mem.empty((B, NP), np.float64), self.mem.empty((B, NP), np.float64)))
-            wsb = bufs("wsl%d_%d" % (beam_width, NP),
-                       lambda: self.mem.bytes(self.lib.mgr_ctc_beam_lm_ws_bytes(B, T, Cn, int(beam_width), NP)))
-            pins = bufs("beam_lm%d" % NP, lambda: [(dev.pinned((B, NP, T - skip), np.int32), dev.pinned((B, NP), np.int32),
-                                                    dev.pinned((B, NP), np.float64), dev.pinned((B, NP), np.float64)) for _ in range(2)])
-        elif output == "lexicon":
-            from .decoding import compile_lexicon, phrase_lm_tables
-            if lexicon is None:
-                raise ValueError("output='lexicon' needs a lexicon")
-            loff, lwords = compile_lexicon(lexicon, Cn)        # (host arrays: the library reads and checks them at every call)
-            G = len(loff) - 1
-            ext, fin = phrase_lm_tables(G, lm, lm_end, alpha, beta)
-            dil = bufs("dil", lambda: self.mem.empty((B,), np.int32))
-            dil.upload(np.full(B, T - skip, np.int32))
-            dext = bufs("lex_ext%d" % G, lambda: self.mem.empty((G + 1, G), np.float64))
-            dext.upload(ext)
-            dfin = None
-            if fin is not None:
-                dfin = bufs("lex_fin%d" % G, lambda: self.mem.empty((G + 1,), np.float64))
-                dfin.upload(fin)
-            cap = T - skip      # a phrase takes a frame at least: the count the kernel reports never exceeds what is downloaded
-            dlex = bufs("dlex", lambda: (self.mem.empty((B,), np.int32), self.mem.empty((B, cap), np.int32), self.mem.empty((B, cap, 2), np.int32),
-                                         self.mem.empty((B, cap), np.float32), self.mem.empty((B,), np.float64), self.mem.empty((B,), np.float64)))
-            wsx = bufs("wslex%d_%d" % (G, len(lwords)), lambda: self.mem.bytes(self.lib.mgr_ctc_lexicon_ws_bytes(B, T, Cn, G, loff.ctypes.data)))
-            pins = bufs("lexicon", lambda: [(dev.pinned((B,), np.int32), dev.pinned((B, cap), np.int32), dev.pinned((B, cap, 2), np.int32),
-                                             dev.pinned((B, cap), np.float32), dev.pinned((B,), np.float64), dev.pinned((B,), np.float64))
-                                            for _ in range(2)])
-        elif output == "segments":
-            # room for T - skip runs per sample, the most there can be: the count the kernel reports never exceeds what is downloaded
-            cap = T - skip
-            dseg = bufs("dseg", lambda: (self.mem.empty((B,), np.int32), self.mem.empty((B, cap), np.int32),
-                                         self.mem.empty((B, cap, 2), np.int32), self.mem.empty((B, cap), np.float32)))
-            pins = bufs("seg", lambda: [(dev.pinned((B,), np.int32), dev.pinned((B, cap), np.int32), dev.pinned((B, cap, 2), np.int32),
-                                         dev.pinned((B, cap), np.float32)) for _ in range(2)])
-        elif output == "align":
-            Lm = self.Lmax
-            # one set of device outputs per output slot, like the losses below
-            aring = bufs("aring", lambda: [(self.mem.empty((B, T - skip), np.int32), self.mem.empty((B, Lm, 2), np.int32),
-                                            self.mem.empty((B, Lm), np.float32), self.mem.empty((B,), np.float64)) for _ in range(2)])
-            wsa = bufs("wsa", lambda: self.mem.bytes(self.lib.mgr_ctc_align_ws_bytes(B, T, Cn, Lm)))
-            pins = bufs("align", lambda: [(dev.pinned((B, T - skip), np.int32), dev.pinned((B, Lm, 2), np.int32),
-                                           dev.pinned((B, Lm), np.float32), dev.pinned((B,), np.float64)) for _ in range(2)])
-            host_labels = {}
-        elif output == "score":
-            from .decoding import EDIT_MAX_LEN, check_costs, ignore_mask, lm_tables
-            if decode not in ("greedy", "beam", "beam_lm"):
+        name = {"greedy": "segments", "beam": "beam", "beam_lm": "beam_lm"}.get(decode) if output == "score" else output
+        if output == "score":
+            if name is None:
                 raise ValueError("unknown decode %r for output='score'" % (decode,))
-            if T - skip > EDIT_MAX_LEN or self.Lmax > EDIT_MAX_LEN:
-                raise ValueError("T - skip = %d or Lmax = %d above the %d labels mgr_edit_distance compares" % (T - skip, self.Lmax, EDIT_MAX_LEN))
-            ecosts = check_costs(costs)
-            emask = ignore_mask((Cn - 1,) if ignore is None else ignore)
-            # the decode kernels' device outputs: the buffers of the matching outputs above (one set: decode, comparison and copies of
-            # a batch are consecutive on the output stream); the losses in two slots, as below
-            if decode == "greedy":
-                cap = T - skip
-                dseg = bufs("dseg", lambda: (self.mem.empty((B,), np.int32), self.mem.empty((B, cap), np.int32),
-                                             self.mem.empty((B, cap, 2), np.int32), self.mem.empty((B, cap), np.float32)))
-                hyp_d, hyplen_d = dseg[1], dseg[0]
-            else:
-                dil = bufs("dil", lambda: self.mem.empty((B,), np.int32))
-                dil.upload(np.full(B, T - skip, np.int32))
-                if decode == "beam":
-                    dout = bufs("dout", lambda: self.mem.empty((B, T - skip), np.int32))
-                    dlen = bufs("dlen", lambda: self.mem.empty((B,), np.int32))
-                    dlogp = bufs("dlogp", lambda: self.mem.empty((B,), np.float64))
-                    wsb = bufs("wsb%d" % beam_width, lambda: self.mem.bytes(self.lib.mgr_ctc_beam_ws_bytes(B, T, Cn, int(beam_width))))
-                    hyp_d, hyplen_d = dout, dlen
-                else:
-                    NP = 1
-                    ext, fin = lm_tables(Cn, lm, lm_end, alpha, beta)
-                    dext = bufs("lm_ext", lambda: self.mem.empty((Cn + 1, Cn), np.float64))
-                    dext.upload(ext)
-                    dfin = None
-                    if fin is not None:
-                        dfin = bufs("lm_fin", lambda: self.mem.empty((Cn + 1,), np.float64))
-                        dfin.upload(fin)
-                    dnb = bufs("dnb%d" % NP, lambda: (self.mem.empty((B, NP, T - skip), np.int32), self.mem.empty((B, NP), np.int32),
-                                                      self.mem.empty((B, NP), np.float64), self.mem.empty((B, NP), np.float64)))
-                    wsb = bufs("wsl%d_%d" % (beam_width, NP),
-                               lambda: self.mem.bytes(self.lib.mgr_ctc_beam_lm_ws_bytes(B, T, Cn, int(beam_width), NP)))
-                    hyp_d, hyplen_d = dnb[0], dnb[1]      # (a length of -1 - no hypothesis - is clipped to 0 by the comparison)
-            dscore = bufs("dscore", lambda: (self.mem.empty((B,), np.int32), self.mem.empty((B, 4), np.int32), self.mem.empty((B, 2), np.int32)))
-            lring = bufs("lring", lambda: [self.loss_b, self.mem.empty((B,))])
-            pins = bufs("score", lambda: [(dev.pinned((B,), np.float32), dev.pinned((B,), np.int32), dev.pinned((B, 4), np.int32),
-                                           dev.pinned((B, 2), np.int32)) for _ in range(2)])
-        else:
-            pins = bufs("loss", lambda: [dev.pinned((B,), np.float32) for _ in range(2)])
+            if T - skip > decoding.EDIT_MAX_LEN or self.Lmax > decoding.EDIT_MAX_LEN:
+                raise ValueError("T - skip = %d or Lmax = %d above the %d labels mgr_edit_distance compares"
+                                 % (T - skip, self.Lmax, decoding.EDIT_MAX_LEN))
+            ecosts = decoding.check_costs(costs)
+            emask = decoding.ignore_mask((Cn - 1,) if ignore is None else ignore)
+        elif output == "beam_lm" and not 1 <= int(top_paths) <= int(beam_width):          # (before anything is allocated for it; the library checks again)
+            raise ValueError("top_paths %d out of [1, beam_width = %d]" % (int(top_paths), int(beam_width)))
+        elif output == "lexicon" and lexicon is None:
+            raise ValueError("output='lexicon' needs a lexicon")
+        op, host_labels = None, {}
+        if name in ops:
+            # The op's device outputs, workspace and tables, each cached under what sizes it - so "segments" and "score" with the greedy
+            # decode, or "beam_lm" and "score" at one path, share them.  One set of outputs: decode, comparison and copies of a batch are
+            # consecutive on the output stream - but two for "align", which runs on stream 0: one per output slot, like the losses below
+            op = ops[name]()
+            shapes = op.outputs(B, T, self.Lmax)
+            dring = bufs((name, "out", shapes), lambda: [tuple(sh if sh is None else self.mem.empty(*sh) for sh in shapes)
+                                                        for _ in range(2 if name == "align" else 1)])
+            nbytes = op.ws_bytes(self.lib, B, T, self.Lmax) if op.ws_bytes else None
+            ws = None if nbytes is None else bufs((name, "ws", nbytes), lambda: self.mem.bytes(nbytes))
+            # (the tables are uploaded once per call, not per batch)
+            tables = [t if t is None else bufs((name, "table", k, t.shape), lambda: self.mem.empty(t.shape, t.dtype)).upload(t)
+                      for k, t in enumerate(op.tables)]
+            dil = None          # ("align" reads the lengths that came with the labels)
+            if op.uses_len and name != "align":
+                dil = bufs("dil", lambda: self.mem.empty((B,), np.int32)).upload(np.full(B, T - skip, np.int32))
+        # per output slot o: the pinned arrays a result arrives in, and the device arrays src(o) they are copied from
+        if output == "posteriors":
+            pins, src = bufs("P", lambda: sets(2, dev.pinned, [((B, T, Cn), np.float32)])), lambda o: (pring[o],)
+        elif output in ("loss", "score"):
             # one device buffer per output slot, like pring: batch i's copy (its own stream, behind EV_FUSED only) must not find
             # batch i + 1's losses in the buffer - stream 0 waits for EV_OUT[o] of batch i - 2 before it reuses slot o
             lring = bufs("lring", lambda: [self.loss_b, self.mem.empty((B,))])
+            dscore = ()
+            if output == "score":
+                dscore = bufs("dscore", lambda: sets(1, self.mem.empty, [((B,), np.int32), ((B, 4), np.int32), ((B, 2), np.int32)]))[0]
+            pins = bufs(output, lambda: sets(2, dev.pinned, [((B,), np.float32)] + [(d.shape, d.dtype) for d in dscore]))
+            src = lambda o: (lring[o],) + dscore
+        else:
+            pins = bufs((name, "pinned", shapes), lambda: sets(2, dev.pinned, [sh for sh in shapes if sh is not None]))
+            src = lambda o: [d for d in dring[o % len(dring)] if d is not None]     # (the one set, or "align"'s set of slot o)
 
         spin = bufs("status16", lambda: [dev.pinned((16,), np.uint32) for _ in range(2)])
 
         def collect(i):
             o = i & 1
             dev.event_sync(self.EV_OUT[o])
-            if output == "posteriors":
-                r = pins[o].copy()
-            elif output == "argmax":
-                r = (pins[o][0].copy(), pins[o][1].copy())
-            elif output == "beam":
-                po, pl, ps = pins[o]
-                r = ([[int(v) for v in po[b, :pl[b]]] for b in range(B)], ps.copy())
-            elif output == "beam_lm":
-                from .decoding import nbest_from_arrays
-                r = nbest_from_arrays(*pins[o], NP)
-            elif output == "lexicon":
-                from .decoding import lexicon_from_arrays
-                r = (lexicon_from_arrays(*pins[o][:4]), pins[o][4].copy(), pins[o][5].copy())
-            elif output == "segments":
-                from .decoding import segments_from_arrays
-                r = segments_from_arrays(*pins[o])
-            elif output == "align":
-                from .decoding import alignment_from_arrays
-                lab, ll = host_labels.pop(i)
-                ppath, pseg, pconf, plogp = pins[o]
-                r = (alignment_from_arrays(np.clip(lab, 0, Cn - 1), ll, pseg, pconf, plogp), plogp.copy(), ppath.copy())
-            elif output == "score":
-                r = tuple(a.copy() for a in pins[o])
+            if output in ops:
+                r = op.result(*pins[o], *host_labels.pop(i, ()))
             else:
-                r = pins[o].copy()
+                r = pins[o] if output == "score" else pins[o][0]
+            # the pinned buffers are reused two batches later: every array handed out is a copy (the lists hold Python numbers)
+            own = lambda m: m.copy() if isinstance(m, np.ndarray) else m
+            r = tuple(own(m) for m in r) if isinstance(r, tuple) else own(r)
             # the status block of THIS batch's pass travels with its result (no extra synchronisation): the samples whose hidden
             # state went NaN / Inf in it get NaN scores and no labels - not plausible numbers, and not every later batch
             return self._end_pass(spin[o].copy(), r, what="batch %d of the pipelined run" % i)
@@ -1326,73 +1249,27 @@ class Engine:
                 self._bind(self._pass_status[o])        # (batch i + 1's encoder pass, enqueued above, bound the other block)
                 self._enqueue_fusion_head(train_phase, None, ring[f], self.rng_step + (i - started[0]))
                 dev.stream(0)
-                if output == "loss":
+                if output == "align":
+                    op.launch(dev, self.P, self.ilen_d, dring[o], tables, ws, self.labels_d, self.llen_d)
+                elif labelled:
                     dev.call("mgr_ctc_loss_grad", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1,
-                             float(sp.ctc["eps"]), 1.0, lring[o], 0, self.ws_ctc, self.ws_ctc.nbytes)
+                             eps, 1.0, lring[o], 0, self.ws_ctc, self.ws_ctc.nbytes)
+                if output in ("loss", "align"):       # ("score" reads the labels again on the output stream below)
                     dev.record(self.EV_LAB[self._lab_slot])
                     self._lab_user[self._lab_slot] = 1 << 60
-                elif output == "align":
-                    dev.call("mgr_ctc_align", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1,
-                             C.c_float(float(sp.ctc["eps"])), *aring[o], wsa, wsa.nbytes)
-                    dev.record(self.EV_LAB[self._lab_slot])
-                    self._lab_user[self._lab_slot] = 1 << 60
-                elif output == "score":
-                    dev.call("mgr_ctc_loss_grad", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1,
-                             float(sp.ctc["eps"]), 1.0, lring[o], 0, self.ws_ctc, self.ws_ctc.nbytes)
-                    ref_d, reflen_d, lab_slot = self.labels_d, self.llen_d, self._lab_slot     # (read again on the output stream below)
                 dev.record(self.EV_FUSED[f])
                 # ---- decode kernels and the way back to pinned host memory: their own stream, beside batch i + 1's fusion layer
                 dev.stream(OUT)
                 dev.wait_event(OUT, self.EV_FUSED[f])
-                if output == "posteriors":
-                    dev.d2h_async(pins[o], pring[o])
-                elif output == "argmax":
-                    dev.call("mgr_frame_argmax", pring[o], B, T, Cn, skip, dbest, dprob)
-                    dev.d2h_async(pins[o][0], dbest)
-                    dev.d2h_async(pins[o][1], dprob)
-                elif output == "beam":
-                    dev.call("mgr_ctc_beam_search", pring[o], dil, B, T, Cn, skip, Cn - 1, int(beam_width), C.c_float(float(sp.ctc["eps"])),
-                             1 if merge_repeated else 0, dout, dlen, dlogp, wsb, wsb.nbytes)
-                    dev.d2h_async(pins[o][0], dout)
-                    dev.d2h_async(pins[o][1], dlen)
-                    dev.d2h_async(pins[o][2], dlogp)
-                elif output == "beam_lm":
-                    dev.call("mgr_ctc_beam_search_lm", pring[o], dil, B, T, Cn, skip, Cn - 1, int(beam_width), C.c_float(float(sp.ctc["eps"])),
-                             dext, dfin, NP, *dnb, wsb, wsb.nbytes)
-                    for k in range(4):
-                        dev.d2h_async(pins[o][k], dnb[k])
-                elif output == "lexicon":
-                    dev.call("mgr_ctc_lexicon_decode", pring[o], dil, B, T, Cn, skip, Cn - 1, C.c_float(float(sp.ctc["eps"])),
-                             loff.ctypes.data, lwords.ctypes.data, G, dext, dfin, cap, *dlex[:4], None, dlex[4], dlex[5], wsx, wsx.nbytes)
-                    for k in range(6):
-                        dev.d2h_async(pins[o][k], dlex[k])
-                elif output == "segments":
-                    dev.call("mgr_greedy_segments", pring[o], B, T, Cn, skip, C.c_float(-1.0 if threshold is None else float(threshold)),
-                             cap, *dseg)
-                    for k in range(4):
-                        dev.d2h_async(pins[o][k], dseg[k])
-                elif output == "align":
-                    for k in range(4):
-                        dev.d2h_async(pins[o][k], aring[o][k])
-                elif output == "score":
-                    if decode == "greedy":
-                        dev.call("mgr_greedy_segments", pring[o], B, T, Cn, skip, C.c_float(-1.0 if threshold is None else float(threshold)),
-                                 cap, *dseg)
-                    elif decode == "beam":
-                        dev.call("mgr_ctc_beam_search", pring[o], dil, B, T, Cn, skip, Cn - 1, int(beam_width), C.c_float(float(sp.ctc["eps"])),
-                                 1 if merge_repeated else 0, dout, dlen, dlogp, wsb, wsb.nbytes)
-                    else:
-                        dev.call("mgr_ctc_beam_search_lm", pring[o], dil, B, T, Cn, skip, Cn - 1, int(beam_width),
-                                 C.c_float(float(sp.ctc["eps"])), dext, dfin, NP, *dnb, wsb, wsb.nbytes)
-                    dev.call("mgr_edit_distance", hyp_d, hyplen_d, B, T - skip, ref_d, reflen_d, B, self.Lmax, None, None, B, ecosts[0],
-                             ecosts[1], ecosts[2], emask, dscore[0], dscore[1], dscore[2], None, None, None, 0)
-                    dev.record(self.EV_LAB[lab_slot])        # the labels' last reader of this batch is on this stream
-                    self._lab_user[lab_slot] = 1 << 60
-                    dev.d2h_async(pins[o][0], lring[o])
-                    for k in range(3):
-                        dev.d2h_async(pins[o][k + 1], dscore[k])
-                else:
-                    dev.d2h_async(pins[o], lring[o])
+                if op is not None and output != "align":
+                    op.launch(dev, pring[o], dil, dring[0], tables, ws)
+                if output == "score":
+                    dev.call("mgr_edit_distance", dring[0][op.hyp[0]], dring[0][op.hyp[1]], B, T - skip, self.labels_d, self.llen_d, B, self.Lmax,
+                             None, None, B, ecosts[0], ecosts[1], ecosts[2], emask, dscore[0], dscore[1], dscore[2], None, None, None, 0)
+                    dev.record(self.EV_LAB[self._lab_slot])        # the labels' last reader of this batch is on this stream
+                    self._lab_user[self._lab_slot] = 1 << 60
+                for pin, d in zip(pins[o], src(o)):
+                    dev.d2h_async(pin, d)
                 dev.d2h_async(spin[o], self._pass_status[o])
                 dev.record(self.EV_OUT[o])
                 dev.stream(0)

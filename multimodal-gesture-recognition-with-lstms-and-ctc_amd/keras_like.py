@@ -598,34 +598,21 @@ class Model:
                 counts.append(n)
                 yield ins
 
-        output = {None: "posteriors", "argmax": "argmax", "beam": "beam", "beam_lm": "beam_lm", "segments": "segments",
-                  "lexicon": "lexicon"}[decode]
-        lm_args = dict(lm=lm, lm_end=lm_end, alpha=alpha, beta=beta, top_paths=top_paths) if output == "beam_lm" else {}
-        if output == "lexicon":
-            lm_args = dict(lm=lm, lm_end=lm_end, alpha=alpha, beta=beta, lexicon=lexicon)
+        # decode names one of the engine's decode outputs that take unlabelled batches (predict_stream reads of lm .. lexicon only what
+        # that output uses); None names the posteriors
+        if decode is not None and (decode not in e.decode_ops() or decode in e.LABELLED):
+            raise KeyError(decode)
         outs = []
-        for i, r in enumerate(e.predict_stream(feed(), output=output, train_phase=bool(learning_phase()), beam_width=beam_width,
-                                               threshold=threshold, **lm_args)):
-            n = counts[i]
-            if output in ("posteriors", "segments"):
-                outs.append(r[:n])
-            elif output == "argmax":
-                outs.append((r[0][:n], r[1][:n]))
-            elif output in ("beam_lm", "lexicon"):
-                outs.append((r[0][:n], r[1][:n], r[2][:n]))
-            else:
-                outs.append((r[0][:n], r[1][:n]))
+        for i, r in enumerate(e.predict_stream(feed(), output=decode or "posteriors", train_phase=bool(learning_phase()),
+                                               beam_width=beam_width, threshold=threshold, lm=lm, lm_end=lm_end, alpha=alpha, beta=beta,
+                                               top_paths=top_paths, lexicon=lexicon)):
+            # a result is one member or a tuple of members, a member a per-sample list or an array with leading dimension B: each is
+            # trimmed to the batch's true sample count, and the batches are joined member by member
+            outs.append(tuple(m[:counts[i]] for m in r) if isinstance(r, tuple) else r[:counts[i]])
             if verbose:
                 print("%d/%d" % (i + 1, steps))
-        if output == "posteriors":
-            return np.concatenate(outs, axis=0)
-        if output == "segments":
-            return [sg for o in outs for sg in o]
-        if output == "argmax":
-            return np.concatenate([o[0] for o in outs], axis=0), np.concatenate([o[1] for o in outs], axis=0)
-        if output in ("beam_lm", "lexicon"):
-            return [p for o in outs for p in o[0]], np.concatenate([o[1] for o in outs], axis=0), np.concatenate([o[2] for o in outs], axis=0)
-        return [p for o in outs for p in o[0]], np.concatenate([o[1] for o in outs], axis=0)
+        join = lambda ms: np.concatenate(ms, axis=0) if isinstance(ms[0], np.ndarray) else [sample for m in ms for sample in m]
+        return tuple(join(ms) for ms in zip(*outs)) if isinstance(outs[0], tuple) else join(outs)
 
     def align_generator(self, generator, steps, return_path=False):
         """Forced alignment over `steps` batches of a training generator (inputs with the_labels / input_length / label_length, as

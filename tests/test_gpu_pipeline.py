@@ -170,3 +170,82 @@ def test_inference_on_the_f32_mfma_kernels_equals_the_split_f16_path(device):
         assert np.array_equal(b, c)
         assert np.abs(a - b).max() < 2e-5           # posteriors in [0, 1]
     eng.close()
+
+
+def _same(a, b):
+    """Exact equality of two results: tuples member by member, arrays with np.array_equal, per-sample lists with ==."""
+    if isinstance(a, tuple):
+        return isinstance(b, tuple) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    return np.array_equal(a, b) if isinstance(a, np.ndarray) else isinstance(b, list) and a == b
+
+
+def test_decode_outputs_equal_the_host_wrappers_and_cached_buffers_follow_their_parameters(device):
+    """Engine.predict_stream and the decoding.* wrappers launch every decode kernel from one shared description; the two ways that
+    can go wrong.  A wrong argument in one caller: every decode output of the pipelined run equals, exactly, its host wrapper on the
+    posteriors of the same batches (the wrappers get the engine's eps and skip where they take them; those that do not use the
+    spec's default 1e-8).  A stale cached buffer: on ONE engine, runs whose parameters size the buffers differently follow each other,
+    each equal to its own one-batch-at-a-time run, and a repeated setting repeats its result.  And a host wrapper that raises (the
+    library refuses beam_width = 0 on the host, before any launch) frees what it allocated: the next call answers as before."""
+    from mgr_amd import _capi, decoding
+    from mgr_amd.configs import audio_spec
+    from mgr_amd.engine import Engine
+    from mgr_amd.synthetic import synthetic_weights
+    spec = audio_spec(h=128)
+    B, T, Lmax = 16, 72, 6
+    Cn, skip, eps = spec.num_classes, int(spec.ctc["skip"]), float(spec.ctc["eps"])
+    assert eps == 1e-8                   # (what beam_search_decode / beam_search_lm_decode, which take no eps, pass)
+    eng = Engine(spec, B, T, Lmax, device=device, seed=5)
+    eng.set_weights(synthetic_weights(spec, 11))
+    data = _batches(spec, B, T, Lmax, 3)
+
+    def stream(output, batches=data, **kw):
+        return list(eng.predict_stream(iter([b if output in ("align", "score") else b[0] for b in batches]), output=output, **kw))
+
+    def one_by_one(output, **kw):
+        return [stream(output, [b], **kw)[0] for b in data]
+
+    post = stream("posteriors")
+    rng = np.random.default_rng(7)
+
+    def bigram(n_prev, n_next):          # a random bigram with forbidden transitions, and its end-of-sequence column
+        lm = rng.standard_normal((n_prev, n_next))
+        lm[rng.random(lm.shape) < 0.2] = -np.inf
+        return dict(lm=lm, lm_end=rng.standard_normal(n_prev), alpha=0.7, beta=0.3)
+
+    lab_lm = bigram(Cn + 1, Cn)
+    lex3 = [[3, 4], [7], [10, 3, 11]]
+    lex5 = lex3 + [[20, 21, 22, 23], [5]]
+    lm3, lm5 = bigram(4, 3), bigram(6, 5)
+    thr = float(np.median(post[0].max(axis=-1)))      # about half of the frames fall under the confidence filter
+    # ---- every decode output against its host wrapper
+    cases = {
+        "argmax": ({}, lambda P, b: decoding.frame_argmax(P, skip, device)),
+        "segments": (dict(threshold=thr), lambda P, b: decoding.greedy_segments(P, thr, skip, device)),
+        "beam": (dict(beam_width=10), lambda P, b: decoding.beam_search_decode(P, None, 10, skip, True, device)),
+        "beam_lm": (dict(beam_width=8, top_paths=3, **lab_lm),
+                    lambda P, b: decoding.beam_search_lm_decode(P, beam_width=8, top_paths=3, skip=skip, dev=device, **lab_lm)),
+        "lexicon": (dict(lexicon=lex3, **lm3), lambda P, b: decoding.lexicon_decode(P, lex3, skip=skip, dev=device, eps=eps, **lm3)),
+        "align": ({}, lambda P, b: decoding.forced_align(P, b[1], b[3], b[2], skip, device, return_path=True, eps=eps)),
+    }
+    for output, (kw, host) in cases.items():
+        got = stream(output, **kw)
+        assert len(got) == len(data)
+        for r, P, b in zip(got, post, data):
+            assert _same(r, host(P, b)), output
+    segs = [sg for r in stream("segments", threshold=thr) for sg in r]
+    assert any(segs) and segs != [sg for r in stream("segments") for sg in r]          # (the filter did something)
+    # ---- runs that size the cached buffers differently, one after the other on this engine
+    runs = [("beam_lm", dict(beam_width=10, top_paths=1, **lab_lm)), ("beam_lm", dict(beam_width=4, top_paths=3, **lab_lm)),
+            ("beam_lm", dict(beam_width=10, top_paths=1, **lab_lm)),
+            ("lexicon", dict(lexicon=lex3, **lm3)), ("lexicon", dict(lexicon=lex5, **lm5)), ("lexicon", dict(lexicon=lex3, **lm3)),
+            ("score", dict(decode="beam_lm", beam_width=10, **lab_lm)), ("beam_lm", dict(beam_width=10, top_paths=3, **lab_lm))]
+    res = [stream(output, **kw) for output, kw in runs]
+    for (output, kw), r in zip(runs, res):
+        assert all(_same(x, y) for x, y in zip(r, one_by_one(output, **kw))), (output, sorted(kw))
+    assert all(_same(x, y) for x, y in zip(res[0], res[2])) and all(_same(x, y) for x, y in zip(res[3], res[5]))
+    eng.close()
+    # ---- a wrapper that raises leaves the device usable
+    want = decoding.beam_search_decode(post[0], None, 10, skip, True, device)
+    with pytest.raises(_capi.MgrError, match="beam width"):
+        decoding.beam_search_decode(post[0], None, 0, skip, True, device)
+    assert _same(decoding.beam_search_decode(post[0], None, 10, skip, True, device), want)
