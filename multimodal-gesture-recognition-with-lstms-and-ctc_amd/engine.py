@@ -1905,11 +1905,15 @@ class Engine:
         k = self.iterations
         lr_k = o["lr"] * (1.0 / (1.0 + o["decay"] * k))
         t = k + 1
-        lr_t = lr_k * math.sqrt(1.0 - o["beta_2"] ** t) / (1.0 - o["beta_1"] ** t)
+        # the bias correction takes the betas AS THE KERNEL GETS THEM (the C ABI's floats): v is built with 1 - 0.999f, which is
+        # 1.3e-5 off 0.001, and a correction formed from the double 0.999 left every step 6.6e-6 too long (as float32 Keras does,
+        # one beta for both keeps m / sqrt(v) free of the rounding)
+        b1, b2 = float(np.float32(o["beta_1"])), float(np.float32(o["beta_2"]))
+        lr_t = lr_k * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
         dev.call("mgr_update_gate_set", self.gate_flag)
         try:
-            dev.call("mgr_adam_step", self.params, self.grads, self.m, self.v, self.n_train, lr_t, o["beta_1"],
-                     o["beta_2"], o["epsilon"], o["clipvalue"] or 0.0, gscale)
+            dev.call("mgr_adam_step", self.params, self.grads, self.m, self.v, self.n_train, lr_t, b1, b2, o["epsilon"],
+                     o["clipvalue"] or 0.0, gscale)
             for name, (off, n, shape, kind) in self.seg.items():
                 if kind == "kernel":
                     mv = self.spec.kernel_maxnorm(name.rsplit("/", 2)[0])   # "<prefix>/<fwd|bwd>/W" -> "<prefix>"

@@ -212,13 +212,27 @@ class Trainer:
         self.eps = o.get("epsilon", 1e-7)
         self.maxnorm = o.get("maxnorm", 3.0)
 
+    def kernel_maxnorm(self, name):
+        """The bound of kernel "<stream>/l<k>/<dir>/W" or "fusion/<dir>/W": the layer's own "maxnorm" entry (0 = none) where
+        it has one, else the optimizer-wide one."""
+        prefix = name.rsplit("/", 2)[0]
+        if prefix == "fusion":
+            lay = self.spec["fusion"]
+        else:
+            sname, k = prefix.rsplit("/l", 1)
+            lay = next(s for s in self.spec["streams"] if s["name"] == sname)["layers"][int(k)]
+        v = lay.get("maxnorm")
+        return self.maxnorm if v is None else v
+
     def apply(self, grads, gscale=1.0):
         lr_t = kr.adam_lr_t(self.lr, self.decay, self.iterations, self.b1, self.b2)
         for n in self.names:
             kr.adam_step(self.w[n], grads[n], self.m[n], self.v[n], lr_t, self.b1, self.b2,
                          self.eps, self.clipvalue, gscale)
-            if self.kinds[n] == "kernel" and self.maxnorm and self.maxnorm > 0:
-                kr.maxnorm_cols(self.w[n], self.maxnorm)
+            if self.kinds[n] == "kernel":
+                mv = self.kernel_maxnorm(n)
+                if mv and mv > 0:
+                    kr.maxnorm_cols(self.w[n], mv)
         self.iterations += 1
 
     def train_on_batch(self, inputs, labels, input_length, label_length, rand=None):

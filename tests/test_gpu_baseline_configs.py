@@ -1,7 +1,7 @@
 """-m gpu: the BASELINE.json configs that are parity cases rather than bench lines.
  A  audio plumbing  : 2-layer BiLSTM(128)+CTC, B=8,  T=200,  39-d, full size, loss + softmax + gradients vs oracle (the step runs
-                      with apply_update=False: the update kernels have their own tests, test_gpu_kernels.py:test_adam_maxnorm_noise_argmax and the
-                      golden trajectories of test_gpu_network.py)
+                      with apply_update=False: the update kernels have their own tests, test_gpu_update_kernels.py elementwise against fp64, and
+                      the weight movement of the golden and max-norm trajectories of test_gpu_network.py)
  S  skeletal        : BiLSTM(128)+CTC,         B=32, T=1000, 22-d, full size, loss vs oracle (1e-4 relative)
  F  fusion (ref sizes 500/300/100) at B=4, T=96 and at the full T=1900 with B=2: loss + trainable grads
  E  early fusion: 2x BiLSTM(500) on the 59-d concatenated input, all trainable, B=4, T=64
