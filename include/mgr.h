@@ -609,6 +609,35 @@ int mgr_ctc_lexicon_decode(mgr_ctx* ctx, const float* P, const int32_t* input_le
                            int32_t* n_phr, int32_t* phr, int32_t* seg, float* conf, int32_t* path, double* score, double* logp, void* ws,
                            size_t ws_bytes);
 
+/* ---- K14: CTC hypothesis scoring: what rescoring N-best lists across modalities needs from each of them - the CTC
+ * likelihood of K label sequences per sample in one launch.
+ *     logp[b,k] = ln sum over all CTC alignments pi of hypothesis k of prod_t y[t, pi_t]
+ * over the frames skip .. skip + Tp - 1, Tp = input_len[b] clipped into [0, T - skip], y = (P + eps) / sum_c (P + eps): blank, skip,
+ * eps and - without a lexicon - the clipping of labels into the class range are those of mgr_ctc_loss_grad / mgr_ctc_align, and for a
+ * hypothesis a label row of the loss could hold logp is -loss.  fp64, natural-log units (the recursion runs on renormalised f32
+ * values in base-2 units, what it subtracted is summed in fp64).
+ * hyp [B,K,Lh] int32 / hyp_len [B,K] int32 (device) are laid out as mgr_ctc_beam_search_lm writes out / out_len: rows of any width Lh
+ * <= MGR_RESCORE_MAX_WIDTH, only the first hyp_len entries of a row are read (a length above Lh counts as Lh), a length < 0 means "no
+ * hypothesis in this slot".
+ * Lexicon: phrase_off [G+1] / phrase_words (HOST memory, as in K13; checked entry by entry at every call by K13's rules; C <= 64) or
+ * NULL, NULL, 0.  With a lexicon the entries of hyp are PHRASE ids and the hypothesis is the concatenation of its phrases' words - a
+ * blank is forced only between equal neighbouring words, within and across phrases; the expansion happens on the device.
+ * Results: logp [B,K] double, n_lab [B,K] int32 or NULL = the number of labels after expansion.
+ *   absent slot                                   logp -inf, n_lab -1
+ *   labels + forced blanks > Tp (also Tp = 0)     logp -inf, n_lab the expanded count
+ *   a phrase id outside [0, G)                    logp NaN ("not scored"), n_lab -1
+ *   more than MGR_RESCORE_MAX_LABELS labels       logp NaN, n_lab the expanded count
+ *   the empty hypothesis                          logp = sum_t ln y[t, blank] (0 at Tp = 0), n_lab 0
+ * The workspace holds the class-major emissions, computed once per sample and shared by its hypotheses; its size does not depend on
+ * the lexicon (the query takes it for symmetry with the call).  No atomics: deterministic, and a sample's row does not depend on the
+ * rest of the batch.  B <= 65535. */
+#define MGR_RESCORE_MAX_LABELS 255
+#define MGR_RESCORE_MAX_WIDTH  65536
+size_t mgr_ctc_rescore_ws_bytes(int B, int T, int C, int G, const int32_t* phrase_off);
+int mgr_ctc_rescore(mgr_ctx* ctx, const float* P, const int32_t* input_len, int B, int T, int C, int skip, int blank, float eps,
+                    const int32_t* phrase_off, const int32_t* phrase_words, int G, const int32_t* hyp, const int32_t* hyp_len, int K,
+                    int Lh, double* logp, int32_t* n_lab, void* ws, size_t ws_bytes);
+
 /* ---- K12: scoring decodes: the weighted edit distance of n_pairs pairs of label sequences, with the substitution /
  * deletion / insertion split of HTK's HResults, in one launch.  All pointers are device memory.
  * hyp [n_hyp,Lh], ref [n_ref,Lr] int32, rows padded with -1; hyp_len [n_hyp] / ref_len [n_ref] int32 or NULL: NULL = the whole row,

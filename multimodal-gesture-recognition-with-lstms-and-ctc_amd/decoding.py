@@ -125,6 +125,21 @@ def align_op(n_classes, skip, return_path=False, eps=1e-8):
                     ws_bytes=lambda lib, N, T, Lmax: lib.mgr_ctc_align_ws_bytes(N, T, Cn, Lmax), uses_len=True)
 
 
+def rescore_op(n_classes, skip, lexicon=None, eps=1e-8):
+    """mgr_ctc_rescore (K14): the hypothesis arrays (hyp (N, K, Lh), hyp_len (N, K)) travel where align passes its labels, so the
+    `Lmax` the description's functions get is K."""
+    Cn = int(n_classes)
+    off, words = compile_lexicon(lexicon, Cn) if lexicon is not None else (None, None)     # (host arrays, checked again at every call)
+    G = 0 if off is None else len(off) - 1
+    host = lambda a: None if a is None else a.ctypes.data
+
+    def launch(dev, P, input_len, outs, tables, ws, hyp, hyp_len):
+        dev.call("mgr_ctc_rescore", P, input_len, P.shape[0], P.shape[1], Cn, skip, Cn - 1, C.c_float(eps), host(off), host(words), G,
+                 hyp, hyp_len, hyp.shape[1], hyp.shape[2], *outs, ws, ws.nbytes)
+    return DecodeOp("rescore", lambda N, T, K: (_f64(N, K), _i32(N, K)), launch, lambda logp, n_lab, hyp, hyp_len: (logp, n_lab),
+                    ws_bytes=lambda lib, N, T, K=None: lib.mgr_ctc_rescore_ws_bytes(N, T, Cn, G, host(off)), uses_len=True)
+
+
 def _posteriors(pred_out):
     return np.ascontiguousarray(pred_out, dtype=np.float32)
 
@@ -480,6 +495,138 @@ def decode_beam_mlf(pred_out, f_list, map_gest, ignore_list, name_fmt, out_file,
     if out_file is not None:
         write_mlf(out_file, ret, f_list, ignore_list, name_fmt)
     return ret, nbest
+
+
+# ---- rescoring N-best lists across modalities (K14): CTC scores of pooled hypotheses, combined and re-ranked -----------
+RESCORE_MAX_LABELS, RESCORE_MAX_WIDTH = 255, 65536       # MGR_RESCORE_MAX_* of include/mgr.h
+
+
+def pack_nbest(paths, K=None, width=None):
+    """Per sample a list of label lists (what beam_search_lm_decode(top_paths > 1) or pool_hypotheses return) -> the arrays
+    mgr_ctc_rescore reads, in the layout mgr_ctc_beam_search_lm writes: (hyp (N, K, Lh) int32 padded -1, hyp_len (N, K) int32, -1 =
+    no hypothesis in the slot).  K / width default to the largest list / longest hypothesis (at least 1); smaller ones are refused."""
+    paths = [[[int(v) for v in h] for h in hyps] for hyps in paths]
+    most = max([len(h) for h in paths] + [1])
+    longest = max([len(h) for hyps in paths for h in hyps] + [1])
+    K, Lh = most if K is None else int(K), longest if width is None else int(width)
+    if K < most or Lh < longest:
+        raise ValueError("K = %d / width = %d: the lists hold up to %d hypotheses of up to %d labels" % (K, Lh, most, longest))
+    if Lh > RESCORE_MAX_WIDTH:
+        raise ValueError("width = %d: rows of at most %d entries" % (Lh, RESCORE_MAX_WIDTH))
+    hyp, hyp_len = -np.ones((len(paths), K, Lh), np.int32), -np.ones((len(paths), K), np.int32)
+    for b, hyps in enumerate(paths):
+        for k, h in enumerate(hyps):
+            hyp[b, k, :len(h)] = h
+            hyp_len[b, k] = len(h)
+    return hyp, hyp_len
+
+
+def ctc_scores(pred_out, paths_or_arrays, lexicon=None, input_length=None, skip=2, dev=None, eps=1e-8, return_counts=False):
+    """log p(hypothesis | posteriors) for many hypotheses per sample in one launch (mgr_ctc_rescore): the sum over ALL CTC
+    alignments, under the loss's conventions (frames skip .., y = softmax(log(P + eps)), blank = C - 1) - for a label row the loss
+    takes, minus the loss.  pred_out (N, T, C); paths_or_arrays: per sample a list of label lists, or the (hyp (N, K, Lh), hyp_len
+    (N, K)) of pack_nbest / of the beam decoder's device output.  With a lexicon (whatever compile_lexicon takes) the entries are
+    PHRASE ids and their word expansion is scored, expanded on the device.
+    Returns logp (N, K) float64: -inf for an absent slot or a hypothesis that does not fit the input length, NaN ("not scored") for
+    one with a phrase id outside the lexicon or more than 255 expanded labels[, n_lab (N, K) int32: the expanded label counts]."""
+    P = _posteriors(pred_out)
+    arrays = isinstance(paths_or_arrays, tuple) and len(paths_or_arrays) == 2 and np.ndim(paths_or_arrays[0]) == 3
+    hyp, hyp_len = paths_or_arrays if arrays else pack_nbest(paths_or_arrays)
+    hyp, hyp_len = np.ascontiguousarray(hyp, np.int32), np.ascontiguousarray(hyp_len, np.int32)
+    if hyp.shape[0] != P.shape[0] or hyp_len.shape != hyp.shape[:2]:
+        raise ValueError("hypotheses %s / lengths %s for %d samples" % (hyp.shape, hyp_len.shape, P.shape[0]))
+    logp, n_lab = _run(rescore_op(P.shape[2], skip, lexicon, eps), P, skip, dev, input_length, (hyp, hyp_len))
+    return (logp, n_lab) if return_counts else logp
+
+
+def pool_hypotheses(*nbest_lists, cap=None):
+    """The hypotheses every stream scores: per sample the ordered union without duplicates of its lists - the first list's order, then
+    what each further list adds, in its order; cap truncates.  Each argument is per sample a list of label lists."""
+    if not nbest_lists:
+        return []
+    N = len(nbest_lists[0])
+    if any(len(l) != N for l in nbest_lists):
+        raise ValueError("lists for %s samples" % ([len(l) for l in nbest_lists],))
+    pool = []
+    for b in range(N):
+        seen, out = set(), []
+        for lst in nbest_lists:
+            for h in lst[b]:
+                key = tuple(int(v) for v in h)
+                if key not in seen:
+                    seen.add(key)
+                    out.append(list(key))
+        pool.append(out if cap is None else out[:int(cap)])
+    return pool
+
+
+def combine_scores(parts, paths, weights=None, lm=None, lm_end=None, alpha=1.0, beta=0.0):
+    """Stream-weighted totals of pooled hypotheses and their ranking (host, fp64).  parts (N, K, M): the score of hypothesis k of
+    sample b in stream m (ctc_scores); paths: the pool, per sample at most K label lists over one gesture alphabet.
+        total = sum_m weights[m] * parts[.., m] + alpha * (lm[prev + 1, g] over the hypothesis + lm_end[last + 1]) + beta * len
+    with the tables of phrase_lm_tables (row / index 0 = start of sequence / the empty sequence; -inf forbids; lm_end may be None).
+    A zero weight leaves its stream out, whatever the stream holds.  Returns (order (N, K) int64: slot indices, best first; total
+    (N, K) float64 in that order).  Ties go to pool order; hypotheses whose total is -inf or NaN and absent slots (total -inf) come
+    last, in pool order."""
+    parts = np.asarray(parts, np.float64)
+    if parts.ndim != 3 or parts.shape[0] != len(paths):
+        raise ValueError("parts %s for %d samples" % (parts.shape, len(paths)))
+    N, K, M = parts.shape
+    w = np.ones(M) if weights is None else np.asarray(weights, np.float64).reshape(-1)
+    if w.shape != (M,) or not np.all(np.isfinite(w)):
+        raise ValueError("weights %r for %d streams" % (weights, M))
+    ext = fin = None
+    if lm is not None or lm_end is not None:
+        G = np.shape(lm)[1] if lm is not None else len(lm_end) - 1
+        ext, fin = phrase_lm_tables(G, lm, lm_end, alpha, 0.0)
+    total = np.zeros((N, K))
+    for m in range(M):
+        if w[m] != 0.0:
+            total += w[m] * parts[:, :, m]
+    order = np.zeros((N, K), np.int64)
+    for b, hyps in enumerate(paths):
+        if len(hyps) > K:
+            raise ValueError("sample %d has %d hypotheses, parts hold %d" % (b, len(hyps), K))
+        for k, h in enumerate(hyps):
+            t, prev = float(beta) * len(h), 0
+            for g in h:
+                if ext is not None:
+                    if not 0 <= int(g) < ext.shape[1]:
+                        raise ValueError("sample %d: label %d is outside the tables' %d" % (b, int(g), ext.shape[1]))
+                    t += ext[prev, int(g)]
+                    prev = int(g) + 1
+            if fin is not None:
+                t += fin[prev if h else 0]
+            total[b, k] += t
+        total[b, len(hyps):] = -np.inf
+        good = np.isfinite(total[b])
+        first = np.flatnonzero(good)
+        first = first[np.argsort(-total[b, first], kind="stable")]
+        order[b] = np.concatenate([first, np.flatnonzero(~good)])
+    return order, np.take_along_axis(total, order, axis=1)
+
+
+def rescore_nbest(streams, paths, weights=None, lm=None, lm_end=None, alpha=1.0, beta=0.0, dev=None):
+    """Multiple-hypotheses rescoring: every stream scores the same pool, the scores are combined (combine_scores) and
+    the pool is re-ranked.  streams: a list of (pred_out (N, T, C), dict(lexicon=, input_length=, skip=, eps=)) - T and C may differ
+    from stream to stream, a stream with a lexicon reads the pool's labels as phrase ids - or of ((N, K) scores computed elsewhere,
+    e.g. by Model.rescore_generator, anything).  paths: the pool (pool_hypotheses).
+    Returns (ranked paths: per sample its hypotheses best first, total (N, K), parts (N, K, M) in ranked order, order (N, K)) - paths
+    and total are what mbr_decode(paths, scores) and nbest_attainable(paths, refs) take."""
+    hyp, hyp_len = pack_nbest(paths)
+    cols = []
+    for pred_out, opts in streams:
+        if np.ndim(pred_out) == 2:
+            s = np.asarray(pred_out, np.float64)
+            if s.shape != hyp_len.shape:
+                raise ValueError("scores %s for a pool of %s" % (s.shape, hyp_len.shape))
+        else:
+            s = ctc_scores(pred_out, (hyp, hyp_len), dev=dev, **(opts or {}))
+        cols.append(s)
+    parts = np.stack(cols, axis=2)
+    order, total = combine_scores(parts, paths, weights, lm, lm_end, alpha, beta)
+    ranked = [[list(paths[b][k]) for k in order[b] if k < len(paths[b])] for b in range(len(paths))]
+    return ranked, total, np.take_along_axis(parts, order[:, :, None], axis=1), order
 
 
 def edit_distance(a, b):

@@ -8,6 +8,7 @@ multimodal_fusion/sequence_decoding.py:121); there is no CPU fallback.
 """
 import collections
 import ctypes as C
+import itertools
 import math
 
 import numpy as np
@@ -1053,15 +1054,31 @@ class Engine:
                         by mgr_edit_distance of its device output against the batch's labels with costs = (sub, del, ins), both
                         sides without the labels in ignore (None: the blank, which the greedy decode keeps).  36 bytes per sample
                         travel to the host, no label sequence does (a training engine, like "loss")
+          "rescore"     (logp (B, K) float64, n_lab (B, K) int32): mgr_ctc_rescore on the device - the CTC log-likelihood, summed over all
+                        alignments, of K hypotheses per sample (decoding.ctc_scores of the posteriors).  Batches are tuples
+                        (inputs, hyp (B, K, Lh) int32 padded -1, hyp_len (B, K) int32, -1 = no hypothesis) as decoding.pack_nbest lays
+                        them out - with `lexicon` the entries are phrase ids -; K and Lh are those of the first batch.  The hypothesis
+                        arrays go up through pinned double buffers on the output stream; an inference-only engine will do
         Results are bit-identical to the one-batch-at-a-time calls (predict / loss_on_batch): same kernels, same order per batch."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         Cn, skip, eps = sp.num_classes, int(sp.ctc["skip"]), float(sp.ctc["eps"])
         # ("score" decodes one path; top_paths is read for "beam_lm" alone)
         ops = self.decode_ops(beam_width, merge_repeated, threshold, top_paths if output == "beam_lm" else 1, lexicon,
                                lm=lm, lm_end=lm_end, alpha=alpha, beta=beta)
-        if output not in ("posteriors", "loss", "score") + tuple(ops):
+        if output not in ("posteriors", "loss", "score", "rescore") + tuple(ops):
             raise ValueError("unknown output %r" % (output,))
         labelled = output in self.LABELLED
+        hypo = output == "rescore"
+        if hypo:      # (K and the row width size the buffers below: the first batch is looked at before anything is enqueued)
+            rest = iter(batches)
+            head = next(rest, None)
+            if head is None:
+                return
+            batches = itertools.chain([head], rest)
+            hshape = tuple(int(v) for v in np.shape(head[1]))
+            if len(hshape) != 3 or hshape[0] != B or np.shape(head[2]) != hshape[:2]:
+                raise ValueError("output='rescore' takes batches (inputs, hyp (%d, K, Lh), hyp_len (%d, K)), got hyp %s / hyp_len %s"
+                                 % (B, B, hshape, np.shape(head[2])))
         if labelled and self.inference_only:
             raise ValueError("output=%r needs a training engine (labels%s)" % (output, "" if output == "align" else ", CTC workspace"))
         self._bind()
@@ -1098,15 +1115,19 @@ class Engine:
         elif output == "lexicon" and lexicon is None:
             raise ValueError("output='lexicon' needs a lexicon")
         op, host_labels = None, {}
-        if name in ops:
+        if hypo:
+            op = decoding.rescore_op(Cn, skip, lexicon, eps)
+        elif name in ops:
+            op = ops[name]()
+        if op is not None:
             # The op's device outputs, workspace and tables, each cached under what sizes it - so "segments" and "score" with the greedy
             # decode, or "beam_lm" and "score" at one path, share them.  One set of outputs: decode, comparison and copies of a batch are
             # consecutive on the output stream - but two for "align", which runs on stream 0: one per output slot, like the losses below
-            op = ops[name]()
-            shapes = op.outputs(B, T, self.Lmax)
+            Lq = hshape[1] if hypo else self.Lmax       # ("rescore": K travels where the labelled ops get Lmax)
+            shapes = op.outputs(B, T, Lq)
             dring = bufs((name, "out", shapes), lambda: [tuple(sh if sh is None else self.mem.empty(*sh) for sh in shapes)
                                                         for _ in range(2 if name == "align" else 1)])
-            nbytes = op.ws_bytes(self.lib, B, T, self.Lmax) if op.ws_bytes else None
+            nbytes = op.ws_bytes(self.lib, B, T, Lq) if op.ws_bytes else None
             ws = None if nbytes is None else bufs((name, "ws", nbytes), lambda: self.mem.bytes(nbytes))
             # (the tables are uploaded once per call, not per batch)
             tables = [t if t is None else bufs((name, "table", k, t.shape), lambda: self.mem.empty(t.shape, t.dtype)).upload(t)
@@ -1114,6 +1135,10 @@ class Engine:
             dil = None          # ("align" reads the lengths that came with the labels)
             if op.uses_len and name != "align":
                 dil = bufs("dil", lambda: self.mem.empty((B,), np.int32)).upload(np.full(B, T - skip, np.int32))
+            if hypo:      # one device set (upload and kernel of a batch are consecutive on the output stream), two pinned ones
+                hspec = [(hshape, np.int32), (hshape[:2], np.int32)]
+                dhyp = bufs(("rescore", "hyp", hshape), lambda: sets(1, self.mem.empty, hspec))[0]
+                phyp = bufs(("rescore", "hyp pinned", hshape), lambda: sets(2, dev.pinned, hspec))
         # per output slot o: the pinned arrays a result arrives in, and the device arrays src(o) they are copied from
         if output == "posteriors":
             pins, src = bufs("P", lambda: sets(2, dev.pinned, [((B, T, Cn), np.float32)])), lambda o: (pring[o],)
@@ -1135,7 +1160,7 @@ class Engine:
         def collect(i):
             o = i & 1
             dev.event_sync(self.EV_OUT[o])
-            if output in ops:
+            if output in ops or hypo:
                 r = op.result(*pins[o], *host_labels.pop(i, ()))
             else:
                 r = pins[o] if output == "score" else pins[o][0]
@@ -1170,7 +1195,7 @@ class Engine:
         def start_encoders(i, item):
             """Upload batch i and enqueue its noise / depth-1 projections on stream 0 (two_stage), or nothing yet; returns the
             generator that enqueues the rest of its encoder pass on ES."""
-            inputs = item[0] if labelled else item
+            inputs = item[0] if labelled or hypo else item
             f = i % len(ring)
             first = 0 if two_stage else ES
             self._upload_inputs(inputs, None, train_phase, stream=first)
@@ -1261,7 +1286,16 @@ class Engine:
                 # ---- decode kernels and the way back to pinned host memory: their own stream, beside batch i + 1's fusion layer
                 dev.stream(OUT)
                 dev.wait_event(OUT, self.EV_FUSED[f])
-                if op is not None and output != "align":
+                if hypo:
+                    # (pinned set o was last read by batch i - 2's copies, behind EV_OUT[o], which collect(i - 2) has waited for)
+                    if np.shape(item[1]) != hshape or np.shape(item[2]) != hshape[:2]:
+                        raise ValueError("batch %d: hyp %s / hyp_len %s, the first batch had %s" % (i, np.shape(item[1]), np.shape(item[2]), hshape))
+                    for pin, d, a in zip(phyp[o], dhyp, item[1:3]):
+                        pin[...] = a
+                        dev.h2d_async(d, pin)
+                    host_labels[i] = (None, None)
+                    op.launch(dev, pring[o], dil, dring[0], tables, ws, *dhyp)
+                elif op is not None and output != "align":
                     op.launch(dev, pring[o], dil, dring[0], tables, ws)
                 if output == "score":
                     dev.call("mgr_edit_distance", dring[0][op.hyp[0]], dring[0][op.hyp[1]], B, T - skip, self.labels_d, self.llen_d, B, self.Lmax,

@@ -614,6 +614,47 @@ class Model:
         join = lambda ms: np.concatenate(ms, axis=0) if isinstance(ms[0], np.ndarray) else [sample for m in ms for sample in m]
         return tuple(join(ms) for ms in zip(*outs)) if isinstance(outs[0], tuple) else join(outs)
 
+    def rescore_generator(self, generator, steps, paths, lexicon=None, return_counts=False):
+        """CTC scores of pooled hypotheses over `steps` batches, pipelined like predict_generator (Engine.predict_stream,
+        output="rescore"): logp (N, K) float64, log p(hypothesis k of sample b | this network's posteriors for b) summed over all
+        alignments - decoding.ctc_scores(predict_generator(...), paths, lexicon=lexicon) bit for bit, without the posteriors leaving
+        the device.  paths: for the N samples the generator yields, in its order, per sample a list of label lists (what
+        decoding.pool_hypotheses returns), or the (hyp (N, K, Lh), hyp_len (N, K)) arrays of decoding.pack_nbest; with `lexicon` the
+        entries are phrase ids.  -inf: no hypothesis in the slot, or one that does not fit the frames; NaN: not scored (ctc_scores).
+        One column of decoding.rescore_nbest's parts per network.  return_counts: also n_lab (N, K) int32, the expanded label counts."""
+        from .decoding import pack_nbest
+        steps = int(steps)
+        arrays = isinstance(paths, tuple) and len(paths) == 2 and np.ndim(paths[0]) == 3
+        hyp, hyp_len = (np.asarray(paths[0], np.int32), np.asarray(paths[1], np.int32)) if arrays else pack_nbest(paths)
+        K = hyp.shape[1]
+        if steps <= 0:
+            return (np.zeros((0, K)), np.zeros((0, K), np.int32)) if return_counts else np.zeros((0, K))
+        first = next(generator)
+        x0 = first[0] if isinstance(first, tuple) else first
+        f0 = next(iter(self._split_inputs(x0).values()))
+        B = f0.shape[0]
+        e = self._ensure_engine(B, f0.shape[1], self._engine.Lmax if self._engine else 1,
+                                inference_only=self._engine is None or self._engine.inference_only)
+        counts = []
+
+        def feed():
+            at = 0
+            for i in range(steps):
+                batch = first if i == 0 else next(generator)
+                ins, n = self._pad_batch(self._split_inputs(batch[0] if isinstance(batch, tuple) else batch), B)
+                if at + n > hyp.shape[0]:
+                    raise ValueError("hypotheses for %d samples, the generator yields more" % hyp.shape[0])
+                counts.append(n)
+                h, hl = -np.ones((B,) + hyp.shape[1:], np.int32), -np.ones((B, K), np.int32)       # (padded rows: no hypotheses)
+                h[:n], hl[:n] = hyp[at:at + n], hyp_len[at:at + n]
+                at += n
+                yield ins, h, hl
+
+        outs = [(lp[:counts[i]], nl[:counts[i]]) for i, (lp, nl) in
+                enumerate(e.predict_stream(feed(), output="rescore", train_phase=bool(learning_phase()), lexicon=lexicon))]
+        logp, n_lab = (np.concatenate(m, axis=0) for m in zip(*outs))
+        return (logp, n_lab) if return_counts else logp
+
     def align_generator(self, generator, steps, return_path=False):
         """Forced alignment over `steps` batches of a training generator (inputs with the_labels / input_length / label_length, as
         fit_generator takes them), pipelined like evaluate_generator: per sample the most probable CTC alignment of ITS labels to the
