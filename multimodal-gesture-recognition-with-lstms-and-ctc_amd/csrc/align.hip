@@ -1,10 +1,12 @@
 // K11: locating gestures in time.  Two device operations:
 //
 // mgr_ctc_align - Viterbi forced alignment: the alpha recursion of ctc.hip with max in place of log-sum-exp, a 2-bit back-pointer per
-// frame and state, and a backtrace.  Two kernels: emissions (a thread per frame, class-major rows like ctc.hip's), then one WAVE per
-// sample: the extended label sequence lives across the lanes as (blank, label) pairs, lane * PPL + j holds states 2p and 2p + 1, the only
-// cross-lane traffic of a step is one DPP shift of the neighbouring pair's label value, and a lane fetches CH steps of its label's and
-// the blank's emissions with 16-byte loads, a chunk ahead of the recursion.
+// frame and state, and a backtrace.  Two kernels: emissions (k_lattice_emissions in natural-log units: a thread per frame, class-major
+// rows), then one WAVE per sample over the lattice as ctc_lattice.h lays it across the lanes: (blank, label) pairs, lane * PPL + j holds
+// states 2p and 2p + 1, the only cross-lane traffic of a step is one DPP shift of the neighbouring pair's label value, and a lane
+// fetches CH steps of its label's and the blank's emissions with 16-byte loads, a chunk ahead of the recursion.  The pairs, the chunks,
+// the renormalisation and the pick of the final states come from that header; the max step, the back-pointer packing and the backtrace
+// are this file's.
 // Back-pointers: a pair's two pointers are one nibble per frame; a lane collects eight frames of a pair in one register and stores one
 // word per pair and eight frames: (Lmax + 1) * ceil(To / 8) words, 143 KB at 301 states and 1898 frames, 34 KB at 71 states.  They live
 // in the workgroup's LDS when they fit 160 KB (every shape the networks have) and in the workspace otherwise: the backtrace is a chain
@@ -20,62 +22,14 @@
 // threshold), the collapse of repeats, and per run its label, first / last surviving frame and mean probability.  One workgroup per
 // sample, everything per frame in LDS: per-label counts by LDS atomics, the frame of a label's k_s-th occurrence by a ballot scan (one
 // wave per label), survivors and run starts by two block-wide prefix sums.
-#include "common.h"
+#include "ctc_lattice.h"
 
 namespace {
-
-constexpr float kNegInf = -__builtin_huge_valf();
-
-// cross-lane traffic through DPP (see ctc.hip): wave_shr:1 moves a value to the next lane of the whole wave
-constexpr int DPP_WAVE_SHR1 = 0x138;
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v, float fill) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float wave_max_f32(float m) {
-  m = fmaxf(m, dpp_f32<0x111>(m, m));   // row_shr:1 (lanes without a source keep their own value)
-  m = fmaxf(m, dpp_f32<0x112>(m, m));
-  m = fmaxf(m, dpp_f32<0x114>(m, m));
-  m = fmaxf(m, dpp_f32<0x118>(m, m));   // lane 15 of a row holds the row's maximum
-  const int i = __float_as_int(m);
-  return fmaxf(fmaxf(__int_as_float(__builtin_amdgcn_readlane(i, 15)), __int_as_float(__builtin_amdgcn_readlane(i, 31))),
-               fmaxf(__int_as_float(__builtin_amdgcn_readlane(i, 47)), __int_as_float(__builtin_amdgcn_readlane(i, 63))));
-}
 
 // row length of the class-major emissions: To + the over-read of two chunks of 8 steps, a multiple of 4 floats
 __host__ __device__ inline size_t align_ts(int To) { return ((size_t)To + 16 + 3) / 4 * 4; }
 __host__ __device__ inline int align_nb(int To) { return (To + 7) / 8; }   // back-pointer blocks of eight frames
 __host__ __device__ inline int align_state_words(int To) { return (To + 63) / 64 * 32; }   // uint16 per frame, whole blocks of 64 frames
-__device__ __forceinline__ int clip_len(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// emissions ln y(t, c) = ln(P + eps) - ln(sum_c (P + eps)), class-major: E[b][c][TS].  One frame per thread; the frames of a row
-// behind the sample's length (the recursion's prefetch reads them and uses none) are zeros.
-__global__ __launch_bounds__(256) void k_align_emissions(const float* __restrict__ P, const int32_t* __restrict__ input_len, int T, int C, int skip,
-                                                         float eps, float* __restrict__ E) {
-  const int b = blockIdx.y, To = T - skip;
-  const size_t TS = align_ts(To);
-  const int Tp = clip_len(input_len[b], To);
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if ((size_t)t >= TS) return;
-  float* Eb = E + (size_t)b * C * TS;
-  if (t >= Tp) {
-    for (int c = 0; c < C; ++c) Eb[(size_t)c * TS + t] = 0.f;
-    return;
-  }
-  const float* row = P + ((size_t)b * T + skip + t) * C;
-  float s = 0.f;
-  for (int c = 0; c < C; ++c) s += row[c] + eps;
-  const float ls = logf(s);
-  for (int c = 0; c < C; ++c) Eb[(size_t)c * TS + t] = logf(row[c] + eps) - ls;
-}
-
-template <int PPL>
-struct AlignChunk {
-  static constexpr int CH = PPL <= 2 ? 8 : 4;   // time steps per prefetched chunk
-  float eb[CH];
-  float el[CH][PPL];
-};
-
 // One wave per sample.  LDS: the label row, first / last frame per label, the path's state per frame, then (LDS_BP) the back-pointer words.
 template <int PPL, bool LDS_BP>
 __global__ __launch_bounds__(64) void k_ctc_align(const float* __restrict__ P, const int32_t* __restrict__ labels,
@@ -84,7 +38,7 @@ __global__ __launch_bounds__(64) void k_ctc_align(const float* __restrict__ P, c
                                                   int32_t* __restrict__ path, int32_t* __restrict__ seg, float* __restrict__ conf,
                                                   double* __restrict__ logp) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  constexpr int CH = AlignChunk<PPL>::CH;
+  constexpr int CH = Chunk<PPL>::CH;
   const int b = blockIdx.x, lane = threadIdx.x;
   const int To = T - skip, NP = Lmax + 1, NB = align_nb(To);
   const size_t TS = align_ts(To);
@@ -96,33 +50,13 @@ __global__ __launch_bounds__(64) void k_ctc_align(const float* __restrict__ P, c
   uint32_t* bp = LDS_BP ? smem + 3 * NP + align_state_words(To) : BPg + (size_t)b * NB * NP;
   const float* Eb = E + (size_t)b * C * TS;
   for (int i = lane; i < NP; i += 64) {   // labels clipped into the class range, as ctc.hip's ctc_labels
-    int v = (i < L) ? labels[(size_t)b * Lmax + i] : -1;
-    s_lab[i] = v < 0 ? 0 : (v >= C ? C - 1 : v);
+    s_lab[i] = clip_label((i < L) ? labels[(size_t)b * Lmax + i] : -1, C);
     s_first[i] = -1;
     s_last[i] = -1;
   }
   __syncthreads();
 
-  int lab[PPL];
-  bool vl[PPL], vb[PPL], cs[PPL];
-#pragma unroll
-  for (int j = 0; j < PPL; ++j) {
-    const int p = lane * PPL + j;
-    vl[j] = p < L;
-    vb[j] = p <= L;
-    lab[j] = vl[j] ? s_lab[p] : blank;
-  }
-  {
-    const int prev_last = __shfl_up(lab[PPL - 1], 1);
-    const bool prev_vl = __shfl_up((int)vl[PPL - 1], 1) != 0;
-#pragma unroll
-    for (int j = 0; j < PPL; ++j) {
-      const int p = lane * PPL + j;
-      const int pl = (j > 0) ? lab[j - 1] : prev_last;
-      const bool pv = (j > 0) ? vl[j - 1] : (lane > 0 && prev_vl);
-      cs[j] = vl[j] && p >= 1 && pv && lab[j] != blank && lab[j] != pl;   // the skip of two states, as in the loss
-    }
-  }
+  const Pairs<PPL> pr(s_lab, L, blank, lane);   // (cs: the skip of two states, as in the loss)
 
   float ab[PPL], al[PPL];
   double coff = 0.0;
@@ -131,33 +65,16 @@ __global__ __launch_bounds__(64) void k_ctc_align(const float* __restrict__ P, c
     for (int j = 0; j < PPL; ++j) {
       const int p = lane * PPL + j;
       ab[j] = (p == 0) ? Eb[(size_t)blank * TS] : kNegInf;
-      al[j] = (p == 0 && vl[j]) ? Eb[(size_t)lab[j] * TS] : kNegInf;
+      al[j] = (p == 0 && pr.vl[j]) ? Eb[(size_t)pr.lab[j] * TS] : kNegInf;
     }
-    AlignChunk<PPL> cur, nxt;
-    auto load = [&](AlignChunk<PPL>& ch, int t0) {   // steps t0 .. t0 + CH - 1 (t0 a multiple of 4: 16-byte aligned; over-read stays in the row)
-      const float* rb = Eb + (size_t)blank * TS + t0;
-#pragma unroll
-      for (int q = 0; q < CH / 4; ++q) {
-        const float4 v = *reinterpret_cast<const float4*>(rb + 4 * q);
-        ch.eb[4 * q] = v.x; ch.eb[4 * q + 1] = v.y; ch.eb[4 * q + 2] = v.z; ch.eb[4 * q + 3] = v.w;
-      }
-#pragma unroll
-      for (int j = 0; j < PPL; ++j) {
-        const float* rl = Eb + (size_t)lab[j] * TS + t0;
-#pragma unroll
-        for (int q = 0; q < CH / 4; ++q) {
-          const float4 v = *reinterpret_cast<const float4*>(rl + 4 * q);
-          ch.el[4 * q][j] = v.x; ch.el[4 * q + 1][j] = v.y; ch.el[4 * q + 2][j] = v.z; ch.el[4 * q + 3][j] = v.w;
-        }
-      }
-    };
-    load(cur, 0);
+    Chunk<PPL> cur, nxt;   // steps t0 .. t0 + CH - 1, t0 a multiple of 4: 16-byte aligned
+    cur.load(Eb, TS, blank, pr.lab, 0);
     uint32_t bits[PPL];
 #pragma unroll
     for (int j = 0; j < PPL; ++j) bits[j] = 0u;
     int since = 0;
     for (int t0 = 0; t0 < Tp; t0 += CH) {
-      load(nxt, t0 + CH);
+      nxt.load(Eb, TS, blank, pr.lab, t0 + CH);
 #pragma unroll
       for (int k = 0; k < CH; ++k) {
         const int t = t0 + k;
@@ -170,14 +87,14 @@ __global__ __launch_bounds__(64) void k_ctc_align(const float* __restrict__ P, c
             const float up = (j > 0) ? al[j - 1] : carry;
             // blank state 2p: stay (0), or from label p - 1 (1); a tie stays
             const bool b1 = up > ab[j];
-            nb[j] = vb[j] ? cur.eb[k] + (b1 ? up : ab[j]) : kNegInf;
+            nb[j] = pr.vb[j] ? cur.eb[k] + (b1 ? up : ab[j]) : kNegInf;
             // label state 2p + 1: stay (0), from its blank (1), from label p - 1 where the skip is allowed (2); a tie takes the smaller step
             float m = al[j];
             uint32_t s = 0u;
             if (ab[j] > m) { m = ab[j]; s = 1u; }
-            const float u2 = cs[j] ? up : kNegInf;
+            const float u2 = pr.cs[j] ? up : kNegInf;
             if (u2 > m) { m = u2; s = 2u; }
-            nl[j] = vl[j] ? cur.el[k][j] + m : kNegInf;
+            nl[j] = pr.vl[j] ? cur.el[k][j] + m : kNegInf;
             bits[j] |= ((b1 ? 1u : 0u) | (s << 2)) << sh;
           }
 #pragma unroll
@@ -199,35 +116,13 @@ __global__ __launch_bounds__(64) void k_ctc_align(const float* __restrict__ P, c
       since += CH;
       if (since >= 16) {   // renormalise: keep the running values O(10)
         since = 0;
-        float m = kNegInf;
-#pragma unroll
-        for (int j = 0; j < PPL; ++j) m = fmaxf(m, fmaxf(ab[j], al[j]));
-        m = wave_max_f32(m);
-        if (m != kNegInf) {
-#pragma unroll
-          for (int j = 0; j < PPL; ++j) {
-            ab[j] -= m;
-            al[j] -= m;
-          }
-          coff += (double)m;
-        }
+        coff += (double)renorm(ab, al);
       }
     }
   }
   // the two final states: the last blank 2L and the last label 2L - 1; a tie takes the blank
-  float fb = kNegInf, fl = kNegInf;
-  if (Tp > 0) {
-#pragma unroll
-    for (int j = 0; j < PPL; ++j) {
-      const int p = lane * PPL + j;
-      if (p == L) fb = ab[j];
-      if (p == L - 1) fl = al[j];
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) {   // (exactly one lane holds each)
-    fb = fmaxf(fb, __shfl_xor(fb, o));
-    fl = fmaxf(fl, __shfl_xor(fl, o));
-  }
+  const float2 f = Tp > 0 ? final_states(ab, al, L, lane) : make_float2(kNegInf, kNegInf);   // (Tp is uniform over the wave)
+  const float fb = f.x, fl = f.y;
   const float fin = fmaxf(fb, fl);
   const bool feasible = fin != kNegInf;
   __syncthreads();   // the back-pointer words of every lane are in place
@@ -454,7 +349,8 @@ int mgr_ctc_align(mgr_ctx* c, const float* P, const int32_t* labels, const int32
   const int ppl = (NP + 63) / 64;
   hipStream_t s = mgr_stream(c);
   mgr_prof_begin(c, MGR_K_CTC);
-  hipLaunchKernelGGL(k_align_emissions, dim3((unsigned)((align_ts(To) + 255) / 256), B), dim3(256), 0, s, P, input_len, T, C, skip, eps, L.E);
+  hipLaunchKernelGGL(k_lattice_emissions<false>, dim3((unsigned)((align_ts(To) + 255) / 256), B), dim3(256), 0, s, P, input_len, T, C, skip, eps,
+                     align_ts(To), L.E);
 #define MGR_ALIGN_LAUNCH(N)                                                                                                                \
   do {                                                                                                                                     \
     if (in_lds)                                                                                                                            \

@@ -18,59 +18,17 @@
 // are normalised by their own sum.
 // The gradient (k_ctc_grad) combines alpha+beta into per-class occupancies through an LDS row per thread and
 // chains through softmax(log(P+eps)) and the network's own softmax to dLogits.
+// The lattice's pieces - the base-2 log-sum-exp, the DPP shift and wave maximum, the pairs across the lanes, the chunked emission fetch,
+// the alpha step, the renormalisation, the final states - are in ctc_lattice.h, shared with align.hip and rescore.hip; the loops (alpha's
+// chunks start at t = 1 with the 3-float row offset; rows stored two steps at a time) and the beta step are this file's.
 // Vector-memory instructions of the serial chain (round 4; a wave that is alone with its chain pays 60-130 cycles of issue for
 // each): the emissions are stored CLASS-MAJOR, forward in time for alpha and reversed for beta, so that a lane fetches eight
 // steps of its label's (and the blank's) emissions with two 16-byte loads instead of 16 four-byte ones, and alpha / beta rows
 // are stored two time steps at a time (one 16-byte store per lane and pair of steps): ~1 instead of ~3 per step.
-#include "common.h"
+#include "ctc_lattice.h"
 
 namespace {
 
-constexpr float kNegInf = -__builtin_huge_valf();
-
-// The recursions run in BASE-2 log units (round 6): log2 y emissions, log2 alpha / beta, so that a log-sum-exp is v_exp_f32 / v_log_f32
-// on their own - no log2(e) / ln 2 multiplications, and none of logf's denormal-range and last-ulp fix-ups either: the argument of the
-// logarithm lies in [1, 3] (the largest term contributes exactly 1), where the raw instruction's 1 ulp is 1e-7 absolute on values that
-// are added to numbers of size O(10).  That was 30 of the 95 instructions of a step of the serial chain (12 for each logf).
-// All-(-inf) inputs (log 0): the maximum is floored at a huge finite negative number, x - floor stays -inf, 2^-inf = 0, log2 0 = -inf.
-constexpr float kLseFloor = -3.0e38f;
-constexpr double kLn2 = 0.693147180559945309417232121458;
-__device__ __forceinline__ float exp2_raw(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float log2_raw(float x) { return __builtin_amdgcn_logf(x); }
-__device__ __forceinline__ float lse2(float a, float b) {
-  const float m = fmaxf(fmaxf(a, b), kLseFloor);
-  return m + log2_raw(exp2_raw(a - m) + exp2_raw(b - m));
-}
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-  const float m = fmaxf(fmaxf(fmaxf(a, b), c), kLseFloor);
-  return m + log2_raw(exp2_raw(a - m) + exp2_raw(b - m) + exp2_raw(c - m));
-}
-
-// Cross-lane traffic of the recursions through DPP (one v_mov_b32_dpp, a few cycles) instead of __shfl_* (a ds_bpermute round trip
-// through the LDS crossbar, ~100 cycles, on the serial chain of every time step): wave_shr:1 / wave_shl:1 move a value to the
-// next / previous lane of the whole wave; lanes without a source receive `fill`.
-constexpr int DPP_WAVE_SHR1 = 0x138, DPP_WAVE_SHL1 = 0x130;
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v, float fill) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// wave-wide maximum: DPP within the rows of 16 lanes, then the four row results through v_readlane (uniform)
-__device__ __forceinline__ float wave_max_f32(float m) {
-  m = fmaxf(m, dpp_f32<0x111>(m, m));   // row_shr:1 (lanes without a source keep their own value)
-  m = fmaxf(m, dpp_f32<0x112>(m, m));
-  m = fmaxf(m, dpp_f32<0x114>(m, m));
-  m = fmaxf(m, dpp_f32<0x118>(m, m));   // lane 15 of a row holds the row's maximum
-  const int i = __float_as_int(m);
-  return fmaxf(fmaxf(__int_as_float(__builtin_amdgcn_readlane(i, 15)), __int_as_float(__builtin_amdgcn_readlane(i, 31))),
-               fmaxf(__int_as_float(__builtin_amdgcn_readlane(i, 47)), __int_as_float(__builtin_amdgcn_readlane(i, 63))));
-}
-
-template <int PPL>
-struct Chunk {
-  static constexpr int CH = PPL <= 2 ? 8 : 4;   // time steps per prefetched chunk (a multiple of 4: float4 loads along time)
-  float eb[CH];
-  float el[CH][PPL];
-};
 // row length of the class-major emission copies: T' + the over-read of two chunks + the 3-float offset that puts t = 1 on a
 // 16-byte boundary (alpha's chunks start at t = 1, 9, 17, ...)
 __host__ __device__ inline size_t ctc_ts(int To) { return ((size_t)To + 24 + 3) / 4 * 4; }
@@ -88,9 +46,7 @@ struct CtcSample {
 // the sample's labels into the workgroup's LDS (clipped into the class range)
 __device__ __forceinline__ void ctc_labels(const CtcSample& cs_, int tid, int nthreads, const int32_t* __restrict__ labels, int C, int Lmax) {
   for (int i = tid; i < Lmax; i += nthreads) {
-    int v = (i < cs_.L) ? labels[(size_t)cs_.b * Lmax + i] : -1;
-    v = v < 0 ? 0 : (v >= C ? C - 1 : v);
-    cs_.s_lab[i] = v;
+    cs_.s_lab[i] = clip_label((i < cs_.L) ? labels[(size_t)cs_.b * Lmax + i] : -1, C);
   }
 }
 // ---- phase 0: emissions log2 y(t,c) = log2(P+eps) - log2(sum_c (P+eps)), class-major, forward and reversed in time.  One frame per
@@ -102,11 +58,9 @@ __device__ __forceinline__ void ctc_phase0(const CtcSample& cs_, int tid, int bl
   const int t = blk * 256 + tid;
   if (t < Tp) {
     const float* row = P + ((size_t)b * T + skip + t) * C;
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += row[c] + eps;
-    float ls = log2f(s);
+    const float ls = frame_log_norm<true>(row, C, eps);
     for (int c = 0; c < C; ++c) {
-      const float v = log2f(row[c] + eps) - ls;   // (base-2 units, as everything the recursions touch)
+      const float v = emission_log<true>(row[c] + eps) - ls;   // (base-2 units, as everything the recursions touch)
       LYTb[(size_t)c * TS + t + 3] = v;
       LYRb[(size_t)c * TS + (Tp - 1 - t)] = v;
     }
@@ -131,26 +85,7 @@ __device__ __forceinline__ void ctc_phase1(const CtcSample& cs_, int role, int l
   float *LYTb = cs_.LYTb, *LYRb = cs_.LYRb, *ALb = cs_.ALb, *BEb = cs_.BEb;
   int* s_lab = cs_.s_lab;
   if (role < 2 && Tp > 0) {
-    int lab[PPL];
-    bool vl[PPL], vb[PPL], cs[PPL];
-#pragma unroll
-    for (int j = 0; j < PPL; ++j) {
-      int p = lane * PPL + j;
-      vl[j] = p < L;
-      vb[j] = p <= L;
-      lab[j] = vl[j] ? s_lab[p] : blank;
-    }
-    {
-      int prev_last = __shfl_up(lab[PPL - 1], 1);
-      bool prev_vl = __shfl_up((int)vl[PPL - 1], 1) != 0;
-#pragma unroll
-      for (int j = 0; j < PPL; ++j) {
-        int p = lane * PPL + j;
-        int pl = (j > 0) ? lab[j - 1] : prev_last;
-        bool pv = (j > 0) ? vl[j - 1] : (lane > 0 && prev_vl);
-        cs[j] = vl[j] && p >= 1 && pv && lab[j] != blank && lab[j] != pl;
-      }
-    }
+    const Pairs<PPL> pr(s_lab, L, blank, lane);
     if (role == 0) {
       float ab[PPL], al[PPL];
       float hb[PPL], hl[PPL];   // the even step of the pair in flight (rows are stored two steps at a time)
@@ -158,50 +93,24 @@ __device__ __forceinline__ void ctc_phase1(const CtcSample& cs_, int role, int l
       for (int j = 0; j < PPL; ++j) {
         int p = lane * PPL + j;
         ab[j] = (p == 0) ? LYTb[(size_t)blank * TS + 3] : kNegInf;
-        al[j] = (p == 0 && vl[j]) ? LYTb[(size_t)lab[j] * TS + 3] : kNegInf;
+        al[j] = (p == 0 && pr.vl[j]) ? LYTb[(size_t)pr.lab[j] * TS + 3] : kNegInf;
         hb[j] = ab[j];
         hl[j] = al[j];
         if (Tp == 1 && p <= Lmax) *reinterpret_cast<float2*>(ALb + 4 * p) = make_float2(ab[j], al[j]);
       }
-      Chunk<PPL> cur, nxt;
-      auto load = [&](Chunk<PPL>& ch, int t0) {   // steps t0 .. t0 + CH - 1 (t0 = 1 mod CH: 16-byte aligned; over-read stays in the row)
-        const float* rb = LYTb + (size_t)blank * TS + t0 + 3;
-#pragma unroll
-        for (int q = 0; q < CH / 4; ++q) {
-          const float4 v = *reinterpret_cast<const float4*>(rb + 4 * q);
-          ch.eb[4 * q] = v.x; ch.eb[4 * q + 1] = v.y; ch.eb[4 * q + 2] = v.z; ch.eb[4 * q + 3] = v.w;
-        }
-#pragma unroll
-        for (int j = 0; j < PPL; ++j) {
-          const float* rl = LYTb + (size_t)lab[j] * TS + t0 + 3;
-#pragma unroll
-          for (int q = 0; q < CH / 4; ++q) {
-            const float4 v = *reinterpret_cast<const float4*>(rl + 4 * q);
-            ch.el[4 * q][j] = v.x; ch.el[4 * q + 1][j] = v.y; ch.el[4 * q + 2][j] = v.z; ch.el[4 * q + 3][j] = v.w;
-          }
-        }
-      };
-      load(cur, 1);
+      Chunk<PPL> cur, nxt;   // steps t0 .. t0 + CH - 1, t0 = 1 mod CH: with the rows' 3-float offset 16-byte aligned
+      cur.load(LYTb + 3, TS, blank, pr.lab, 1);
       double coff = 0.0;
       int since = 0;
       for (int t0 = 1; t0 < Tp; t0 += CH) {
-        load(nxt, t0 + CH);
+        nxt.load(LYTb + 3, TS, blank, pr.lab, t0 + CH);
 #pragma unroll
         for (int k = 0; k < CH; ++k) {
           int t = t0 + k;
           if (t < Tp) {
-            const float carry = dpp_f32<DPP_WAVE_SHR1>(al[PPL - 1], kNegInf);   // (lane 0: log 0)
-            float nb[PPL], nl[PPL];
+            alpha_step(pr, ab, al, cur.eb[k], cur.el[k]);
 #pragma unroll
             for (int j = 0; j < PPL; ++j) {
-              float up = (j > 0) ? al[j - 1] : carry;
-              nb[j] = vb[j] ? cur.eb[k] + lse2(ab[j], up) : kNegInf;
-              nl[j] = vl[j] ? cur.el[k][j] + lse3(al[j], ab[j], cs[j] ? up : kNegInf) : kNegInf;
-            }
-#pragma unroll
-            for (int j = 0; j < PPL; ++j) {
-              ab[j] = nb[j];
-              al[j] = nl[j];
               int p = lane * PPL + j;
               if (t & 1) {          // the pair (t - 1, t) is complete: one 16-byte store
                 if (p <= Lmax) *reinterpret_cast<float4*>(ALb + ab_off(t - 1, S2) + 4 * p) = make_float4(hb[j], hl[j], ab[j], al[j]);
@@ -217,34 +126,12 @@ __device__ __forceinline__ void ctc_phase1(const CtcSample& cs_, int role, int l
         since += CH;
         if (since >= 16) {  // renormalise: keep the running log-values O(10)
           since = 0;
-          float m = kNegInf;
-#pragma unroll
-          for (int j = 0; j < PPL; ++j) m = fmaxf(m, fmaxf(ab[j], al[j]));
-          m = wave_max_f32(m);
-          if (m != kNegInf) {
-#pragma unroll
-            for (int j = 0; j < PPL; ++j) {
-              ab[j] -= m;
-              al[j] -= m;
-            }
-            coff += (double)m;
-          }
+          coff += (double)renorm(ab, al);
         }
       }
       // log p(l|x) = lse(alpha(2L, Tp-1), alpha(2L-1, Tp-1)) + accumulated offset
-      float fb = kNegInf, fl = kNegInf;
-#pragma unroll
-      for (int j = 0; j < PPL; ++j) {
-        int p = lane * PPL + j;
-        if (p == L) fb = ab[j];
-        if (p == L - 1) fl = al[j];
-      }
-      // reduce across lanes (exactly one lane holds each)
-      for (int o = 32; o > 0; o >>= 1) {
-        fb = fmaxf(fb, __shfl_xor(fb, o));
-        fl = fmaxf(fl, __shfl_xor(fl, o));
-      }
-      float lfin = lse2(fb, fl);
+      const float2 f = final_states(ab, al, L, lane);
+      float lfin = lse2(f.x, f.y);
       if (lane == 0) {
         // (+inf: no alignment fits - what k_ctc_grad reads as "no gradient")
         loss[b] = (lfin == kNegInf) ? __builtin_huge_valf() : (float)(-((double)lfin + coff) * kLn2);
@@ -253,9 +140,9 @@ __device__ __forceinline__ void ctc_phase1(const CtcSample& cs_, int role, int l
       float bb[PPL], bl[PPL];
       bool csn[PPL];  // can_skip of pair p+1
       {
-        int nfirst = __shfl_down((int)cs[0], 1);
+        int nfirst = __shfl_down((int)pr.cs[0], 1);
 #pragma unroll
-        for (int j = 0; j < PPL; ++j) csn[j] = (j < PPL - 1) ? cs[j + 1] : (lane < 63 && nfirst != 0);
+        for (int j = 0; j < PPL; ++j) csn[j] = (j < PPL - 1) ? pr.cs[j + 1] : (lane < 63 && nfirst != 0);
       }
       float hb[PPL], hl[PPL];   // the odd step of the pair in flight (beta walks down: t + 1 comes before t)
 #pragma unroll
@@ -269,29 +156,13 @@ __device__ __forceinline__ void ctc_phase1(const CtcSample& cs_, int role, int l
         if (((Tp - 1) & 1) == 0 && p <= Lmax) *reinterpret_cast<float2*>(BEb + ab_off(Tp - 1, S2) + 4 * p) = make_float2(bb[j], bl[j]);
       }
       Chunk<PPL> cur, nxt;
-      // step index n = 0.. walks t = Tp-2-n; uses emissions at t+1 = Tp-1-n = reversed index n
-      auto load = [&](Chunk<PPL>& ch, int n0) {   // reversed steps n0 .. n0 + CH - 1 (n0 = 0 mod CH: aligned)
-        const float* rb = LYRb + (size_t)blank * TS + n0;
-#pragma unroll
-        for (int q = 0; q < CH / 4; ++q) {
-          const float4 v = *reinterpret_cast<const float4*>(rb + 4 * q);
-          ch.eb[4 * q] = v.x; ch.eb[4 * q + 1] = v.y; ch.eb[4 * q + 2] = v.z; ch.eb[4 * q + 3] = v.w;
-        }
-#pragma unroll
-        for (int j = 0; j < PPL; ++j) {
-          const float* rl = LYRb + (size_t)lab[j] * TS + n0;
-#pragma unroll
-          for (int q = 0; q < CH / 4; ++q) {
-            const float4 v = *reinterpret_cast<const float4*>(rl + 4 * q);
-            ch.el[4 * q][j] = v.x; ch.el[4 * q + 1][j] = v.y; ch.el[4 * q + 2][j] = v.z; ch.el[4 * q + 3][j] = v.w;
-          }
-        }
-      };
-      load(cur, 0);
+      // step index n = 0.. walks t = Tp-2-n; uses emissions at t+1 = Tp-1-n = reversed index n: a chunk is the reversed steps
+      // n0 .. n0 + CH - 1 (n0 = 0 mod CH: aligned)
+      cur.load(LYRb, TS, blank, pr.lab, 0);
       const int nsteps = Tp - 1;
       int since = 0;
       for (int n0 = 0; n0 < nsteps; n0 += CH) {
-        load(nxt, n0 + CH);
+        nxt.load(LYRb, TS, blank, pr.lab, n0 + CH);
 #pragma unroll
         for (int k = 0; k < CH; ++k) {
           int n = n0 + k;
@@ -300,8 +171,8 @@ __device__ __forceinline__ void ctc_phase1(const CtcSample& cs_, int role, int l
             float xb[PPL], xl[PPL];  // beta(.,t+1) + emission(.,t+1)
 #pragma unroll
             for (int j = 0; j < PPL; ++j) {
-              xb[j] = vb[j] ? bb[j] + cur.eb[k] : kNegInf;
-              xl[j] = vl[j] ? bl[j] + cur.el[k][j] : kNegInf;
+              xb[j] = pr.vb[j] ? bb[j] + cur.eb[k] : kNegInf;
+              xl[j] = pr.vl[j] ? bl[j] + cur.el[k][j] : kNegInf;
             }
             const float nxb = dpp_f32<DPP_WAVE_SHL1>(xb[0], kNegInf);   // (lane 63: log 0)
             const float nxl = dpp_f32<DPP_WAVE_SHL1>(xl[0], kNegInf);
@@ -309,8 +180,8 @@ __device__ __forceinline__ void ctc_phase1(const CtcSample& cs_, int role, int l
             for (int j = 0; j < PPL; ++j) {
               float b1 = (j < PPL - 1) ? xb[j + 1] : nxb;  // blank of pair p+1 (state u+1 for the label state)
               float l1 = (j < PPL - 1) ? xl[j + 1] : nxl;  // label of pair p+1 (state u+2)
-              bb[j] = vb[j] ? lse2(xb[j], xl[j]) : kNegInf;
-              bl[j] = vl[j] ? lse3(xl[j], b1, csn[j] ? l1 : kNegInf) : kNegInf;
+              bb[j] = pr.vb[j] ? lse2(xb[j], xl[j]) : kNegInf;
+              bl[j] = pr.vl[j] ? lse3(xl[j], b1, csn[j] ? l1 : kNegInf) : kNegInf;
               int p = lane * PPL + j;
               if (t & 1) {          // first half of the pair (t - 1, t) to arrive: keep it (or store it alone at t = ... never: t >= 0 even ends)
                 hb[j] = bb[j];
@@ -325,17 +196,7 @@ __device__ __forceinline__ void ctc_phase1(const CtcSample& cs_, int role, int l
         since += CH;
         if (since >= 16) {
           since = 0;
-          float m = kNegInf;
-#pragma unroll
-          for (int j = 0; j < PPL; ++j) m = fmaxf(m, fmaxf(bb[j], bl[j]));
-          m = wave_max_f32(m);
-          if (m != kNegInf) {
-#pragma unroll
-            for (int j = 0; j < PPL; ++j) {
-              bb[j] -= m;
-              bl[j] -= m;
-            }
-          }
+          renorm(bb, bl);   // (no offset kept: the gradient normalises every frame by its own sum)
         }
       }
     }

@@ -15,15 +15,14 @@
 // lane as 16 bytes.  They live in LDS when they fit beside the rows and in the workspace otherwise.  The backtrace from (m, n) is a
 // chain of m + n dependent steps at most: every lane runs it with wave-uniform values (scalar instructions, see align.hip), the
 // ops land in LDS back to front (their number, n + I, is known from the final key) and leave with one parallel copy.
-#include "common.h"
+#include "ctc_lattice.h"
 
 namespace {
 
 typedef long long i64;
 constexpr i64 kInf = 0x7fffffffffffffffLL;
 
-// cross-lane traffic through DPP (see ctc.hip, align.hip), restated here for 64-bit keys: two v_mov_b32_dpp
-constexpr int DPP_WAVE_SHR1 = 0x138;
+// cross-lane traffic through DPP (the control codes and the reasons: ctc_lattice.h), here for 64-bit keys: two v_mov_b32_dpp
 template <int CTRL>
 __device__ __forceinline__ i64 dpp_i64(i64 v, i64 fill) {   // lanes without a source get fill
   const int lo = __builtin_amdgcn_update_dpp((int)(unsigned)(fill & 0xffffffffLL), (int)(unsigned)(v & 0xffffffffLL), CTRL, 0xf, 0xf, false);
@@ -39,10 +38,10 @@ __device__ __forceinline__ i64 readlane_i64(i64 v, int l) {
 // EXCLUSIVE prefix minimum over the wave (lane 0: kInf): row_shr 1, 2, 4, 8 inside the rows of 16 lanes, the three row totals
 // through v_readlane, one wave_shr:1
 __device__ __forceinline__ i64 wave_excl_min(i64 x, int lane) {
-  x = min_i64(x, dpp_i64<0x111>(x, x));
-  x = min_i64(x, dpp_i64<0x112>(x, x));
-  x = min_i64(x, dpp_i64<0x114>(x, x));
-  x = min_i64(x, dpp_i64<0x118>(x, x));
+  x = min_i64(x, dpp_i64<DPP_ROW_SHR1>(x, x));
+  x = min_i64(x, dpp_i64<DPP_ROW_SHR2>(x, x));
+  x = min_i64(x, dpp_i64<DPP_ROW_SHR4>(x, x));
+  x = min_i64(x, dpp_i64<DPP_ROW_SHR8>(x, x));
   const i64 t0 = readlane_i64(x, 15);
   const i64 t1 = min_i64(t0, readlane_i64(x, 31));
   const i64 t2 = min_i64(t1, readlane_i64(x, 47));
@@ -55,8 +54,6 @@ __device__ __forceinline__ i64 wave_excl_min(i64 x, int lane) {
 __host__ __device__ inline int edit_cpl(int n) { return (n + 1 + 63) / 64; }   // columns per lane for n ref labels
 // back-pointer bytes of one pair at the widths (Lh rows of cpl(Lr) x 16 bytes)
 __host__ __device__ inline size_t edit_bp_bytes(int Lh, int Lr) { return (size_t)Lh * edit_cpl(Lr) * 16; }
-
-__device__ __forceinline__ int clip_len(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // a row -> its surviving labels, in order, in LDS; returns their number (wave-uniform)
 __device__ __forceinline__ int edit_filter(const int32_t* __restrict__ row, int len, uint64_t ignore_mask, int* dst, int lane) {

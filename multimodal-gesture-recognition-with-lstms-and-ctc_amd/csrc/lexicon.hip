@@ -6,12 +6,12 @@
 //   state 0 = INIT (blank before any phrase), state 2j + 1 = the word j, state 2j + 2 = the blank behind word j: B(g, k) inside a
 //   phrase, Z(g) behind its last word - the extended label sequence of ctc.hip / align.hip over the concatenated lexicon, in which
 //   the step onto a phrase's FIRST word does not come from the neighbouring states but from INIT, every Z(g') and every last word.
-// Two kernels: emissions (class-major rows, the layout of align.hip's), then ONE WORKGROUP per sample with a state per thread (64 ..
-// 512 threads).  A frame is one barrier: every thread reads its two neighbours' values of the previous frame from LDS (two buffers,
-// swapped per frame), a phrase-entry thread also the G pairs (Z(g'), last word of g') - kept beside the state values as one 8-byte
-// entry per phrase, a broadcast read - and its column of ext (f32, LDS, consecutive lanes consecutive words; kept twice, the second
-// copy with -inf where the last word of g' equals the first word of g): G^2 candidates per frame spread over the G entry threads.
-// Emissions are fetched four frames at a time with 16-byte loads, a chunk ahead.
+// Two kernels: emissions (k_lattice_emissions of ctc_lattice.h in natural-log units: class-major rows), then ONE WORKGROUP per sample
+// with a state per thread (64 .. 512 threads).  A frame is one barrier: every thread reads its two neighbours' values of the previous
+// frame from LDS (two buffers, swapped per frame), a phrase-entry thread also the G pairs (Z(g'), last word of g') - kept beside the
+// state values as one 8-byte entry per phrase, a broadcast read - and its column of ext (f32, LDS, consecutive lanes consecutive
+// words; kept twice, the second copy with -inf where the last word of g' equals the first word of g): G^2 candidates per frame spread
+// over the G entry threads.  Emissions are fetched four frames at a time with 16-byte loads, a chunk ahead.
 // Back-pointers: 2 bits per frame for every state but the phrase entries (stay, from s - 1, from s - 2), sixteen frames to a word:
 // ceil(To / 16) * N words; a byte per frame for a phrase entry (0 stay, 1 INIT, 2 + 2g' from Z(g'), 3 + 2g' from the last word of g'),
 // four frames to a word: ceil(To / 4) * G words - 46 KB + 40 KB at the reference's lexicon (97 states, 21 phrases) and 1898 frames.
@@ -25,26 +25,18 @@
 // 1900-frame path does not sit where an f32 ulp is 5e-4.
 // Ties: the smaller back-pointer code wins (stay, then one state, then two; for a phrase entry stay, INIT, then the phrases in
 // order, Z(g') before the last word of g'); among the final states the smallest state index.
-#include "common.h"
+#include "ctc_lattice.h"
 
 namespace {
 
-constexpr float kNegInf = -__builtin_huge_valf();
 constexpr int MAXG = MGR_LEXICON_MAX_PHRASES;
 constexpr size_t kLdsMax = 160 * 1024;
-
-// the lexicon travels as a kernel argument: word ids are below 64, offsets at most 255
-struct LexArg {
-  uint8_t off[MAXG + 1];
-  uint8_t words[MGR_LEXICON_MAX_WORDS + 1];
-};
 
 // row length of the class-major emissions: To + the over-read of the chunk fetched ahead, a multiple of 4 floats
 __host__ __device__ inline size_t lex_ts(int To) { return ((size_t)To + 8 + 3) / 4 * 4; }
 __host__ __device__ inline int lex_nb16(int To) { return (To + 15) / 16; }
 __host__ __device__ inline int lex_nb4(int To) { return (To + 3) / 4; }
 __host__ __device__ inline int lex_gp(int G) { return (G + 3) & ~3; }   // phrases rounded up to the entry loop's four per turn
-__device__ __forceinline__ int clip_len(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // LDS of the decode kernel, in 32-bit words
 struct LexLds { size_t red, x, vb, ext, scan, wred, off, cls, ent, state, starts, bp2, bpe, words; };
@@ -66,27 +58,6 @@ __host__ __device__ inline LexLds lex_lds(int NT, int G, int N, int To, bool wit
   L.bpe = o;    o += with_bp ? (size_t)lex_nb4(To) * G : 0;
   L.words = o;
   return L;
-}
-
-// emissions ln y(t, c) = ln(P + eps) - ln(sum_c (P + eps)), class-major: E[b][c][TS] (k_align_emissions' layout with this file's row
-// length).  One frame per thread; the frames of a row behind the sample's length (the prefetch reads them and uses none) are zeros.
-__global__ __launch_bounds__(256) void k_lexicon_emissions(const float* __restrict__ P, const int32_t* __restrict__ input_len, int T, int C,
-                                                           int skip, float eps, float* __restrict__ E) {
-  const int b = blockIdx.y, To = T - skip;
-  const size_t TS = lex_ts(To);
-  const int Tp = clip_len(input_len[b], To);
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if ((size_t)t >= TS) return;
-  float* Eb = E + (size_t)b * C * TS;
-  if (t >= Tp) {
-    for (int c = 0; c < C; ++c) Eb[(size_t)c * TS + t] = 0.f;
-    return;
-  }
-  const float* row = P + ((size_t)b * T + skip + t) * C;
-  float s = 0.f;
-  for (int c = 0; c < C; ++c) s += row[c] + eps;
-  const float ls = logf(s);
-  for (int c = 0; c < C; ++c) Eb[(size_t)c * TS + t] = logf(row[c] + eps) - ls;
 }
 
 __device__ __forceinline__ double shfl_xor_d(double v, int o) {
@@ -437,21 +408,10 @@ int mgr_ctc_lexicon_decode(mgr_ctx* c, const float* P, const int32_t* input_len,
   MGR_REQUIRE(blank >= 0 && blank < C, "blank %d out of range", blank);
   MGR_REQUIRE(G >= 1 && G <= MGR_LEXICON_MAX_PHRASES, "G = %d phrases out of [1, %d]", G, MGR_LEXICON_MAX_PHRASES);
   MGR_REQUIRE(T - skip <= MGR_SEGMENTS_MAX_FRAMES, "T - skip = %d too large (max %d)", T - skip, MGR_SEGMENTS_MAX_FRAMES);
-  // the lexicon is host memory: checked here, entry by entry
-  MGR_REQUIRE(phrase_off[0] == 0, "phrase_off[0] = %d, not 0", phrase_off[0]);
   LexArg lex;
   memset(&lex, 0, sizeof(lex));
-  for (int g = 0; g < G; ++g) {
-    MGR_REQUIRE(phrase_off[g + 1] > phrase_off[g], "phrase %d is empty", g);
-    MGR_REQUIRE(phrase_off[g + 1] <= MGR_LEXICON_MAX_WORDS, "the lexicon has more than %d words", MGR_LEXICON_MAX_WORDS);
-    lex.off[g + 1] = (uint8_t)phrase_off[g + 1];
-  }
+  if (const int rc = lex_arg_pack(&lex, phrase_off, phrase_words, G, C, blank)) return rc;
   const int nw = phrase_off[G];
-  for (int j = 0; j < nw; ++j) {
-    MGR_REQUIRE(phrase_words[j] >= 0 && phrase_words[j] < C && phrase_words[j] != blank, "word %d of the lexicon is %d: not a non-blank class", j,
-                phrase_words[j]);
-    lex.words[j] = (uint8_t)phrase_words[j];
-  }
   MGR_REQUIRE(ws && ws_bytes >= mgr_ctc_lexicon_ws_bytes(B, T, C, G, phrase_off), "workspace too small");
   const int To = T - skip, N = 1 + 2 * nw, NT = (N + 63) / 64 * 64;
   const LexWs W = lex_ws_layout(ws, B, T, C, G, nw);
@@ -466,7 +426,8 @@ int mgr_ctc_lexicon_decode(mgr_ctx* c, const float* P, const int32_t* input_len,
   }
   hipStream_t s = mgr_stream(c);
   mgr_prof_begin(c, MGR_K_MISC);
-  hipLaunchKernelGGL(k_lexicon_emissions, dim3((unsigned)((lex_ts(To) + 255) / 256), B), dim3(256), 0, s, P, input_len, T, C, skip, eps, W.E);
+  hipLaunchKernelGGL(k_lattice_emissions<false>, dim3((unsigned)((lex_ts(To) + 255) / 256), B), dim3(256), 0, s, P, input_len, T, C, skip, eps, lex_ts(To),
+                     W.E);
   if (in_lds)
     hipLaunchKernelGGL(k_lexicon_decode<true>, dim3(B), dim3(NT), lds_full, s, P, input_len, T, C, skip, blank, lex, G, nw, ext, fin, cap, W.E,
                        W.bp2, W.bpe, n_phr, phr, seg, conf, path, score, logp);
