@@ -11,11 +11,9 @@
 // The Keras per-gate input-dropout masks are folded into the B-operand staging (nn, nt: one sample per row
 // tile) or the epilogue (tn), so no masked copy of X is ever materialised.  The gate of a packed column is col&3.
 #include "common.h"
+#include "split_f16.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef MGR_GEMM_BK
 #define MGR_GEMM_BK 16
@@ -161,18 +159,7 @@ __device__ __forceinline__ void mma_stage(const float (*As)[LDS_LD], const float
   }
 }
 
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-}
-
-// accumulator element -> (row, col) inside the 128x128 tile
-#define ACC_ROW(wr, mt, reg, lane) ((wr) * 64 + (mt) * 32 + ((reg) & 3) + 8 * ((reg) >> 2) + 4 * ((lane) >> 5))
-#define ACC_COL(wc, nt, lane) ((wc) * 64 + (nt) * 32 + ((lane) & 31))
+// (accumulator element -> (row, col) inside the 128x128 tile: acc_row / acc_col of split_f16.h from the block origin wr * 64 + mt * 32)
 
 // ------------------------------------------------------------------------------------------------ nn
 // grid: (ceil(N/128), ceil(T/128), B)
@@ -248,11 +235,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nn(const float* __restrict__ X,
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      int col = n0 + ACC_COL(wc, nt, lane);
+      int col = n0 + acc_col(wc * 64 + nt * 32, lane & 31);
       float bias = (col < N) ? bp[col] : 0.f;
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        int r = r0 + ACC_ROW(wr, mt, reg, lane);
+        int r = r0 + acc_row(wr * 64 + mt * 32, reg, lane >> 5);
         if (r < T && col < N) Z[((size_t)b * T + r) * N + col] = acc[mt][nt][reg] + bias;
       }
     }
@@ -320,14 +307,14 @@ __global__ __launch_bounds__(256, 4) void k_gemm_nn2(const float* __restrict__ X
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      int col = n0 + ACC_COL(wc, nt, lane);
+      int col = n0 + acc_col(wc * 64 + nt * 32, lane & 31);
       const bool second = col >= Nd;
       const int cd = second ? col - Nd : col;
       float* Zd = second ? Z2 : Z;
       float bias = (col < 2 * Nd) ? (second ? bp2 : bp)[cd] : 0.f;
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        int r = r0 + ACC_ROW(wr, mt, reg, lane);
+        int r = r0 + acc_row(wr * 64 + mt * 32, reg, lane >> 5);
         if (r < T && col < 2 * Nd) Zd[((size_t)b * T + r) * Nd + cd] = acc[mt][nt][reg] + bias;
       }
     }
@@ -473,25 +460,19 @@ __global__ __launch_bounds__(128 * WC, WC == 2 ? 2 : 1) void k_gemm_nn_sparse(co
     float a[APT], w[4], v[4];
   };
   static_assert(APT == RPT * 4, "both A staging forms hold TM * SK / NT elements per thread");
-  // Workgroup -> tile, XCD-aware: consecutive workgroup ids go round-robin over the 8 XCDs (each with its own L2), so the
-  // ncol workgroups that share one (sample, row tile) of X - and read it four times each, once per gate pass - are the ids
-  // x, x + 8, x + 16, ...: they meet in ONE L2 instead of pulling the same rows into all eight.
+  // Workgroup -> tile, XCD-aware (xcd_tile): the ncol workgroups that share one (sample, row tile) of X - and read it four times
+  // each, once per gate pass - meet in ONE L2.
   {
-    const int x = blockIdx.x & 7, jj = blockIdx.x >> 3;
-    const int rt = (jj / ncol) * 8 + x;   // linear (sample, row tile)
+    const XcdTile wt = xcd_tile(blockIdx.x, ncol);
+    const int rt = wt.group;   // linear (sample, row tile)
     if (rt >= nrow * B) return;
-    const int u0 = (jj % ncol) * TU, r0 = (rt % nrow) * TM, b = rt / nrow;
+    const int u0 = wt.item * TU, r0 = (rt % nrow) * TM, b = rt / nrow;
     // TR: X is the transposed copy XT[b][f][t] (row stride ldx = padded T): a kept feature is a contiguous row of time steps, the
     // 64 threads of a quad read 256 contiguous bytes of it; else X[b][t][f]: a kept feature is a column (scattered 4-byte loads)
     const float* Xb = TR ? X + (size_t)b * F * ldx + r0 + r : X + (size_t)b * T * ldx;
     const int ucl = (u0 + r < H) ? u0 + r : H - 1;
     f32x16 acc[4][2];
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[g][mt][e] = 0.f;
+    zero_acc(acc);
     int arow[APT];   // row-major input: element offsets of this thread's rows (clamped: rows >= T are computed but never stored)
 #pragma unroll
     for (int i = 0; i < APT; ++i) {
@@ -580,20 +561,10 @@ __global__ __launch_bounds__(128 * WC, WC == 2 ? 2 : 1) void k_gemm_nn_sparse(co
         }
       }
     }
-    const int unit = u0 + wc * 32 + l31;
+    const int unit = acc_col(u0 + wc * 32, l31);
     if (unit < H) {
       const float4 bias = *reinterpret_cast<const float4*>(bp + unit * 4);
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int row = r0 + wr * 64 + mt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-          if (row < T) {
-            typedef float nt_f4 __attribute__((ext_vector_type(4)));
-            const nt_f4 v = {acc[0][mt][reg] + bias.x, acc[1][mt][reg] + bias.y, acc[2][mt][reg] + bias.z, acc[3][mt][reg] + bias.w};
-            __builtin_nontemporal_store(v, reinterpret_cast<nt_f4*>(Z + ((size_t)b * T + row) * N + unit * 4));
-          }
-        }
+      store_z_tile<true>(acc, 1.f, bias, Z, b, T, N, r0 + wr * 64, unit, lh);   // (non-temporal; f32 sums: nothing to unscale)
     }
   }
 }
@@ -642,10 +613,10 @@ __global__ __launch_bounds__(256, XR > 20 ? 1 : 2) void k_proj_narrow(const floa
   const int N = 4 * H;
   const int ncol = (H + TU - 1) / TU, nrow = (T + TM - 1) / TM, nchunk = (nrow + NP_RPW - 1) / NP_RPW;
   // workgroup -> (sample, chunk of row tiles, unit tile), XCD-aware as in k_gemm_nn_sparse: the unit tiles that share X rows meet in one L2
-  const int x = blockIdx.x & 7, jj = blockIdx.x >> 3;
-  const int rc = (jj / ncol) * 8 + x;
+  const XcdTile wt = xcd_tile(blockIdx.x, ncol);
+  const int rc = wt.group;
   if (rc >= nchunk * B) return;
-  const int u0 = (jj % ncol) * TU, b = rc / nchunk, rt0 = (rc % nchunk) * NP_RPW;
+  const int u0 = wt.item * TU, b = rc / nchunk, rt0 = (rc % nchunk) * NP_RPW;
   const int rt1 = rt0 + NP_RPW < nrow ? rt0 + NP_RPW : nrow;
   {   // the list of gate `wave`: lane = feature
     const int Fp = (F + SP_SK - 1) / SP_SK * SP_SK;
@@ -729,12 +700,7 @@ __global__ __launch_bounds__(256, XR > 20 ? 1 : 2) void k_proj_narrow(const floa
     __syncthreads();
     if (rt + 1 < rt1) xload(rt + 1);
     f32x16 acc[4][2];
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[g][mt][e] = 0.f;
+    zero_acc(acc);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int nst = (Lc[g] + SP_SK - 1) / SP_SK;
@@ -751,19 +717,7 @@ __global__ __launch_bounds__(256, XR > 20 ? 1 : 2) void k_proj_narrow(const floa
         }
       }
     }
-    if (unit < H) {
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int row = r0 + wr * 64 + mt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-          if (row < T) {
-            typedef float nt_f4 __attribute__((ext_vector_type(4)));
-            const nt_f4 v = {acc[0][mt][reg] + bias.x, acc[1][mt][reg] + bias.y, acc[2][mt][reg] + bias.z, acc[3][mt][reg] + bias.w};
-            __builtin_nontemporal_store(v, reinterpret_cast<nt_f4*>(Z + ((size_t)b * T + row) * N + unit * 4));
-          }
-        }
-    }
+    if (unit < H) store_z_tile<true>(acc, 1.f, bias, Z, b, T, N, r0 + wr * 64, unit, lh);   // (non-temporal, as k_gemm_nn_sparse)
   }
 }
 
@@ -772,24 +726,13 @@ __global__ __launch_bounds__(256, XR > 20 ? 1 : 2) void k_proj_narrow(const floa
 // kept features, 16 list positions per stage) on the f16 matrix pipe (round 4): every f32 operand goes to LDS as an f16 (hi, lo)
 // pair of its scaled value - x sx = hi + lo to 22+ bits - and a stage is THREE v_mfma_f32_32x32x16_f16 per 32 x 32 block
 // (hi hi + lo hi + hi lo, f32 accumulation; the dropped lo lo term is 2^-22 of the product) instead of sixteen
-// v_mfma_f32_32x32x2_f32: 96 instead of 1024 matrix-pipe cycles per stage and block.  See lstm_cluster.hip (cluster_run_k16) for the
-// error argument; the parity tests hold both kernels to the same bounds against the f64 oracle.
+// v_mfma_f32_32x32x2_f32: 96 instead of 1024 matrix-pipe cycles per stage and block.  The split, the scale and the three-MFMA product are
+// split_f16.h's; see lstm_cluster.hip (cluster_run_k16) for the error argument; the parity tests hold both kernels to the same bounds
+// against the f64 oracle.
 // Scales (powers of two, so scaling is exact): sx from the caller's bound on |X| (activations of LSTM layers: 1, with a residual
 // sum 2), sw from the largest |W| of the call (k_gate_major) times the largest mask factor 1 / (1 - p); the largest scaled magnitude
 // lies in [2^14, 2^15).  An input beyond the stated bound overflows f16 and shows as Inf / NaN in Z - never silently.
 // List position p = q + 4c of a stage (quad q, slot c: the staging threads' order) is MFMA k-slot (half q >> 1, element 4 (q & 1) + c).
-typedef _Float16 f16x8_ __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4_ __attribute__((ext_vector_type(4)));
-// x = hi + lo, both f16: hi = rn(x), lo = rn(x - hi), x an f32 VALUE.  The empty asm pins that value: without it hipcc contracts a
-// product that feeds x into the subtraction (v_fma_mix: exact product - hi') AND takes that hi' by rounding the exact product to
-// f16 in one step, while the hi it stores was rounded from the f32 product - two different roundings of x now and then, i.e. a lo
-// that belongs to another hi: one operand in a few hundred with 11 instead of 22 bits (seen with the mask factor 2.5; a power-of-two
-// factor makes the product exact and hides it).
-__device__ __forceinline__ void mgr_split_f16(float x, _Float16& hi, _Float16& lo) {
-  asm volatile("" : "+v"(x));
-  hi = (_Float16)x;
-  lo = (_Float16)(x - (float)hi);
-}
 __global__ __launch_bounds__(256, 2) void k_gemm_nn_sparse16(const float* __restrict__ X, int ldx, const int* __restrict__ kidx,
                                                              const float* __restrict__ kval, const int* __restrict__ kcnt,
                                                              const float* __restrict__ Wp, const float* __restrict__ bp,
@@ -806,31 +749,19 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nn_sparse16(const float* __rest
   const int q = tid / QT, r = tid % QT;
   const int l31 = lane & 31, lh = lane >> 5;
   const int ncol = (H + TU - 1) / TU, nrow = (T + TM - 1) / TM;
-  float sw = 1.f;
-  {
-    const float m = __uint_as_float(*wmax) * vmax;
-    int ex = 0;
-    if (m > 0.f && m < 3.0e38f) (void)frexpf(m, &ex);
-    ex = ex < -60 ? -60 : ex;
-    sw = m < 3.0e38f ? ldexpf(1.f, 15 - ex) : 0.f;
-  }
-  const float inv = sw > 0.f ? 1.f / (sw * sx) : __uint_as_float(0x7FC00000u);
+  const float sw = split_scale<SPLIT_NONFINITE_ZERO>(__uint_as_float(*wmax) * vmax, -60);   // (an Inf weight: scale 0, Z is NaN - visible)
+  const float inv = split_unscale(1.f, sw, sx);
   struct Regs {
     float a[RPT * 4], w[4], v[4];
   };
-  const int x = blockIdx.x & 7, jj = blockIdx.x >> 3;   // XCD-aware tile order: see k_gemm_nn_sparse
-  const int rt = (jj / ncol) * 8 + x;
+  const XcdTile wt = xcd_tile(blockIdx.x, ncol);   // (the column tiles of one (sample, row tile) meet in one L2)
+  const int rt = wt.group;
   if (rt >= nrow * B) return;
-  const int u0 = (jj % ncol) * TU, r0 = (rt % nrow) * TM, b = rt / nrow;
+  const int u0 = wt.item * TU, r0 = (rt % nrow) * TM, b = rt / nrow;
   const float* Xb = X + (size_t)b * F * ldx + r0 + r;
   const int ucl = (u0 + r < H) ? u0 + r : H - 1;
   f32x16 acc[4][2];
-#pragma unroll
-  for (int g = 0; g < 4; ++g)
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[g][mt][e] = 0.f;
+  zero_acc(acc);
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     const int nst1 = (kcnt[g * B + b] + SK - 1) / SK;
@@ -861,40 +792,29 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nn_sparse16(const float* __rest
         for (int i = 0; i < RPT; ++i) R.a[i * 4 + c] = Xb[(size_t)f * ldx + QT * i];
       }
     };
-    auto split4 = [](const float (&xs)[4], f16x4_& hi, f16x4_& lo) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        _Float16 h, l;
-        mgr_split_f16(xs[c], h, l);
-        hi[c] = h;
-        lo[c] = l;
-      }
-    };
     auto stash = [&](const Regs& R, int buf) {
-      f16x4_ hi, lo;
+      f16x4 hi, lo;
 #pragma unroll
       for (int i = 0; i < RPT; ++i) {
         const float xs[4] = {R.a[i * 4] * sx, R.a[i * 4 + 1] * sx, R.a[i * 4 + 2] * sx, R.a[i * 4 + 3] * sx};
-        split4(xs, hi, lo);
-        *reinterpret_cast<f16x4_*>(&Ah[buf][q >> 1][r + QT * i][(q & 1) * 4]) = hi;
-        *reinterpret_cast<f16x4_*>(&Al[buf][q >> 1][r + QT * i][(q & 1) * 4]) = lo;
+        split_f16_vec<4>(xs, hi, lo);
+        *reinterpret_cast<f16x4*>(&Ah[buf][q >> 1][r + QT * i][(q & 1) * 4]) = hi;
+        *reinterpret_cast<f16x4*>(&Al[buf][q >> 1][r + QT * i][(q & 1) * 4]) = lo;
       }
       const float ws[4] = {R.w[0] * R.v[0] * sw, R.w[1] * R.v[1] * sw, R.w[2] * R.v[2] * sw, R.w[3] * R.v[3] * sw};
-      split4(ws, hi, lo);
-      *reinterpret_cast<f16x4_*>(&Bh[buf][q >> 1][r][(q & 1) * 4]) = hi;
-      *reinterpret_cast<f16x4_*>(&Bl[buf][q >> 1][r][(q & 1) * 4]) = lo;
+      split_f16_vec<4>(ws, hi, lo);
+      *reinterpret_cast<f16x4*>(&Bh[buf][q >> 1][r][(q & 1) * 4]) = hi;
+      *reinterpret_cast<f16x4*>(&Bl[buf][q >> 1][r][(q & 1) * 4]) = lo;
     };
     auto mma = [&](int buf) {
       const int ra = wr * 64 + l31, ub = wc * 32 + l31;
-      const f16x8_ bh = *reinterpret_cast<const f16x8_*>(&Bh[buf][lh][ub][0]);
-      const f16x8_ bl = *reinterpret_cast<const f16x8_*>(&Bl[buf][lh][ub][0]);
+      const f16x8 bh = *reinterpret_cast<const f16x8*>(&Bh[buf][lh][ub][0]);
+      const f16x8 bl = *reinterpret_cast<const f16x8*>(&Bl[buf][lh][ub][0]);
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
-        const f16x8_ ah = *reinterpret_cast<const f16x8_*>(&Ah[buf][lh][ra + 32 * mt][0]);
-        const f16x8_ al = *reinterpret_cast<const f16x8_*>(&Al[buf][lh][ra + 32 * mt][0]);
-        acc[g][mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[g][mt], 0, 0, 0);
-        acc[g][mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[g][mt], 0, 0, 0);
-        acc[g][mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[g][mt], 0, 0, 0);
+        const f16x8 ah = *reinterpret_cast<const f16x8*>(&Ah[buf][lh][ra + 32 * mt][0]);
+        const f16x8 al = *reinterpret_cast<const f16x8*>(&Al[buf][lh][ra + 32 * mt][0]);
+        mfma3_split(ah, al, bh, bl, acc[g][mt]);
       }
     };
     if (nst > 0) {
@@ -915,19 +835,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nn_sparse16(const float* __rest
       }
     }
   }
-  const int unit = u0 + wc * 32 + l31;
+  const int unit = acc_col(u0 + wc * 32, l31);
   if (unit < H) {
     const float4 bias = *reinterpret_cast<const float4*>(bp + unit * 4);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int row = r0 + wr * 64 + mt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-        if (row < T)
-          *reinterpret_cast<float4*>(Z + ((size_t)b * T + row) * N + unit * 4) =
-              make_float4(fmaf(acc[0][mt][reg], inv, bias.x), fmaf(acc[1][mt][reg], inv, bias.y), fmaf(acc[2][mt][reg], inv, bias.z),
-                          fmaf(acc[3][mt][reg], inv, bias.w));
-      }
+    store_z_tile<false>(acc, inv, bias, Z, b, T, N, r0 + wr * 64, unit, lh);   // (plain stores: what this kernel was measured with)
   }
 }
 
@@ -952,28 +863,16 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nn_dense16(const float* __restr
   const int q = __builtin_amdgcn_readfirstlane(tid / QT), r = tid % QT;   // quad of list positions (= the wave), unit / row
   const int l31 = lane & 31, lh = lane >> 5;
   const int ncol = (H + TU - 1) / TU, nrow = (T + TM - 1) / TM;
-  float sw = 1.f;
-  {
-    const float m = __uint_as_float(*wmax) * vmax;
-    int ex = 0;
-    if (m > 0.f && m < 3.0e38f) (void)frexpf(m, &ex);
-    ex = ex < -60 ? -60 : ex;
-    sw = m < 3.0e38f ? ldexpf(1.f, 15 - ex) : 0.f;
-  }
-  const float inv = sw > 0.f ? 1.f / (sw * sx) : __uint_as_float(0x7FC00000u);
-  const int x = blockIdx.x & 7, jj = blockIdx.x >> 3;   // XCD-aware tile order: see k_gemm_nn_sparse
-  const int rt = (jj / ncol) * 8 + x;
+  const float sw = split_scale<SPLIT_NONFINITE_ZERO>(__uint_as_float(*wmax) * vmax, -60);   // (an Inf weight: scale 0, Z is NaN - visible)
+  const float inv = split_unscale(1.f, sw, sx);
+  const XcdTile wt = xcd_tile(blockIdx.x, ncol);   // (the column tiles of one (sample, row tile) meet in one L2)
+  const int rt = wt.group;
   if (rt >= nrow * B) return;
-  const int u0 = (jj % ncol) * TU, r0 = (rt % nrow) * TM, b = rt / nrow;
+  const int u0 = wt.item * TU, r0 = (rt % nrow) * TM, b = rt / nrow;
   const float* Xb = X + (size_t)b * F * ldx + r0 + r;
   const int ucl = (u0 + r < H) ? u0 + r : H - 1;
   f32x16 acc[4][2];
-#pragma unroll
-  for (int g = 0; g < 4; ++g)
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[g][mt][e] = 0.f;
+  zero_acc(acc);
   struct Regs {
     float ra[RPT * 4], rw[16], rm[16];
   };
@@ -999,53 +898,40 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nn_dense16(const float* __restr
       }
     }
   };
-  auto split4 = [](const float (&xs)[4], f16x4_& hi, f16x4_& lo) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      _Float16 h, l;
-      mgr_split_f16(xs[c], h, l);
-      hi[c] = h;
-      lo[c] = l;
-    }
-  };
   auto stash = [&](const Regs& R, int buf) {
     const float (&ra)[RPT * 4] = R.ra;
     const float (&rw)[16] = R.rw;
     const float (&rm)[16] = R.rm;
-    f16x4_ hi, lo;
+    f16x4 hi, lo;
 #pragma unroll
     for (int i = 0; i < RPT; ++i) {
       const float xs[4] = {ra[i * 4] * sx, ra[i * 4 + 1] * sx, ra[i * 4 + 2] * sx, ra[i * 4 + 3] * sx};
-      split4(xs, hi, lo);
-      *reinterpret_cast<f16x4_*>(&Ah[buf][q >> 1][r + QT * i][(q & 1) * 4]) = hi;
-      *reinterpret_cast<f16x4_*>(&Al[buf][q >> 1][r + QT * i][(q & 1) * 4]) = lo;
+      split_f16_vec<4>(xs, hi, lo);
+      *reinterpret_cast<f16x4*>(&Ah[buf][q >> 1][r + QT * i][(q & 1) * 4]) = hi;
+      *reinterpret_cast<f16x4*>(&Al[buf][q >> 1][r + QT * i][(q & 1) * 4]) = lo;
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const float ws[4] = {rw[g * 4] * rm[g * 4], rw[g * 4 + 1] * rm[g * 4 + 1], rw[g * 4 + 2] * rm[g * 4 + 2], rw[g * 4 + 3] * rm[g * 4 + 3]};
-      split4(ws, hi, lo);
-      *reinterpret_cast<f16x4_*>(&Bh[buf][g][q >> 1][r][(q & 1) * 4]) = hi;
-      *reinterpret_cast<f16x4_*>(&Bl[buf][g][q >> 1][r][(q & 1) * 4]) = lo;
+      split_f16_vec<4>(ws, hi, lo);
+      *reinterpret_cast<f16x4*>(&Bh[buf][g][q >> 1][r][(q & 1) * 4]) = hi;
+      *reinterpret_cast<f16x4*>(&Bl[buf][g][q >> 1][r][(q & 1) * 4]) = lo;
     }
   };
   auto mma = [&](int buf) {
     const int ra_ = wr * 64 + l31, ub = wc * 32 + l31;
-    f16x8_ ah[2], al[2];
+    f16x8 ah[2], al[2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
-      ah[mt] = *reinterpret_cast<const f16x8_*>(&Ah[buf][lh][ra_ + 32 * mt][0]);
-      al[mt] = *reinterpret_cast<const f16x8_*>(&Al[buf][lh][ra_ + 32 * mt][0]);
+      ah[mt] = *reinterpret_cast<const f16x8*>(&Ah[buf][lh][ra_ + 32 * mt][0]);
+      al[mt] = *reinterpret_cast<const f16x8*>(&Al[buf][lh][ra_ + 32 * mt][0]);
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const f16x8_ bh = *reinterpret_cast<const f16x8_*>(&Bh[buf][g][lh][ub][0]);
-      const f16x8_ bl = *reinterpret_cast<const f16x8_*>(&Bl[buf][g][lh][ub][0]);
+      const f16x8 bh = *reinterpret_cast<const f16x8*>(&Bh[buf][g][lh][ub][0]);
+      const f16x8 bl = *reinterpret_cast<const f16x8*>(&Bl[buf][g][lh][ub][0]);
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        acc[g][mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bh, acc[g][mt], 0, 0, 0);
-        acc[g][mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mt], bh, acc[g][mt], 0, 0, 0);
-        acc[g][mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bl, acc[g][mt], 0, 0, 0);
-      }
+      for (int mt = 0; mt < 2; ++mt) mfma3_split(ah[mt], al[mt], bh, bl, acc[g][mt]);
     }
   };
   // (two register sets, loads two stages ahead, no conditional load in the loop: k_gemm_nn_sparse16; a stage index beyond the
@@ -1066,19 +952,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nn_dense16(const float* __restr
     stash(R0, 0);
     __syncthreads();
   }
-  const int unit = u0 + wc * 32 + l31;
+  const int unit = acc_col(u0 + wc * 32, l31);
   if (unit < H) {
     const float4 bias = *reinterpret_cast<const float4*>(bp + unit * 4);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int row = r0 + wr * 64 + mt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-        if (row < T)
-          *reinterpret_cast<float4*>(Z + ((size_t)b * T + row) * N + unit * 4) =
-              make_float4(fmaf(acc[0][mt][reg], inv, bias.x), fmaf(acc[1][mt][reg], inv, bias.y), fmaf(acc[2][mt][reg], inv, bias.z),
-                          fmaf(acc[3][mt][reg], inv, bias.w));
-      }
+    store_z_tile<false>(acc, inv, bias, Z, b, T, N, r0 + wr * 64, unit, lh);   // (plain stores: what this kernel was measured with)
   }
 }
 
@@ -1145,10 +1022,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tn(const float* __restrict__ A,
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) {
-        int col = n0 + ACC_COL(wc, nt, lane);
+        int col = n0 + acc_col(wc * 64 + nt * 32, lane & 31);
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-          int f = f0 + ACC_ROW(wr, mt, reg, lane);
+          int f = f0 + acc_row(wr * 64 + mt * 32, reg, lane >> 5);
           float m = 1.f;
           if (mask4 && f < F && col < N) m = mask4[((size_t)(col & 3) * B + b) * F + f];
           tot[mt][nt][reg] += acc[mt][nt][reg] * m;
@@ -1160,10 +1037,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tn(const float* __restrict__ A,
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      int col = n0 + ACC_COL(wc, nt, lane);
+      int col = n0 + acc_col(wc * 64 + nt * 32, lane & 31);
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        int f = f0 + ACC_ROW(wr, mt, reg, lane);
+        int f = f0 + acc_row(wr * 64 + mt * 32, reg, lane >> 5);
         if (f < F && col < N) out[(size_t)f * N + col] = tot[mt][nt][reg];
       }
     }
@@ -1191,13 +1068,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tn_sparse(const float* __restri
   __shared__ float rowf[BM];
   static_assert(NBUF == 2 && BK == 16, "staging below assumes two LDS buffers of 16 k");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
-  // XCD-aware decode (consecutive workgroup ids go round-robin over the 8 XCDs): all workgroups of a sample - which share
-  // its X rows and dZ columns - get ids congruent mod 8, i.e. one L2
+  // XCD-aware decode (xcd_tile): all workgroups of a sample - which share its X rows and dZ columns - get ids congruent mod 8, i.e. one L2
   const int nft = (Fp + BM - 1) / BM, nut = (H + BN - 1) / BN, wps = 4 * nft * nut;
-  const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
-  const int b = (jj / wps) * 8 + xcd;
+  const XcdTile wt = xcd_tile(blockIdx.x, wps);
+  const int b = wt.group;
   if (b >= B) return;
-  const int w = jj % wps, g = w / (nft * nut), gb = g * B + b;
+  const int w = wt.item, g = w / (nft * nut), gb = g * B + b;
   const int q0 = ((w / nut) % nft) * BM, u0 = (w % nut) * BN;
   const int cnt = kcnt[gb];
   if (q0 >= cnt) return;   // (uniform) no kept feature in this row tile
@@ -1255,10 +1131,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tn_sparse(const float* __restri
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      const int u = u0 + ACC_COL(wc, nt, lane);
+      const int u = u0 + acc_col(wc * 64 + nt * 32, lane & 31);
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const int r = ACC_ROW(wr, mt, reg, lane);
+        const int r = acc_row(wr * 64 + mt * 32, reg, lane >> 5);
         if (q0 + r < cnt && u < H) out[(size_t)(q0 + r) * H + u] = acc[mt][nt][reg] * rowf[r];
       }
     }
@@ -1282,10 +1158,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tn_sparse16(const float* __rest
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
   const int l31 = lane & 31, lh = lane >> 5;
   const int nft = (Fp + BM - 1) / BM, nut = (H + BN - 1) / BN, wps = 4 * nft * nut;   // (decode: see k_gemm_tn_sparse)
-  const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
-  const int b = (jj / wps) * 8 + xcd;
+  const XcdTile wt = xcd_tile(blockIdx.x, wps);
+  const int b = wt.group;
   if (b >= B) return;
-  const int w = jj % wps, g = w / (nft * nut), gb = g * B + b;
+  const int w = wt.item, g = w / (nft * nut), gb = g * B + b;
   const int q0 = ((w / nut) % nft) * BM, u0 = (w % nut) * BN;
   const int cnt = kcnt[gb];
   if (q0 >= cnt) return;
@@ -1296,11 +1172,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tn_sparse16(const float* __rest
   const float* xrow = X + ((size_t)b * F + kidx[(size_t)gb * Fp + q]) * ldx + 16 * kb;
   const float* zrow = dZ + ((size_t)b * N + 4 * un + g) * ldz + 16 * kb;
   auto zscale = [&](int unit) -> float {   // the power of two that puts the row's largest |dZ| in [2^14, 2^15)
-    const float zm = __uint_as_float(zmax[(size_t)b * N + 4 * unit + g]);
-    int ex = 0;
-    if (zm > 0.f && zm < 3.0e38f) (void)frexpf(zm, &ex);
-    ex = ex < -100 ? -100 : ex;
-    return zm < 3.0e38f ? ldexpf(1.f, 15 - ex) : __uint_as_float(0x7FC00000u);   // (an Inf / NaN gradient stays visible)
+    return split_scale<SPLIT_NONFINITE_NAN>(__uint_as_float(zmax[(size_t)b * N + 4 * unit + g]), -100);   // (an Inf / NaN gradient stays visible)
   };
   const float sz = zscale(un);
   f32x16 acc[2][2];
@@ -1315,38 +1187,32 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tn_sparse16(const float* __rest
       R.b[i] = *reinterpret_cast<const float4*>(zrow + t0 + 4 * i);
     }
   };
-  auto split8 = [](const float4& v0, const float4& v1, float s, f16x8_& hi, f16x8_& lo) {
+  auto split8 = [](const float4& v0, const float4& v1, float s, f16x8& hi, f16x8& lo) {
     const float xs[8] = {v0.x * s, v0.y * s, v0.z * s, v0.w * s, v1.x * s, v1.y * s, v1.z * s, v1.w * s};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      _Float16 h, l;
-      mgr_split_f16(xs[e], h, l);
-      hi[e] = h;
-      lo[e] = l;
-    }
+    split_f16_vec<8>(xs, hi, lo);
   };
   auto stash = [&](const Regs& R, int buf) {
-    f16x8_ hi, lo;
+    f16x8 hi, lo;
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
       split8(R.a[2 * hf], R.a[2 * hf + 1], sx, hi, lo);
-      *reinterpret_cast<f16x8_*>(&Ah[buf][kb][hf][m][0]) = hi;
-      *reinterpret_cast<f16x8_*>(&Al[buf][kb][hf][m][0]) = lo;
+      *reinterpret_cast<f16x8*>(&Ah[buf][kb][hf][m][0]) = hi;
+      *reinterpret_cast<f16x8*>(&Al[buf][kb][hf][m][0]) = lo;
       split8(R.b[2 * hf], R.b[2 * hf + 1], sz, hi, lo);
-      *reinterpret_cast<f16x8_*>(&Bh[buf][kb][hf][m][0]) = hi;
-      *reinterpret_cast<f16x8_*>(&Bl[buf][kb][hf][m][0]) = lo;
+      *reinterpret_cast<f16x8*>(&Bh[buf][kb][hf][m][0]) = hi;
+      *reinterpret_cast<f16x8*>(&Bl[buf][kb][hf][m][0]) = lo;
     }
   };
   auto mma = [&](int buf) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      f16x8_ ah[2], al[2], bh[2], bl[2];
+      f16x8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        ah[i] = *reinterpret_cast<const f16x8_*>(&Ah[buf][ks][lh][wr * 64 + i * 32 + l31][0]);
-        al[i] = *reinterpret_cast<const f16x8_*>(&Al[buf][ks][lh][wr * 64 + i * 32 + l31][0]);
-        bh[i] = *reinterpret_cast<const f16x8_*>(&Bh[buf][ks][lh][wc * 64 + i * 32 + l31][0]);
-        bl[i] = *reinterpret_cast<const f16x8_*>(&Bl[buf][ks][lh][wc * 64 + i * 32 + l31][0]);
+        ah[i] = *reinterpret_cast<const f16x8*>(&Ah[buf][ks][lh][wr * 64 + i * 32 + l31][0]);
+        al[i] = *reinterpret_cast<const f16x8*>(&Al[buf][ks][lh][wr * 64 + i * 32 + l31][0]);
+        bh[i] = *reinterpret_cast<const f16x8*>(&Bh[buf][ks][lh][wc * 64 + i * 32 + l31][0]);
+        bl[i] = *reinterpret_cast<const f16x8*>(&Bl[buf][ks][lh][wc * 64 + i * 32 + l31][0]);
       }
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt)
@@ -1386,13 +1252,13 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tn_sparse16(const float* __rest
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      const int u = u0 + ACC_COL(wc, nt, lane);
+      const int u = u0 + acc_col(wc * 64 + nt * 32, lane & 31);
       // (the two reciprocals apart: zscale reaches 2^115 for a row of tiny gradients, and zscale * sx would overflow to Inf there -
       // cf = 0 flushed such a row's dW contribution to zero instead of rescaling it; both are powers of two, the products are exact)
       const float cz = 1.f / zscale(u < H ? u : H - 1), cx = 1.f / sx;
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const int r = ACC_ROW(wr, mt, reg, lane);
+        const int r = acc_row(wr * 64 + mt * 32, reg, lane >> 5);
         if (q0 + r < cnt && u < H) out[(size_t)(q0 + r) * H + u] = acc[mt][nt][reg] * cx * cz * kval[(size_t)gb * Fp + q0 + r];
       }
     }
@@ -1480,10 +1346,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(const float* __restrict__ dZ
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      int f = f0 + ACC_COL(wc, nt, lane);
+      int f = f0 + acc_col(wc * 64 + nt * 32, lane & 31);
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        int r = r0 + ACC_ROW(wr, mt, reg, lane);
+        int r = r0 + acc_row(wr * 64 + mt * 32, reg, lane >> 5);
         if (r < T && f < F) {
           float* o = dX + ((size_t)b * T + r) * lddx + f;
           *o = accumulate ? (*o + acc[mt][nt][reg]) : acc[mt][nt][reg];
@@ -1565,6 +1431,28 @@ static int colsum_wgs(size_t rows) {
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// The host's part of a split-f16 call, from the x_absmax argument (mgr.h).  x_absmax > 0: a bound on |X| the CALLER states - checked on
+// the device (k_absmax_gate raises the gate word), f32 kernel if violated; < 0: |x_absmax| is a bound the PRODUCER of XT guarantees: no
+// check, no gate; 0 or beyond 1e30: no bound, no split-f16 kernel (MGR_TUNE_GEMM_F32 = 1: never).
+struct SplitCall {
+  bool f16, trusted;   // the split-f16 kernel runs; its bound is not checked
+  float sx;            // |X| sx < 2^15 (0 without the f16 kernel)
+  unsigned* gate;      // the word of MGR_GATED, or null: nothing to check
+};
+static SplitCall split_call(const mgr_ctx* c, float x_absmax, bool shape_ok /* what else the kernel asks of the call */, unsigned* gate_word) {
+  const float xb = fabsf(x_absmax);
+  SplitCall k;
+  k.trusted = x_absmax < 0.f;
+  k.f16 = shape_ok && xb > 0.f && xb < 1.0e30f && c->tune[MGR_TUNE_GEMM_F32] == 0;
+  k.sx = k.f16 ? split_scale<SPLIT_NONFINITE_NONE>(xb, SPLIT_NO_FLOOR) : 0.f;   // (xb is an ordinary positive number here)
+  k.gate = (k.f16 && !k.trusted) ? gate_word : nullptr;
+  return k;
+}
+// what |X| the f16 range holds at the scale sx: beyond it the split would carry Inf.  n4: float4 elements of the operand, padding included
+static void launch_absmax_gate(hipStream_t s, const float* X, size_t n4, const SplitCall& k) {
+  hipLaunchKernelGGL(k_absmax_gate, dim3(mgr_grid256(n4, 4096)), dim3(256), 0, s, X, n4, 65000.f / k.sx, k.gate);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1639,17 +1527,14 @@ static int input_proj_dropout_impl(mgr_ctx* c, const float* X, int ldx, bool tra
   float *kval = L.kval, *Wg = L.Wg;
   unsigned* wmax = L.wmax;
   hipStream_t s = mgr_stream(c);
-  // x_absmax > 0: a bound the CALLER states - checked on the device (k_absmax_gate), f32 kernel if violated; < 0: |x_absmax| is a bound
-  // the PRODUCER of XT guarantees (mgr.h): no check
-  const bool trusted = x_absmax < 0.f;
-  const float xb = fabsf(x_absmax);
-  // split-f16 kernel (MGR_TUNE_GEMM_F32 = 1: never): transposed input with a bound on |X|, a drop rate that bounds the mask factor
-  const bool f16 = transposed && xb > 0.f && xb < 1.0e30f && drop_rate < 0.99f && c->tune[MGR_TUNE_GEMM_F32] == 0;
+  // split-f16 kernel: transposed input with a bound on |X| (split_call), a drop rate that bounds the mask factor
+  const SplitCall sc = split_call(c, x_absmax, transposed && drop_rate < 0.99f, wmax + 1);
+  const bool f16 = sc.f16;
+  unsigned* const gate = sc.gate;
   // dense K loop with the mask as a factor (k_gemm_nn_dense16): where there is no mask (inference); MGR_TUNE_PROJ_DENSE16_MASKED = 2:
   // always.  With a mask the per-gate K loops over the kept features are faster (audio depth 2: 1.99 against 2.28 ms)
   const bool dense = f16 && (!mask4 || c->tune[MGR_TUNE_PROJ_DENSE16_MASKED] == 2);
   MGR_REQUIRE(mask4 || transposed, "a projection without a dropout mask is only handled from the transposed copy");
-  unsigned* gate = (f16 && !trusted) ? wmax + 1 : nullptr;
   const bool lists = !dense || gate;   // the kept-feature lists: what every kernel but the dense one walks (no mask: all features)
   mgr_prof_begin(c, MGR_K_GEMM_NN);
   // narrow row-major inputs (the depth-1 projections): k_proj_narrow makes its lists and its weight image itself - one launch, nothing
@@ -1691,13 +1576,10 @@ static int input_proj_dropout_impl(mgr_ctx* c, const float* X, int ldx, bool tra
   const int tu = wide ? 128 : 64;
   const int ntiles = ((H + tu - 1) / tu) * ((((T + SP_TM - 1) / SP_TM) * B + 7) / 8) * 8;   // (row tiles padded to the 8 XCDs)
   if (f16) {
-    int ex;
-    (void)frexpf(xb, &ex);                       // xb = m 2^ex, m in [0.5, 1): |X| sx < 2^15
-    const float sx = ldexpf(1.f, 15 - ex);
-    if (gate) {   // what |X| the f16 range holds at this scale: beyond it the split would carry Inf (ldx is the padded row length)
+    const float sx = sc.sx;
+    if (gate) {   // (ldx is the padded row length)
       MGR_HIP(hipMemsetAsync(gate, 0, sizeof(unsigned), s));
-      const size_t n4 = (size_t)B * F * ldx / 4;
-      hipLaunchKernelGGL(k_absmax_gate, dim3(mgr_grid256(n4, 4096)), dim3(256), 0, s, X, n4, 65000.f / sx, gate);
+      launch_absmax_gate(s, X, (size_t)B * F * ldx / 4, sc);
     }
     if (dense)
       hipLaunchKernelGGL(k_gemm_nn_dense16, dim3(ntiles), dim3(256), 0, s, X, ldx, mask4, Wg, bp, Z, B, T, F, H, wmax,
@@ -1876,25 +1758,18 @@ static int param_grads_dropout_impl(mgr_ctx* c, const float* X, int ldx, const f
     hipLaunchKernelGGL(k_mask_compact, dim3(4 * B), dim3(64), 0, s, mask4, F, Fp, kidx, kval, kcnt, kpos, (unsigned*)nullptr);
     const int grid = 8 * ((B + 7) / 8) * 4 * ((Fp + BM - 1) / BM) * ((H + BN - 1) / BN);
     if (XT) {
-      // split-f16 kernel (MGR_TUNE_GEMM_F32 = 1: never): a bound on |X| (stated: checked on the device, f32 kernel if violated; negative:
-      // guaranteed by the producer of XT), whole stages of 32 time steps in the padded rows
-      const bool trusted = x_absmax < 0.f;
-      const float xb = fabsf(x_absmax);
-      const bool f16 = xb > 0.f && xb < 1.0e30f && c->tune[MGR_TUNE_GEMM_F32] == 0 && ldt >= (T + 31) / 32 * 32;
+      // split-f16 kernel: a bound on |X| (split_call), whole stages of 32 time steps in the padded rows
       float* dZT = L.dZT;
       unsigned* zmax = L.zmax;   // [B][4H] largest |dZ| of a (sample, gate column), + the gate word
-      unsigned* gate = (f16 && !trusted) ? zmax + (size_t)B * 4 * H : nullptr;
+      const SplitCall sc = split_call(c, x_absmax, ldt >= (T + 31) / 32 * 32, zmax + (size_t)B * 4 * H);
+      const bool f16 = sc.f16;
+      unsigned* const gate = sc.gate;
       if (f16) MGR_HIP(hipMemsetAsync(zmax, 0, ((size_t)B * 4 * H + 1) * sizeof(unsigned), s));
       hipLaunchKernelGGL(k_transpose_bt, dim3((ldt + 63) / 64, (4 * H + 63) / 64, B), dim3(256), 0, s, dZ, 4 * H, dZT, ldt, T, 4 * H, 0LL, ldt,
                          f16 ? zmax : (unsigned*)nullptr);
       if (f16) {
-        int ex;
-        (void)frexpf(xb, &ex);
-        const float sx = ldexpf(1.f, 15 - ex);
-        if (gate) {
-          const size_t n4 = (size_t)B * F * ldt / 4;
-          hipLaunchKernelGGL(k_absmax_gate, dim3(mgr_grid256(n4, 4096)), dim3(256), 0, s, XT, n4, 65000.f / sx, gate);
-        }
+        const float sx = sc.sx;
+        if (gate) launch_absmax_gate(s, XT, (size_t)B * F * ldt / 4, sc);
         hipLaunchKernelGGL(k_gemm_tn_sparse16, dim3(grid), dim3(256), 0, s, XT, ldt, kidx, kval, kcnt, dZT, ldt, zmax, P, B, T, Fp, F, H, sx, gate);
         if (gate)
           hipLaunchKernelGGL((k_gemm_tn_sparse<true>), dim3(grid), dim3(256), 0, s, XT, ldt, kidx, kval, kcnt, dZT, ldt, P, B, T, Fp, F, H, gate);

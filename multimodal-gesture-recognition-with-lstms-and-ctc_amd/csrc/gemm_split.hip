@@ -7,16 +7,14 @@
 //
 // SPLIT ROW FORMAT ("XS"): a transposed activation copy XT[b][f][ldt] of f32 (mgr.h, mgr_scan_job.YT) keeps its shape and strides;
 // the 4 ldt bytes of row (b, f) hold ldt f16 values hi(t) followed by ldt f16 values lo(t) with  x 2^13 = hi + lo,  hi = rn_f16(x 2^13),
-// lo = rn_f16(x 2^13 - hi)  (|x| < 7.99; exact scaling, 22+ significant bits - gemm.hip, mgr_split_f16).  The scans write it
+// lo = rn_f16(x 2^13 - hi)  (|x| < 7.99; exact scaling, 22+ significant bits - split_f16.h, split_f16).  The scans write it
 // themselves (lstm_cluster.hip, mgr_scan_job.yt_split), mgr_transpose_bt_split makes it from a row-major tensor.
 // Arithmetic: as everywhere on the split path, A B ~ (Ahi Bhi + Alo Bhi + Ahi Blo) / (sA sB) in ONE f32 accumulator.
 #include "common.h"
+#include "split_f16.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef short tr4 __attribute__((__vector_size__(4 * sizeof(short))));
 typedef short tr8 __attribute__((__vector_size__(8 * sizeof(short))));
 typedef __attribute__((address_space(3))) char lds_char;
@@ -107,16 +105,7 @@ __global__ __launch_bounds__(256) void k_wmax(const float* __restrict__ Wp, size
   if (threadIdx.x == 0) atomicMax(wmax, __float_as_uint(fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]))));
 }
 __device__ __forceinline__ float ps_wscale(const unsigned* wmax) {   // the power of two that puts the largest |W| in [2^14, 2^15)
-  const float m = __uint_as_float(*wmax);
-  int ex = 0;
-  if (m > 0.f && m < 3.0e38f) (void)frexpf(m, &ex);
-  ex = ex < -60 ? -60 : ex;
-  return m < 3.0e38f ? ldexpf(1.f, 15 - ex) : 0.f;    // (an Inf weight: scale 0, the output is NaN - visible)
-}
-__device__ __forceinline__ void ps_split(float x, _Float16& hi, _Float16& lo) {   // (gemm.hip, mgr_split_f16)
-  asm volatile("" : "+v"(x));
-  hi = (_Float16)x;
-  lo = (_Float16)(x - (float)hi);
+  return split_scale<SPLIT_NONFINITE_ZERO>(__uint_as_float(*wmax), -60);    // (an Inf weight: scale 0, the output is NaN - visible)
 }
 // weight planes WS[g][f][hi Hp | lo Hp] f16 of W sw (gate-major, Hp = H rounded up to 64, zero beyond H, row F all zero):
 // Wp[f][4u + g] is the packed kernel
@@ -132,7 +121,7 @@ __global__ __launch_bounds__(256) void k_wplanes(const float* __restrict__ Wp, _
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       _Float16 hi, lo;
-      ps_split(g4[g] * sw, hi, lo);
+      split_f16(g4[g] * sw, hi, lo);
       _Float16* row = WS + ((size_t)g * (F + 1) + f) * 2 * Hp;
       row[u] = hi;
       row[Hp + u] = lo;
@@ -189,8 +178,8 @@ __device__ __forceinline__ void ts_tile(const float* __restrict__ Xb, int ldx, f
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       _Float16 hi0, lo0, hi1, lo1;
-      ps_split(v[i][0] * sc, hi0, lo0);
-      ps_split(v[i][1] * sc, hi1, lo1);
+      split_f16(v[i][0] * sc, hi0, lo0);
+      split_f16(v[i][1] * sc, hi1, lo1);
       const int p = w + 4 * i;
       img[0][lane][p] = (unsigned)__builtin_bit_cast(unsigned short, hi0) | ((unsigned)__builtin_bit_cast(unsigned short, hi1) << 16);
       img[1][lane][p] = (unsigned)__builtin_bit_cast(unsigned short, lo0) | ((unsigned)__builtin_bit_cast(unsigned short, lo1) << 16);
@@ -263,10 +252,10 @@ __global__ __launch_bounds__(128 * WC, WC == 2 ? 2 : 1) void k_proj_split(const 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wave / WC, wc = wave % WC;
   const int N = 4 * H;
   const int ncol = (H + C::TU - 1) / C::TU, nrow = (T + PS_TM - 1) / PS_TM;
-  const int x = blockIdx.x & 7, jj = blockIdx.x >> 3;   // XCD-aware tile order (gemm.hip, k_gemm_nn_sparse): the column tiles of one
-  const int rt = (jj / ncol) * 8 + x;                   // (sample, row tile) meet in one L2
+  const XcdTile wt = xcd_tile(blockIdx.x, ncol);   // (the column tiles of one (sample, row tile) meet in one L2)
+  const int rt = wt.group;
   if (rt >= nrow * B) return;
-  const int u0 = (jj % ncol) * C::TU, r0 = (rt % nrow) * PS_TM, b = rt / nrow;
+  const int u0 = wt.item * C::TU, r0 = (rt % nrow) * PS_TM, b = rt / nrow;
   const char* XSb = XS + (size_t)b * F * ldt * 4;
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_char*)ps_smem;
 
@@ -356,12 +345,7 @@ __global__ __launch_bounds__(128 * WC, WC == 2 ? 2 : 1) void k_proj_split(const 
   }
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int g = 0; g < 4; ++g)
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[g][mb][e] = 0.f;
+  zero_acc(acc);
 
   if (NT > 0) {
     constexpr int PD = C::NBUF - 1;   // stages in flight
@@ -434,9 +418,7 @@ __global__ __launch_bounds__(128 * WC, WC == 2 ? 2 : 1) void k_proj_split(const 
 #pragma unroll
           for (int mb = 0; mb < 2; ++mb) {
             const f16x8 ah = frag(fa[mb][0][0], fa[mb][0][1]), al = frag(fa[mb][1][0], fa[mb][1][1]);
-            acc[g][mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[g][mb], 0, 0, 0);
-            acc[g][mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[g][mb], 0, 0, 0);
-            acc[g][mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[g][mb], 0, 0, 0);
+            mfma3_split(ah, al, bh, bl, acc[g][mb]);
           }
         }
 #undef PS_KSTEP
@@ -446,24 +428,12 @@ __global__ __launch_bounds__(128 * WC, WC == 2 ? 2 : 1) void k_proj_split(const 
   }
   const float sw = ps_wscale(wmax);
   const float cf = __uint_as_float(*cword);
-  const float inv = sw > 0.f ? cf / (sw * XS_SCALE) : __uint_as_float(0x7FC00000u);
+  const float inv = split_unscale(cf, sw, XS_SCALE);
   const int l31 = lane & 31, lh = lane >> 5;
-  const int unit = u0 + wc * 32 + l31;
+  const int unit = acc_col(u0 + wc * 32, l31);
   if (unit < H) {
     const float4 bias = *reinterpret_cast<const float4*>(bp + unit * 4);
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int row = r0 + wr * 64 + mb * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-        if (row < T) {
-          // (non-temporal: Z is read once, by a scan, milliseconds later - it need not displace what concurrent products keep in L2)
-          typedef float nt_f4 __attribute__((ext_vector_type(4)));
-          const nt_f4 v = {fmaf(acc[0][mb][reg], inv, bias.x), fmaf(acc[1][mb][reg], inv, bias.y), fmaf(acc[2][mb][reg], inv, bias.z),
-                           fmaf(acc[3][mb][reg], inv, bias.w)};
-          __builtin_nontemporal_store(v, reinterpret_cast<nt_f4*>(Z + ((size_t)b * T + row) * N + unit * 4));
-        }
-      }
+    store_z_tile<true>(acc, inv, bias, Z, b, T, N, r0 + wr * 64, unit, lh);   // (non-temporal)
   }
 }
 
@@ -500,11 +470,7 @@ __global__ __launch_bounds__(256) void k_rowmax_bt(const float* __restrict__ dZ,
   }
 }
 __device__ __forceinline__ float dw_zscale(unsigned zm_bits) {   // the power of two that puts the row's largest |dZ| in [2^14, 2^15)
-  const float zm = __uint_as_float(zm_bits);
-  int ex = 0;
-  if (zm > 0.f && zm < 3.0e38f) (void)frexpf(zm, &ex);
-  ex = ex < -100 ? -100 : ex;
-  return zm < 3.0e38f ? ldexpf(1.f, 15 - ex) : __uint_as_float(0x7FC00000u);   // (an Inf / NaN gradient stays visible)
+  return split_scale<SPLIT_NONFINITE_NAN>(__uint_as_float(zm_bits), -100);   // (an Inf / NaN gradient stays visible)
 }
 // dZS[b][col] = split row of dZ[b][0..T)[col] * sz(b, col), zero for t >= T
 __global__ __launch_bounds__(256) void k_transpose_split_scaled(const float* __restrict__ dZ, int N, float* __restrict__ dZS, int ldt, int T,
@@ -530,12 +496,12 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_split(const char* __restrict_
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wave >> 1, wc = wave & 1;
   const int N = 4 * H;
-  // XCD-aware decode (gemm.hip, k_gemm_tn_sparse): all workgroups of a sample - which share its X rows and dZ rows - in one L2
+  // XCD-aware decode (xcd_tile): all workgroups of a sample - which share its X rows and dZ rows - in one L2
   const int nft = (Fp32 + DW_BM - 1) / DW_BM, nut = (H + DW_BN - 1) / DW_BN, wps = 4 * nft * nut;
-  const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
-  const int b = (jj / wps) * 8 + xcd;
+  const XcdTile wt = xcd_tile(blockIdx.x, wps);
+  const int b = wt.group;
   if (b >= B) return;
-  const int w_ = jj % wps, g = w_ / (nft * nut), gb = g * B + b;
+  const int w_ = wt.item, g = w_ / (nft * nut), gb = g * B + b;
   const int q0 = ((w_ / nut) % nft) * DW_BM, u0 = (w_ % nut) * DW_BN;
   const int cnt = kcnt[gb];
   if (q0 >= cnt) return;   // (uniform) no kept feature in this row tile
@@ -584,12 +550,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_split(const char* __restrict_
     for (int ks = 0; ks < 2; ++ks) oB[nb][ks] = (unsigned)(16384 + nn * 64 + 16 * ((2 * ks + kh) ^ ((nn >> 2) & 3)));
   }
   f32x16 acc[MB][2];
-#pragma unroll
-  for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[mb][nb][e] = 0.f;
+  zero_acc(acc);
   constexpr int PD = NBUF - 1;
 #pragma unroll
   for (int s0 = 0; s0 < PD; ++s0) issue(s0);
@@ -628,9 +589,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_split(const char* __restrict_
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
           const f16x8 bh = __builtin_bit_cast(f16x8, fb[nb][0]), bl = __builtin_bit_cast(f16x8, fb[nb][1]);
-          acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[mb][nb], 0, 0, 0);
-          acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[mb][nb], 0, 0, 0);
-          acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[mb][nb], 0, 0, 0);
+          mfma3_split(ah, al, bh, bl, acc[mb][nb]);
         }
       }
     }
@@ -640,14 +599,14 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_split(const char* __restrict_
   float* out = P + (size_t)gb * Fp32 * H;
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb) {
-    const int u = u0 + 64 * wc + 32 * nb + l31;
+    const int u = acc_col(u0 + 64 * wc + 32 * nb, l31);
     // (the reciprocals apart from each other: sz reaches 2^115 for a row of tiny gradients; all powers of two, the products are exact)
     const float cz = u < H ? 1.f / dw_zscale(zmax[(size_t)b * N + 4 * u + g]) : 0.f;
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const int r = 32 * MB * wr + 32 * mb + (reg & 3) + 8 * (reg >> 2) + 4 * kh;
+        const int r = acc_row(32 * MB * wr + 32 * mb, reg, kh);
         if (q0 + r < cnt && u < H) out[(size_t)(q0 + r) * H + u] = acc[mb][nb][reg] * cf * cz;
       }
   }

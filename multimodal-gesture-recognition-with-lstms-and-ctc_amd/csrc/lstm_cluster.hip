@@ -37,6 +37,7 @@
 
 #include "lstm_cluster.h"
 #include "lstm_common.h"
+#include "split_f16.h"
 
 namespace {
 
@@ -303,7 +304,6 @@ __device__ __forceinline__ void cluster_run(const ClusterJob& jb, int bg, int ug
 // (4.1 / 5.3); a raised wave priority for the cell phase, or for the wider layer's waves (no change).
 typedef __attribute__((address_space(3))) float lds_float;
 constexpr int KS_STG = 8;                      // steps per staged chunk of the transposed output
-typedef _Float16 yt_f16x8 __attribute__((ext_vector_type(8)));
 // A finished chunk of 8 time steps of one (sample, unit) row of the transposed output leaves the staging tile: as 8 floats, or - split
 // row format, mgr.h - as 8 f16 hi values into the row's first half and 8 f16 lo values into its second half (16 + 16 bytes either way).
 // row: the row's first float; t8: first time step of the chunk; ldt: row length in floats.
@@ -315,17 +315,12 @@ __device__ __forceinline__ void ks_flush_chunk(const float* stg, int lane, float
     *reinterpret_cast<f32x4*>(row + t8) = (f32x4){v[0], v[1], v[2], v[3]};
     *reinterpret_cast<f32x4*>(row + t8 + 4) = (f32x4){v[4], v[5], v[6], v[7]};
   } else {
-    yt_f16x8 hi, lo;
+    f16x8 hi, lo;
 #pragma unroll
-    for (int i = 0; i < KS_STG; ++i) {
-      float xs = v[i] * 8192.f;
-      asm volatile("" : "+v"(xs));   // (hi and the residual from ONE f32 value: gemm.hip, mgr_split_f16)
-      hi[i] = (_Float16)xs;
-      lo[i] = (_Float16)(xs - (float)hi[i]);
-    }
+    for (int i = 0; i < KS_STG; ++i) split_f16_lane(v[i] * 8192.f, hi, lo, i);
     _Float16* r16 = reinterpret_cast<_Float16*>(row);
-    *reinterpret_cast<yt_f16x8*>(r16 + t8) = hi;
-    *reinterpret_cast<yt_f16x8*>(r16 + ldt + t8) = lo;
+    *reinterpret_cast<f16x8*>(r16 + t8) = hi;
+    *reinterpret_cast<f16x8*>(r16 + ldt + t8) = lo;
   }
 }
 // zeros behind T up to the row length (both halves of a split row: 2 ldt f16 = ldt floats of zero bits)
@@ -614,7 +609,6 @@ __device__ __forceinline__ void cluster_run_ks(const ClusterJob& jb, const Clust
 //     |h 2^15 - hi - lo| <= 2^-20 |h 2^15|, an odd unit 2^-22.
 //   * Y, the saved gates and c are the f32 values; the recurrence sees h rounded to 22+ bits (as every f32 consumer of Y would
 //     see it rounded to 24).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // the f16 nearest to x among those whose last mantissa bit is `lsb`, given bits = rn_f16(x): bits itself, or its neighbour on the
 // side x lies on (the f16 bit patterns of one sign are ordered like their magnitudes, exponent boundaries included; x is finite
 // and far below the f16 maximum here)
@@ -722,9 +716,8 @@ __device__ __forceinline__ void cluster_run_k16(const ClusterJob& jb, const Clus
   if (lane == 0) wmax[wave] = umax;
   __syncthreads();
   umax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-  int ex = 0;
-  if (umax > 0.f && umax < 3.0e38f) (void)frexpf(umax, &ex);   // umax = m 2^ex, m in [0.5, 1)   (Inf / NaN weights: the products are
-  ex = ex < -60 ? -60 : ex;                                    //  NaN, the non-finite guard below reports the launch)
+  // umax = m 2^ex, m in [0.5, 1); no non-finite policy (Inf / NaN weights: the products are NaN, the non-finite guard below reports the launch)
+  const int ex = split_exponent(umax, -60);
   const float sU = ldexpf(1.f, 15 - ex);        // largest |U| sU in [2^14, 2^15)
   const float inv = ldexpf(1.f, ex - 30);       // 1 / (sU 2^15)
   f16x8 ah[4][NBW], al[4][NBW];
@@ -734,11 +727,7 @@ __device__ __forceinline__ void cluster_run_k16(const ClusterJob& jb, const Clus
     for (int i = 0; i < NBW; ++i)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        float x = uval(tt, i, e) * sU;
-        asm volatile("" : "+v"(x));   // (hi and the residual from ONE f32 value: gemm.hip, mgr_split_f16)
-        const _Float16 hi = (_Float16)x;
-        ah[tt][i][e] = hi;
-        al[tt][i][e] = (_Float16)(x - (float)hi);
+        split_f16_lane(uval(tt, i, e) * sU, ah[tt][i], al[tt][i], e);
       }
 
   float* ytrow = nullptr;
@@ -899,7 +888,7 @@ __device__ __forceinline__ void cluster_run_k16(const ClusterJob& jb, const Clus
       // lo word's flag on the ODD unit's lo, bit 16 - every unit <= 2^-21 - but the two-mask check it needs in the gather cost the
       // audio step 0.3 us of 1.6: profiles/r05_scan_probes.txt.)
       float hs = h * 32768.f;
-      asm volatile("" : "+v"(hs));   // (as above)
+      asm volatile("" : "+v"(hs));   // (the value pin of split_f16.h)
       unsigned hib = (unsigned)__builtin_bit_cast(unsigned short, (_Float16)hs);
       hib = k16_with_lsb(hib, par, hs, ~lane & 1u);
       const float hif = (float)__builtin_bit_cast(_Float16, (unsigned short)hib);

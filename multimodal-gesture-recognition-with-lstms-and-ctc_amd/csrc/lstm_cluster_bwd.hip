@@ -24,6 +24,7 @@
 // read through an opaque asm.  H = 100 (config F's fusion layer): 3.2 -> see profiles/r03_*; H = 300 / 500 (split roles) likewise.
 #include "lstm_cluster.h"
 #include "lstm_common.h"
+#include "split_f16.h"
 
 namespace {
 
@@ -37,7 +38,6 @@ constexpr int BW16_IMG = 4 * 2 * 64 * 2;               // cluster_bwd_run16: flo
 constexpr int BW_LDS_FLOATS_A = 4 * 256 + 5 * 256 + BW_WAVES * BW_RING_FLOATS + 16;   // (+16: the four dz factors of the split-f16 form)
 constexpr int BW_LDS_FLOATS_B = 2 * BW16_IMG + 16 + BW_WAVES * BW16_RING_FLOATS + 1024;
 constexpr int BW_LDS_FLOATS = BW_LDS_FLOATS_A > BW_LDS_FLOATS_B ? BW_LDS_FLOATS_A : BW_LDS_FLOATS_B;   // (what a caller may assume at most)
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 // LDS-DMA: one wave-instruction copies 64 x 16 B (64 x 4 B) from global memory [gbase + voff] (gbase wave-uniform, voff per
 // lane) to LDS [lds_addr + 16 (4) * lane]; M0 carries the LDS address and is restored (hipcc does not know it was touched)
@@ -142,9 +142,7 @@ __device__ __forceinline__ void cluster_bwd_run(const ClusterBwdJob& jb, int bg,
     if (tid < 4) scl[tid] = 0.f;
     __syncthreads();
     umax = fmaxf(fmaxf(scl[8], scl[9]), fmaxf(scl[10], scl[11]));
-    int ex = 0;
-    if (umax > 0.f && umax < 3.0e38f) (void)frexpf(umax, &ex);
-    ex = ex < -60 ? -60 : ex;
+    const int ex = split_exponent(umax, -60);   // (no non-finite policy: NaN products stay visible in dZ)
     const float sU = ldexpf(1.f, 15 - ex);   // largest |U| sU in [2^14, 2^15)
     sUinv = ldexpf(1.f, ex - 15);
 #pragma unroll
@@ -153,11 +151,7 @@ __device__ __forceinline__ void cluster_bwd_run(const ClusterBwdJob& jb, int bg,
       for (int wsrc = 0; wsrc < 4; ++wsrc)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float x = uval(i, wsrc, e) * sU;
-          asm volatile("" : "+v"(x));   // (hi and the residual from ONE f32 value: gemm.hip, mgr_split_f16)
-          const _Float16 hi = (_Float16)x;
-          ah[i][wsrc][e] = hi;
-          al[i][wsrc][e] = (_Float16)(x - (float)hi);
+          split_f16_lane(uval(i, wsrc, e) * sU, ah[i][wsrc], al[i][wsrc], e);
         }
   } else {
 #pragma unroll
@@ -344,21 +338,14 @@ __device__ __forceinline__ void cluster_bwd_run(const ClusterBwdJob& jb, int bg,
         } else {
 #pragma unroll
           for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-          int e2 = 0;
-          if (m > 0.f && m < 3.0e38f) (void)frexpf(m, &e2);
-          e2 = e2 < -100 ? -100 : e2;
+          const int e2 = split_exponent(m, -100);
           sz = ldexpf(1.f, 15 - e2);   // (an Inf / NaN gradient: NaN products - it stays visible in dZ)
           if (lane == 0) scl[wave] = ldexpf(1.f, e2 - 15) * sUinv;
         }
-        float vs[4] = {dz.x * sz, dz.y * sz, dz.z * sz, dz.w * sz};
+        const float vs[4] = {dz.x * sz, dz.y * sz, dz.z * sz, dz.w * sz};
         f16x4 hi, lo;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          asm volatile("" : "+v"(vs[e]));
-          const _Float16 h = (_Float16)vs[e];
-          hi[e] = h;
-          lo[e] = (_Float16)(vs[e] - (float)h);
-        }
+        for (int e = 0; e < 4; ++e) split_f16_lane(vs[e], hi, lo, e);
         *reinterpret_cast<f16x4*>(dzi + ((wave * 2) * 64 + lane) * 2) = hi;
         *reinterpret_cast<f16x4*>(dzi + ((wave * 2 + 1) * 64 + lane) * 2) = lo;
       } else {
@@ -521,9 +508,7 @@ __device__ __forceinline__ void cluster_bwd_run16(const ClusterBwdJob& jb, int b
     if (lane == 0) scl[8 + wave] = umax;
     __syncthreads();
     umax = fmaxf(fmaxf(scl[8], scl[9]), fmaxf(scl[10], scl[11]));
-    int ex = 0;
-    if (umax > 0.f && umax < 3.0e38f) (void)frexpf(umax, &ex);
-    ex = ex < -60 ? -60 : ex;
+    const int ex = split_exponent(umax, -60);   // (no non-finite policy: NaN products stay visible in dZ)
     const float sU = ldexpf(1.f, 15 - ex);   // largest |U| sU in [2^14, 2^15)
     sUinv = ldexpf(1.f, ex - 15);
 #pragma unroll
@@ -532,11 +517,7 @@ __device__ __forceinline__ void cluster_bwd_run16(const ClusterBwdJob& jb, int b
       for (int wsrc = 0; wsrc < 4; ++wsrc)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float x = uval(i, wsrc, e) * sU;
-          asm volatile("" : "+v"(x));   // (hi and the residual from ONE f32 value: gemm.hip, mgr_split_f16)
-          const _Float16 hi = (_Float16)x;
-          ah[i][wsrc][e] = hi;
-          al[i][wsrc][e] = (_Float16)(x - (float)hi);
+          split_f16_lane(uval(i, wsrc, e) * sU, ah[i][wsrc], al[i][wsrc], e);
         }
   }
   const unsigned sUinv_bits = (unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(sUinv));
@@ -745,15 +726,10 @@ __device__ __forceinline__ void cluster_bwd_run16(const ClusterBwdJob& jb, int b
       if (!(mb > 0 && mb < 0x7f61b1e6)) e2 = 0;                 // (0x7f61b1e6 = 3.0e38f; zero, Inf, NaN)
       const float sz = __int_as_float((127 + 15 - e2) << 23);
       if (lane == 0) scl[p * 4 + wave] = __int_as_float((127 + e2 - 15) << 23) * __uint_as_float(sUinv_bits);
-      float vs[4] = {dz.x * sz, dz.y * sz, dz.z * sz, dz.w * sz};
+      const float vs[4] = {dz.x * sz, dz.y * sz, dz.z * sz, dz.w * sz};
       f16x4 hi, lo;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        asm volatile("" : "+v"(vs[e]));
-        const _Float16 h = (_Float16)vs[e];
-        hi[e] = h;
-        lo[e] = (_Float16)(vs[e] - (float)h);
-      }
+      for (int e = 0; e < 4; ++e) split_f16_lane(vs[e], hi, lo, e);
       float* img = dzi + p * BW16_IMG;
       *reinterpret_cast<f16x4*>(img + ((wave * 2) * 64 + lane) * 2) = hi;
       *reinterpret_cast<f16x4*>(img + ((wave * 2 + 1) * 64 + lane) * 2) = lo;

@@ -2,8 +2,7 @@
 // multimodal_fusion/multimodal.py:159-168: activation='tanh', recurrent_activation='hard_sigmoid').
 #pragma once
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "split_f16.h"   // (f32x4)
 
 __device__ __forceinline__ float mgr_hsig(float z) { return fminf(fmaxf(0.2f * z + 0.5f, 0.f), 1.f); }
 // tanh via one v_exp_f32 + one v_rcp_f32 (1 ulp; __frcp_rn would be the ten-instruction IEEE division sequence, and vector

@@ -27,10 +27,10 @@
 // per step (the dz image is double-buffered on the step parity).
 #include "lstm_cluster.h"
 #include "lstm_common.h"
+#include "split_f16.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) float lds_float;
 constexpr int CB_WAVES = 8;
 
@@ -124,20 +124,14 @@ __global__ __launch_bounds__(CB_WAVES * 64, 1) void k_scan_bwd_cu16(CuBwdJobs J,
     umax = 0.f;
 #pragma unroll
     for (int w = 0; w < CB_WAVES; ++w) umax = fmaxf(umax, scl[16 + w]);
-    int ex = 0;
-    if (umax > 0.f && umax < 3.0e38f) (void)frexpf(umax, &ex);
-    ex = ex < -60 ? -60 : ex;
+    const int ex = split_exponent(umax, -60);   // (no non-finite policy: NaN products stay visible in dZ)
     const float sU = ldexpf(1.f, 15 - ex);   // largest |U| sU in [2^14, 2^15)
     sUinv = ldexpf(1.f, ex - 15);
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        float x = uval(kb, e) * sU;
-        asm volatile("" : "+v"(x));   // (hi and the residual from ONE f32 value)
-        const _Float16 hi = (_Float16)x;
-        ah[kb][e] = hi;
-        al[kb][e] = (_Float16)(x - (float)hi);
+        split_f16_lane(uval(kb, e) * sU, ah[kb], al[kb], e);
       }
   }
   const unsigned sUinv_bits = (unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(sUinv));
@@ -239,15 +233,10 @@ __global__ __launch_bounds__(CB_WAVES * 64, 1) void k_scan_bwd_cu16(CuBwdJobs J,
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk) {
           const float4 d0 = dz[2 * blk], d1 = dz[2 * blk + 1];
-          float vs[8] = {d0.x * sz, d0.y * sz, d0.z * sz, d0.w * sz, d1.x * sz, d1.y * sz, d1.z * sz, d1.w * sz};
+          const float vs[8] = {d0.x * sz, d0.y * sz, d0.z * sz, d0.w * sz, d1.x * sz, d1.y * sz, d1.z * sz, d1.w * sz};
           f16x8 hi, lo;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            asm volatile("" : "+v"(vs[e]));
-            const _Float16 h = (_Float16)vs[e];
-            hi[e] = h;
-            lo[e] = (_Float16)(vs[e] - (float)h);
-          }
+          for (int e = 0; e < 8; ++e) split_f16_lane(vs[e], hi, lo, e);
           *reinterpret_cast<f16x8*>(im + (((2 * wave + blk) * 2 + 0) * 64 + lane) * 4) = hi;
           *reinterpret_cast<f16x8*>(im + (((2 * wave + blk) * 2 + 1) * 64 + lane) * 4) = lo;
         }

@@ -162,6 +162,48 @@ def test_weight_gradient_from_split_rows(device, B, T, F, H, p, reverse):
         assert np.array_equal(gU.download(), gU2.download()) and np.array_equal(gb.download(), gb2.download())
 
 
+def test_weight_gradient_from_split_rows_four_wave_form(device):
+    """k_dw_split<4> (tune key 12 = 1: the form the training step takes beside resident scans; the cases above run the 8-wave form):
+    dW, and dU from the split rows of h_prev, against numpy fp64 under the bound of test_weight_gradient_from_split_rows.  B = 2 leaves
+    the 8-way sample padding of the grid unfilled, T = 130 is four stages of 32 time steps and a 2-step tail, F = 129 one 128-row tile and a
+    row, H = 65 one unit beyond a 64-unit block; p = 0.6 gives the mask factor 2.5, which is no power of two."""
+    dev = device
+    B, T, F, H, p, reverse = 2, 130, 129, 65, 0.6, 0
+    rng = np.random.default_rng(B * 977 + T + F + H)
+    N = 4 * H
+    X = rng.uniform(-2, 2, (B, T, F)).astype(f32)
+    Hs = rng.standard_normal((B, T, H)).astype(f32)
+    M = ((rng.random((4, B, F)) >= p) * f32(1.0 / (1.0 - p))).astype(f32)
+    dZ = ((rng.standard_normal((B, T, N)) * 0.3).astype(f32) * (10.0 ** rng.uniform(-12, 12, size=(B, 1, N))).astype(f32))
+    ldt = (T + 127) // 128 * 128
+    dX, dH, dM, ddZ = dev.array(X), dev.array(Hs), dev.array(M), dev.array(dZ)
+    XS, HsT = dev.zeros((B, F, ldt)), dev.zeros((B, H, ldt))
+    dev.call("mgr_transpose_bt_split", dX, F, XS, ldt, B, T, F)
+    dev.call("mgr_transpose_bt_split_shift", dH, H, HsT, ldt, B, T, H, -1)
+    gate = np.arange(N) % 4
+    ref = np.empty((F, N))
+    for g in range(4):
+        ref[:, gate == g] = np.einsum("btf,btn->fn", X.astype(np.float64) * M[g][:, None, :], dZ[:, :, gate == g].astype(np.float64))
+    hp = np.zeros_like(Hs, dtype=np.float64)
+    hp[:, 1:] = Hs[:, :-1]
+    refU = np.einsum("btk,btn->kn", hp, dZ.astype(np.float64))
+    ws = dev.bytes(dev.lib.mgr_lstm_param_grads_dropout_ts_ws_bytes(B, T, F, H, ldt))
+    gW, gU, gb = dev.empty((F, N)), dev.empty((H, N)), dev.empty((N,))
+    gW.upload(np.full((F, N), np.nan, f32))
+    gU.upload(np.full((H, N), np.nan, f32))
+    dev.call("mgr_memset", ws, 0xFF, ws.nbytes)          # the workspace arrives dirty
+    dev.call("mgr_tune", 12, 1)
+    try:
+        dev.call("mgr_lstm_param_grads_dropout_ts", XS, ldt, dM, p, dH, H, ddZ, gW, gU, gb, B, T, F, H, reverse, ws, ws.nbytes, 0, 0, 0, HsT)
+    finally:
+        dev.call("mgr_tune", 12, 0)
+    for got, want in ((gW.download(), ref), (gU.download(), refU)):
+        cs = np.maximum(np.abs(want).max(axis=0, keepdims=True), 1e-30)      # per column: the spread is per column
+        err = (np.abs(got - want) / cs).max()
+        print("k_dw_split<4>: max error / column maximum %.3e (bound 3e-5)" % err)
+        assert np.all(np.isfinite(got)) and err <= 3e-5, err
+
+
 @pytest.mark.parametrize("hs,B,T", [((500, 300), 40, 21), ((300,), 64, 19), ((100,), 33, 24), ((500,), 16, 9)])
 def test_scans_write_split_rows(device, hs, B, T):
     """mgr_scan_job.yt_split (lstm_cluster.hip, the K-split scan kernels write the transposed copy themselves): the copy in the split
