@@ -1,5 +1,6 @@
 // Job descriptors shared by lstm.hip (planning, admission) and the persistent multi-CU scan kernels
-// (lstm_cluster.hip forward, lstm_cluster_bwd.hip BPTT).
+// (lstm_cluster.hip forward, lstm_cluster_bwd.hip BPTT), and - device section - pieces the persistent scan kernels share:
+// arrival / exit, the octet decode, the give-up protocol of the bounded spins, the LDS-DMA helpers.
 #pragma once
 #include "common.h"
 
@@ -153,6 +154,48 @@ __device__ __forceinline__ bool mgr_cluster_octet(const ClusterCommon& cm, int c
     }
   }
   return same;
+}
+// ---- the give-up protocol: what keeps a lost peer from hanging the GPU.  Every spin of the exchange (a gather that re-fetches until
+// each word shows its epoch parity) counts its WASTED rounds.  Every 256 rounds it reads the launch's give-up word (status[0]) and
+// fails if any workgroup of the launch has given up; beyond kSpinLimit rounds it gives up itself: lane 0 raises MGR_ST_GAVE_UP in
+// the give-up word (relaxed, agent scope), which the peers find and mgr_cluster_exit folds into the sticky status block.  A wave
+// that `failed` stops gathering and runs its remaining steps on whatever it holds: the launch ends, the host reports the status.
+// mgr_spin_tick is one such round for the spins whose counter is an ordinary register (cluster_run, cluster_run_ks,
+// cluster_bwd_run); the counter is the caller's (per step or per launch), s_sleep stays with the caller.  The spins of
+// cluster_run_k16 and cluster_bwd_run16 keep the same text spelled out with counter and flag passed through readfirstlane
+// (hipcc must SEE that they are wave-uniform): taken from here their retry loops compile differently and the training step
+// measured 0.3 - 0.5 % slower (profiles/scan_header_timing.txt).
+constexpr unsigned kSpinLimit = 1u << 20;   // wasted rounds of one counter before its wave gives up (~1 s)
+__device__ __forceinline__ void mgr_spin_tick(unsigned& rounds, bool& failed, unsigned* status, int lane) {
+  ++rounds;
+  if ((rounds & 255u) == 0) {
+    // (through an opaque asm, waited for on the spot: a load hipcc can see inside the polling loops leaves a "maybe pending"
+    // register in its scoreboard, and it then puts an s_waitcnt vmcnt(0) in front of the MFMA chain - behind the Z prefetch)
+    unsigned st;
+    asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(st) : "v"(status) : "memory");
+    if (__builtin_amdgcn_readfirstlane(st) != 0u) failed = true;
+  }
+  if (rounds > kSpinLimit) {
+    failed = true;
+    if (lane == 0) __hip_atomic_store(status, MGR_ST_GAVE_UP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// LDS-DMA: one wave-instruction copies 64 x 16 B (64 x 4 B) from global memory [gbase + voff] (gbase wave-uniform, voff per
+// lane) to LDS [lds_addr + 16 (4) * lane]; M0 carries the LDS address and is restored (hipcc does not know it was touched)
+__device__ __forceinline__ void mgr_dma_b128(const void* gbase, unsigned voff, unsigned lds_addr) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(voff), "s"(gbase), "s"(lds_addr)
+               : "memory");
+}
+__device__ __forceinline__ void mgr_dma_b32(const void* gbase, unsigned voff, unsigned lds_addr) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2 sc1\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(voff), "s"(gbase), "s"(lds_addr)
+               : "memory");
 }
 // which SAMPLE met a non-finite hidden state: bit (b mod 256) of words [8, 16) of the status block (mgr.h, mgr_scan_status_bind)
 __device__ __forceinline__ void mgr_mark_sample(const ClusterCommon& cm, int b) {

@@ -25,7 +25,7 @@
 // (opposite parity) or t, never t+2, because a producer cannot publish epoch t+2 before every peer has published t+1,
 // i.e. finished consuming t.  No fence, no flag round trip, no drain: a step costs ONE store->load flight.
 // hipMalloc memory; slots are zeroed by a memset node ahead of every launch.  Every spin is bounded; a give-up sets
-// status[0] and the host reports an error instead of hanging the GPU.
+// status[0] and the host reports an error instead of hanging the GPU (the give-up protocol: lstm_cluster.h, mgr_spin_tick).
 //
 // Several layer-directions ("jobs": audio fwd/rev, skeletal fwd/rev) share ONE launch so that all spinning workgroups
 // are co-resident by construction (grid <= workgroup slots of the chip); launches on DIFFERENT streams are admitted by
@@ -43,7 +43,6 @@ namespace {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int CL_WAVES = 8;
-constexpr unsigned POLL_LIMIT = 1u << 20;
 
 template <int KS, int TPW>
 __device__ __forceinline__ void cluster_run(const ClusterJob& jb, int bg, int ug, float* smem, unsigned* status) {
@@ -237,12 +236,7 @@ __device__ __forceinline__ void cluster_run(const ClusterJob& jb, int bg, int ug
           }
           if (pend) {
             __builtin_amdgcn_s_sleep(1);
-            ++spins;
-            if ((spins & 255u) == 0 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) failed = true;
-            if (spins > POLL_LIMIT) {
-              failed = true;
-              if (lane == 0) __hip_atomic_store(status, MGR_ST_GAVE_UP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            mgr_spin_tick(spins, failed, status, lane);   // (lstm_cluster.h: the give-up protocol)
           }
         }
       }
@@ -336,25 +330,6 @@ __device__ __forceinline__ void ks_zero_tail(float* row, int T, int ldt, bool sp
     }
   }
 }
-constexpr unsigned KS_ROUND_LIMIT = 1u << 20;  // re-fetch rounds of one wave before it gives up (~1 s)
-
-// LDS-DMA: one wave-instruction copies 64 x 16 B (64 x 4 B) from global memory [gbase + voff] (gbase wave-uniform, voff per
-// lane) to LDS [lds_addr + 16 (4) * lane]; M0 carries the LDS address and is restored (hipcc does not know it was touched)
-__device__ __forceinline__ void mgr_dma_b128(const void* gbase, unsigned voff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(gbase), "s"(lds_addr)
-               : "memory");
-}
-__device__ __forceinline__ void mgr_dma_b32(const void* gbase, unsigned voff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2 sc1\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(gbase), "s"(lds_addr)
-               : "memory");
-}
-
 // LDS of one workgroup (floats): partial sums [2][16][64] f32x4 | 4 staging tiles [8][64] of the transposed output | 4 Z rings
 // [2][64] f32x4 | 4 residual rings [2][64]
 constexpr int KS_LDS_FLOATS = 2 * 16 * 64 * 4 + 4 * KS_STG * 64 + 4 * 2 * 256 + 4 * 2 * 64;
@@ -442,21 +417,7 @@ __device__ __forceinline__ void cluster_run_ks(const ClusterJob& jb, const Clust
   float c = 0.f;
   bool nonfinite = false;
   bool failed = false;
-  unsigned rounds = 0;        // re-fetches / re-polls of the whole launch: the bound of every spin below
-  auto tick = [&]() {         // a wasted round: look at the launch's give-up word now and then, give up after ~1 s of them
-    ++rounds;
-    if ((rounds & 255u) == 0) {
-      // (through an opaque asm, waited for on the spot: a load hipcc can see inside the polling loops leaves a "maybe pending"
-      // register in its scoreboard, and it then puts an s_waitcnt vmcnt(0) in front of the MFMA chain - behind the Z prefetch)
-      unsigned st;
-      asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(st) : "v"(status) : "memory");
-      if (__builtin_amdgcn_readfirstlane(st) != 0u) failed = true;
-    }
-    if (rounds > KS_ROUND_LIMIT) {
-      failed = true;
-      if (lane == 0) __hip_atomic_store(status, MGR_ST_GAVE_UP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  };
+  unsigned rounds = 0;        // re-fetches / re-polls of the whole launch: the bound of every spin below (mgr_spin_tick)
 
   for (int step = 0; step < T; ++step) {
     const int t = reverse ? T - 1 - step : step;
@@ -483,7 +444,7 @@ __device__ __forceinline__ void cluster_run_ks(const ClusterJob& jb, const Clust
         }
         const bool lane_fresh = par ? (a_and & 1u) != 0u : (a_or & 1u) == 0u;
         if (__all(lane_fresh) || failed) break;
-        tick();
+        mgr_spin_tick(rounds, failed, status, lane);
         if (failed) break;
       }
     }
@@ -781,7 +742,7 @@ __device__ __forceinline__ void cluster_run_k16(const ClusterJob& jb, const Clus
       asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(st) : "v"(status) : "memory");
       if (__builtin_amdgcn_readfirstlane(st) != 0u) failed = true;
     }
-    if (rounds > KS_ROUND_LIMIT) {
+    if (rounds > kSpinLimit) {
       failed = true;
       if (lane == 0) __hip_atomic_store(status, MGR_ST_GAVE_UP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }

@@ -14,7 +14,8 @@
 // perturbation of a partial sum); two slots per (destination, source) pair suffice (see lstm_cluster.hip).
 // After the reduction every thread runs the cell backward for ONE (unit, sample): 256 threads = 16 units x 16 samples;
 // saved forward state and dY are prefetched two steps ahead by LDS-DMA through 3-deep per-wave LDS rings.
-// Bounded spins, status word, one launch for all concurrently scanned directions (co-residency by construction).
+// Bounded spins (lstm_cluster.h, mgr_spin_tick), status word, one launch for all concurrently scanned directions (co-residency by
+// construction); the LDS-DMA helpers are lstm_cluster.h's, the cell arithmetic lstm_common.h's.
 //
 // Round 3 (what the forward K-split step taught, lstm_cluster.hip): (i) memory operations complete in issue order, so the
 // prefetch of the saved state (three HBM misses) must be issued BEHIND the gather of the step, not in front of it; (ii) any load
@@ -30,7 +31,6 @@ namespace {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) float lds_float;
-constexpr unsigned POLL_LIMIT = 1u << 20;
 constexpr int BW_WAVES = 4;
 constexpr int BW_RING_FLOATS = 3 * (256 + 64 + 64);   // per compute wave: 3 slots x { gates [64] float4 | dy [64] | c [64] }
 constexpr int BW16_RING_FLOATS = 4 * (256 + 64 + 64);  // cluster_bwd_run16: 4 slots, fetched three steps ahead
@@ -38,23 +38,6 @@ constexpr int BW16_IMG = 4 * 2 * 64 * 2;               // cluster_bwd_run16: flo
 constexpr int BW_LDS_FLOATS_A = 4 * 256 + 5 * 256 + BW_WAVES * BW_RING_FLOATS + 16;   // (+16: the four dz factors of the split-f16 form)
 constexpr int BW_LDS_FLOATS_B = 2 * BW16_IMG + 16 + BW_WAVES * BW16_RING_FLOATS + 1024;
 constexpr int BW_LDS_FLOATS = BW_LDS_FLOATS_A > BW_LDS_FLOATS_B ? BW_LDS_FLOATS_A : BW_LDS_FLOATS_B;   // (what a caller may assume at most)
-
-// LDS-DMA: one wave-instruction copies 64 x 16 B (64 x 4 B) from global memory [gbase + voff] (gbase wave-uniform, voff per
-// lane) to LDS [lds_addr + 16 (4) * lane]; M0 carries the LDS address and is restored (hipcc does not know it was touched)
-__device__ __forceinline__ void mgr_dma_b128(const void* gbase, unsigned voff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(gbase), "s"(lds_addr)
-               : "memory");
-}
-__device__ __forceinline__ void mgr_dma_b32(const void* gbase, unsigned voff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2 sc1\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(gbase), "s"(lds_addr)
-               : "memory");
-}
 
 // SPLIT = false: 4 waves, each gathers its share of the incoming partial tiles AND computes / stores its outgoing ones.
 // SPLIT = true : 8 waves, one workgroup per CU.  Waves 0-3 only compute and store, waves 4-7 only gather: a gather wave
@@ -81,22 +64,6 @@ extern "C" int mgr_debug_bstamps(unsigned long long* out) {
 #else
 #define BSTAMP(i, dep) do { } while (0)
 #endif
-// DPP with the lane's own value where a row has no source (ctc.hip, dpp_f32)
-template <int CTRL>
-__device__ __forceinline__ float bw_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// mgr_cell_bwd with tanh(c) given: both forms of the step below go through THIS function with an opaque tc, so that hipcc contracts the
-// cell arithmetic the same way in both (their results are compared bit for bit)
-__device__ __forceinline__ float4 mgr_cell_bwd_tc(float dh, float4 g4, float tc, float c_prev, float& dc_carry) {
-#pragma clang fp contract(off)   // (every fused operation below is written out: no context-dependent contraction)
-  const float i = g4.x, f = g4.y, g = g4.z, o = g4.w;
-  const float dO = dh * tc;
-  const float dc = __builtin_fmaf(dh * o, __builtin_fmaf(-tc, tc, 1.f), dc_carry);
-  const float di = dc * g, df = dc * c_prev, dg = dc * i;
-  dc_carry = dc * f;
-  return make_float4(di * mgr_hsig_grad(i), df * mgr_hsig_grad(f), dg * __builtin_fmaf(-g, g, 1.f), dO * mgr_hsig_grad(o));
-}
 template <int H, bool SPLIT, bool F16>
 __device__ __forceinline__ void cluster_bwd_run(const ClusterBwdJob& jb, int bg, int ug, float* smem, unsigned* status, bool fast) {
   constexpr int N = 4 * H;
@@ -239,16 +206,7 @@ __device__ __forceinline__ void cluster_bwd_run(const ClusterBwdJob& jb, int bg,
           }
           if (pend) {
             __builtin_amdgcn_s_sleep(1);
-            ++spins;
-            if ((spins & 255u) == 0) {   // (opaque to hipcc, waited for on the spot: no load of its own may stay pending)
-              unsigned st;
-              asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(st) : "v"(status) : "memory");
-              if (__builtin_amdgcn_readfirstlane(st) != 0u) failed = true;
-            }
-            if (spins > POLL_LIMIT) {
-              failed = true;
-              if (lane == 0) __hip_atomic_store(status, MGR_ST_GAVE_UP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            mgr_spin_tick(spins, failed, status, lane);   // (lstm_cluster.h: the give-up protocol)
           }
         }
         // fixed summation order: sources wave, wave+4, ... ascending (own tile in its place)
@@ -322,10 +280,10 @@ __device__ __forceinline__ void cluster_bwd_run(const ClusterBwdJob& jb, int bg,
           //  ds_bpermute round trips and frexpf / ldexpf - the same factor bit for bit, cluster_bwd_run16 below; the 4-wave form keeps
           //  the old sequence: it is the one that runs beside the encoder scans of config F, where every change of its timing is a
           //  change of the whole step, profiles/r05_bptt_probes.txt)
-          m = fmaxf(m, bw_dpp<0x111>(m));   // row_shr:1, 2, 4, 8: lane 15 of a row holds the row's maximum
-          m = fmaxf(m, bw_dpp<0x112>(m));
-          m = fmaxf(m, bw_dpp<0x114>(m));
-          m = fmaxf(m, bw_dpp<0x118>(m));
+          m = fmaxf(m, mgr_dpp<0x111>(m));   // row_shr:1, 2, 4, 8: lane 15 of a row holds the row's maximum
+          m = fmaxf(m, mgr_dpp<0x112>(m));
+          m = fmaxf(m, mgr_dpp<0x114>(m));
+          m = fmaxf(m, mgr_dpp<0x118>(m));
           const int mi = __float_as_int(m);
           m = fmaxf(fmaxf(__int_as_float(__builtin_amdgcn_readlane(mi, 15)), __int_as_float(__builtin_amdgcn_readlane(mi, 31))),
                     fmaxf(__int_as_float(__builtin_amdgcn_readlane(mi, 47)), __int_as_float(__builtin_amdgcn_readlane(mi, 63))));
@@ -613,7 +571,7 @@ __device__ __forceinline__ void cluster_bwd_run16(const ClusterBwdJob& jb, int b
             asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(st) : "v"(status) : "memory");
             if (__builtin_amdgcn_readfirstlane(st) != 0u) failed = true;
           }
-          if (spins > POLL_LIMIT) {
+          if (spins > kSpinLimit) {
             failed = true;
             if (lane == 0) __hip_atomic_store(status, MGR_ST_GAVE_UP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
@@ -662,7 +620,7 @@ __device__ __forceinline__ void cluster_bwd_run16(const ClusterBwdJob& jb, int b
             asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(st) : "v"(status) : "memory");
             if (__builtin_amdgcn_readfirstlane(st) != 0u) failed = true;
           }
-          if (spins > POLL_LIMIT) {
+          if (spins > kSpinLimit) {
             failed = true;
             if (lane == 0) __hip_atomic_store(status, MGR_ST_GAVE_UP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
@@ -713,10 +671,10 @@ __device__ __forceinline__ void cluster_bwd_run16(const ClusterBwdJob& jb, int b
       // this wave's factor: the power of two that puts its largest |dz| of the step in [2^14, 2^15) (wave-uniform: scalar arithmetic
       // on the exponent field; zero, Inf / NaN -> 2^15 as before - a NaN gradient stays visible in dZ)
       float m = fmaxf(fmaxf(fabsf(dz.x), fabsf(dz.y)), fmaxf(fabsf(dz.z), fabsf(dz.w)));
-      m = fmaxf(m, bw_dpp<0x111>(m));   // row_shr:1, 2, 4, 8: lane 15 of a row holds the row's maximum
-      m = fmaxf(m, bw_dpp<0x112>(m));
-      m = fmaxf(m, bw_dpp<0x114>(m));
-      m = fmaxf(m, bw_dpp<0x118>(m));
+      m = fmaxf(m, mgr_dpp<0x111>(m));   // row_shr:1, 2, 4, 8: lane 15 of a row holds the row's maximum
+      m = fmaxf(m, mgr_dpp<0x112>(m));
+      m = fmaxf(m, mgr_dpp<0x114>(m));
+      m = fmaxf(m, mgr_dpp<0x118>(m));
       const int mi = __float_as_int(m);
       m = fmaxf(fmaxf(__int_as_float(__builtin_amdgcn_readlane(mi, 15)), __int_as_float(__builtin_amdgcn_readlane(mi, 31))),
                 fmaxf(__int_as_float(__builtin_amdgcn_readlane(mi, 47)), __int_as_float(__builtin_amdgcn_readlane(mi, 63))));   // (fmaxf drops a NaN as before)

@@ -1,4 +1,5 @@
-// Device helpers shared by the LSTM scan kernels (Keras LSTMCell semantics; reference call sites
+// Device helpers shared by the LSTM scan kernels: the cell functions, forward and BPTT, and the DPP move (Keras LSTMCell
+// semantics; reference call sites
 // multimodal_fusion/multimodal.py:159-168: activation='tanh', recurrent_activation='hard_sigmoid').
 #pragma once
 #include "common.h"
@@ -31,4 +32,22 @@ __device__ __forceinline__ float4 mgr_cell_bwd(float dh, float4 g4, float c, flo
   float di = dc * g, df = dc * c_prev, dg = dc * i;
   dc_carry = dc * f;
   return make_float4(di * mgr_hsig_grad(i), df * mgr_hsig_grad(f), dg * (1.f - g * g), dO * mgr_hsig_grad(o));
+}
+// mgr_cell_bwd with tanh(c) given: every split-f16 form of the BPTT step (lstm_cluster_bwd.hip: cluster_bwd_run, cluster_bwd_run16;
+// lstm_cu_bwd.hip) goes through THIS function with an opaque tc, so that hipcc contracts the cell arithmetic the same way in all of
+// them (the multi-CU forms are compared bit for bit)
+__device__ __forceinline__ float4 mgr_cell_bwd_tc(float dh, float4 g4, float tc, float c_prev, float& dc_carry) {
+#pragma clang fp contract(off)   // (every fused operation below is written out: no context-dependent contraction)
+  const float i = g4.x, f = g4.y, g = g4.z, o = g4.w;
+  const float dO = dh * tc;
+  const float dc = __builtin_fmaf(dh * o, __builtin_fmaf(-tc, tc, 1.f), dc_carry);
+  const float di = dc * g, df = dc * c_prev, dg = dc * i;
+  dc_carry = dc * f;
+  return make_float4(di * mgr_hsig_grad(i), df * mgr_hsig_grad(f), dg * __builtin_fmaf(-g, g, 1.f), dO * mgr_hsig_grad(o));
+}
+
+// DPP with the lane's own value where a row has no source (ctc_lattice.h has the same for the lattices, dpp_f32)
+template <int CTRL>
+__device__ __forceinline__ float mgr_dpp(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xf, 0xf, false));
 }

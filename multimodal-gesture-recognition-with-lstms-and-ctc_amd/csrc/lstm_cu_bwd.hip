@@ -22,7 +22,8 @@
 // Scaling as in lstm_cluster_bwd.hip (F16): U by the power of two that puts the workgroup's largest |U| in [2^14, 2^15); dz per source
 // wave and step by the power of two that puts ITS largest |dz| in [2^14, 2^15), the factor left beside the image; one accumulator
 // per source wave, the partial sums meet as f32, each multiplied by its source's inverse factor (exact scaling) in ascending wave order.
-// Saved forward state comes by LDS-DMA: gates (16 B per cell) and dY rows into a two-slot ring per wave, fetched two steps ahead; the cell
+// Saved forward state comes by LDS-DMA (lstm_cluster.h, mgr_dma_b128): gates (16 B per cell) and dY rows into a two-slot ring per
+// wave, fetched two steps ahead; the cell
 // states into a four-slot ring fetched THREE steps ahead (a step needs c of its own time step and of the next iteration's).  One barrier
 // per step (the dz image is double-buffered on the step parity).
 #include "lstm_cluster.h"
@@ -33,28 +34,6 @@ namespace {
 
 typedef __attribute__((address_space(3))) float lds_float;
 constexpr int CB_WAVES = 8;
-
-__device__ __forceinline__ void cb_dma_b128(const void* gbase, unsigned voff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(gbase), "s"(lds_addr)
-               : "memory");
-}
-template <int CTRL>
-__device__ __forceinline__ float cb_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// (the arithmetic of lstm_cluster_bwd.hip's mgr_cell_bwd_tc: every fused operation written out)
-__device__ __forceinline__ float4 cb_cell_bwd(float dh, float4 g4, float tc, float c_prev, float& dc_carry) {
-#pragma clang fp contract(off)
-  const float i = g4.x, f = g4.y, g = g4.z, o = g4.w;
-  const float dO = dh * tc;
-  const float dc = __builtin_fmaf(dh * o, __builtin_fmaf(-tc, tc, 1.f), dc_carry);
-  const float di = dc * g, df = dc * c_prev, dg = dc * i;
-  dc_carry = dc * f;
-  return make_float4(di * mgr_hsig_grad(i), df * mgr_hsig_grad(f), dg * __builtin_fmaf(-g, g, 1.f), dO * mgr_hsig_grad(o));
-}
 
 template <int H>
 struct CbCfg {
@@ -157,13 +136,13 @@ __global__ __launch_bounds__(CB_WAVES * 64, 1) void k_scan_bwd_cu16(CuBwdJobs J,
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int ec = 16 * wave + 4 * e < H ? e : 0;   // (wave-uniform)
-        cb_dma_b128(G + ((size_t)t * H + 4 * ec) * 4, goff, base + e * 1024);
+        mgr_dma_b128(G + ((size_t)t * H + 4 * ec) * 4, goff, base + e * 1024);
       }
-      cb_dma_b128(dY + (size_t)t * lddy, dyoff, base + 4096);
+      mgr_dma_b128(dY + (size_t)t * lddy, dyoff, base + 4096);
     }
   };
   auto prefetch_c = [&](int k) {     // cell states of iteration k -> c ring slot k & 3 (one instruction)
-    if (wact && k < T) cb_dma_b128(Cs + (size_t)row_of(k) * H, coff, cring_lds + (unsigned)(k & 3) * 1024);
+    if (wact && k < T) mgr_dma_b128(Cs + (size_t)row_of(k) * H, coff, cring_lds + (unsigned)(k & 3) * 1024);
   };
   prefetch(0);
   prefetch(1);
@@ -204,7 +183,7 @@ __global__ __launch_bounds__(CB_WAVES * 64, 1) void k_scan_bwd_cu16(CuBwdJobs J,
     for (int e = 0; e < 4; ++e) {
       dz[e] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (e < NE) {   // (wave-uniform)
-        dz[e] = cb_cell_bwd(dy[e] + dhr[e], g4[e], mgr_tanh(cc[e]), cp[e], dcc[e]);
+        dz[e] = mgr_cell_bwd_tc(dy[e] + dhr[e], g4[e], mgr_tanh(cc[e]), cp[e], dcc[e]);
         if (bvalid) *reinterpret_cast<float4*>(dZ + ((size_t)b * T + t) * N + (16 * wave + 4 * e + uq) * 4) = dz[e];
       }
     }
@@ -215,10 +194,10 @@ __global__ __launch_bounds__(CB_WAVES * 64, 1) void k_scan_bwd_cu16(CuBwdJobs J,
       float m = 0.f;
 #pragma unroll
       for (int e = 0; e < 4; ++e) m = fmaxf(m, fmaxf(fmaxf(fabsf(dz[e].x), fabsf(dz[e].y)), fmaxf(fabsf(dz[e].z), fabsf(dz[e].w))));
-      m = fmaxf(m, cb_dpp<0x111>(m));   // row_shr:1, 2, 4, 8: lane 15 of a row holds the row's maximum
-      m = fmaxf(m, cb_dpp<0x112>(m));
-      m = fmaxf(m, cb_dpp<0x114>(m));
-      m = fmaxf(m, cb_dpp<0x118>(m));
+      m = fmaxf(m, mgr_dpp<0x111>(m));   // row_shr:1, 2, 4, 8: lane 15 of a row holds the row's maximum
+      m = fmaxf(m, mgr_dpp<0x112>(m));
+      m = fmaxf(m, mgr_dpp<0x114>(m));
+      m = fmaxf(m, mgr_dpp<0x118>(m));
       const int mi = __float_as_int(m);
       m = fmaxf(fmaxf(__int_as_float(__builtin_amdgcn_readlane(mi, 15)), __int_as_float(__builtin_amdgcn_readlane(mi, 31))),
                 fmaxf(__int_as_float(__builtin_amdgcn_readlane(mi, 47)), __int_as_float(__builtin_amdgcn_readlane(mi, 63))));

@@ -501,6 +501,75 @@ def test_bwd_multi_matches_oracle(device, B, T, H, path, f32_mfma):
         dev.call("mgr_tune", 1, 0)
 
 
+@pytest.mark.parametrize("H,B,T", [(100, 17, 12), (300, 33, 8)])
+def test_contiguous_cluster_ids_match_oracle_and_the_octet_layout(device, H, B, T):
+    """Tune key 3 = 1: the clusters of the K-split scans and of the multi-CU BPTT sit on CONTIGUOUS workgroup ids (what a batch beyond
+    256 takes as well) instead of XCD-local octets - the other branch of every kernel's walk over the job table.  Both directions in one
+    forward call with the states saved, BPTT over them: against the oracle, and bit for bit what the octet layout gives (placement is
+    speed, never arithmetic).  H = 100: seven unit groups, an odd count."""
+    import ctypes
+    from mgr_amd import _capi
+    dev = device
+    rng = np.random.default_rng(H * 3 + B)
+    F = 5
+    f32 = np.float32
+    fj, bj, refs, keep = [], [], [], []
+    for reverse in (0, 1):
+        x, W, U, b, _ = _lstm_case(rng, B, T, F, H, 0.0)
+        U = U * (0.1 if H >= 300 else 1.0)
+        y_ref, cache = kr.lstm_forward(x, W, U, b, None, bool(reverse))
+        dy = np.ascontiguousarray(rng.standard_normal((B, T, H)))
+        dx_ref, dW_ref, dU_ref, db_ref = kr.lstm_backward(dy, cache, need_dx=True)
+        Wp, Up, bp = dev.empty((F, 4 * H)), dev.empty((H, 4 * H)), dev.empty((4 * H,))
+        dev.call("mgr_lstm_pack", dev.array(W.astype(f32)), Wp, F, H, 0)
+        dev.call("mgr_lstm_pack", dev.array(U.astype(f32)), Up, H, H, 0)
+        dev.call("mgr_lstm_pack", dev.array(b.astype(f32)), bp, 1, H, 0)
+        dX = dev.array(x.astype(f32))
+        Z = dev.empty((B, T, 4 * H))
+        dev.call("mgr_lstm_input_proj", dX, F, 0, Wp, bp, Z, B, T, F, H)
+        Y, G, Cs, dZ = dev.empty((B, T, H)), dev.empty((B, T, H, 4)), dev.empty((B, T, H)), dev.empty((B, T, 4 * H))
+        fj.append(dict(Z=Z, Up=Up, Y=Y, ldy=H, R=0, ldr=0, gates=G, cs=Cs, B=B, T=T, H=H, reverse=reverse))
+        bj.append(dict(dY=dev.array(dy.astype(f32)), gates=G, cs=Cs, Up=Up, dZ=dZ, lddy=H, B=B, T=T, H=H, reverse=reverse))
+        refs.append((y_ref, cache, dx_ref, dU_ref))
+        keep += [Wp, bp, dX]
+    farr, barr = _capi.make_scan_jobs(fj), _capi.make_scan_bwd_jobs(bj)
+    fws = dev.bytes(dev.lib.mgr_lstm_scan_multi_ws_bytes(2, farr))
+    bws = dev.bytes(dev.lib.mgr_lstm_scan_bwd_multi_ws_bytes(2, barr))
+    nan = np.full((B, T, 4 * H), np.nan, f32)
+    got = {}
+    dev.call("mgr_tune", 1, 1)  # synchronous give-up check
+    try:
+        for contiguous in (0, 1):
+            dev.call("mgr_tune", 3, contiguous)
+            for f, bw in zip(fj, bj):      # dirty outputs: each layout must write every word itself
+                f["Y"].upload(nan[:, :, :H]), f["gates"].upload(nan), f["cs"].upload(nan[:, :, :H]), bw["dZ"].upload(nan)
+            _capi.check(dev.lib.mgr_lstm_scan_fwd_multi(dev.ctx, 2, farr, fws.ptr, fws.nbytes))
+            _capi.check(dev.lib.mgr_lstm_scan_bwd_multi(dev.ctx, 2, barr, bws.ptr, bws.nbytes))
+            got[contiguous] = [(f["Y"].download(), f["gates"].download(), f["cs"].download(), bw["dZ"].download()) for f, bw in zip(fj, bj)]
+    finally:
+        dev.call("mgr_tune", 3, 0)
+        dev.call("mgr_tune", 1, 0)
+    for reverse, ((Yh, Gh, Ch, dZh), (y_ref, cache, dx_ref, dU_ref)) in enumerate(zip(got[1], refs)):
+        assert rel_err(Yh, y_ref) < 3e-5
+        assert rel_err(Ch, cache["c"]) < 3e-5
+        assert rel_err(Gh[..., 3], cache["o"]) < 3e-5
+        dZ = bj[reverse]["dZ"]     # (holds the contiguous layout's result: it ran last)
+        gW, gU, gb = dev.empty((F, 4 * H)), dev.empty((H, 4 * H)), dev.empty((4 * H,))
+        ws2 = dev.bytes(dev.lib.mgr_lstm_param_grads_ws_bytes(B, T, F, H))
+        dev.call("mgr_lstm_param_grads", keep[3 * reverse + 2], F, 0, fj[reverse]["Y"], H, dZ, gW, gU, gb, B, T, F, H, reverse, ws2, ws2.nbytes)
+        gUk = dev.empty((H, 4 * H))
+        dev.call("mgr_lstm_pack", gU, gUk, H, H, 1)
+        assert rel_err(gUk.download(), dU_ref) < 1e-4
+        gX = dev.empty((B, T, F))
+        dev.call("mgr_lstm_input_grad", dZ, keep[3 * reverse], 0, gX, F, 0, B, T, F, H)
+        assert rel_err(gX.download(), dx_ref) < 1e-4
+        for a, o in zip(got[1][reverse], got[0][reverse]):
+            assert np.array_equal(a, o)
+    st = ctypes.c_uint(7)
+    dev.call("mgr_scan_status", ctypes.byref(st))     # no persistent scan of this context ever gave up
+    assert st.value == 0
+
+
 @pytest.mark.parametrize("H,B,T", [(100, 20, 24), (300, 18, 16), (500, 33, 12)])
 @pytest.mark.parametrize("scale", [1e-4, 1.0, 1.5])
 def test_split_f16_scan_over_weight_scales(device, H, B, T, scale):
