@@ -638,6 +638,36 @@ int mgr_ctc_rescore(mgr_ctx* ctx, const float* P, const int32_t* input_len, int 
                     const int32_t* phrase_off, const int32_t* phrase_words, int G, const int32_t* hyp, const int32_t* hyp_len, int K,
                     int Lh, double* logp, int32_t* n_lab, void* ws, size_t ws_bytes);
 
+/* ---- K15: expected risk over an N-best list and its gradient: what sequence-level minimum-risk training (MWER / minimum
+ * expected error) needs beside K11's N-best lists, K12's edit distances and K14's scores - the gradient through all K likelihoods of a
+ * sample in one call.  Per sample: K hypothesis slots (hyp / hyp_len / the lexicon exactly as K14 takes them) and one integer risk
+ * r_k per slot (risk [B,K] int32, device: what mgr_edit_distance writes as dist for pair b * K + k).  logp_k is K14's logp: the same
+ * frames, skip, eps, blank, label clipping and expansion.  A slot is LIVE if it is present (hyp_len >= 0), scored (no phrase id outside
+ * [0, G), at most Lcap labels after expansion) and feasible (logp_k > -inf).  Over the live slots, with a = post_scale > 0:
+ *     w_k      = exp(a logp_k) / sum_j exp(a logp_j)          (differences taken in fp64)
+ *     Rbar     = sum_k w_k r_k risk_scale                      -> exp_risk[b]
+ *     g_k      = a w_k (r_k risk_scale - Rbar)                 = dRbar / dlogp_k
+ *     dLogits  = gscale sum_k g_k dlogp_k/dlogits
+ * where dlogp_k/dlogits is minus what mgr_ctc_loss_grad writes into dLogits for the label row = hypothesis k at gscale = 1: the
+ * gradient w.r.t. the Dense logits (P = softmax(logits)), the eps handling and the zeros on the skipped frames and on the frames from
+ * skip + Tp on are k_ctc_grad's, applied linearly.  Since sum_k g_k = 0 the k-independent term of the loss gradient cancels; the
+ * kernel sums only the g_k-weighted state occupancies.  Non-live slots have w_k = 0; with fewer than two live slots the gradient is
+ * zero, with none exp_risk is 0.
+ * Outputs (device): logp [B,K] double (K14's table, and NaN for a slot with more than Lcap labels), weight [B,K] or NULL, exp_risk
+ * [B], dLogits [B,T,C] or NULL (then no lattice is stored).  accumulate != 0: dLogits += instead of =, so a caller that has the CTC
+ * gradient in dLogits needs no add pass (frames that get zero are then left as they are).
+ * 1 <= K <= MGR_RISK_MAX_SLOTS; 1 <= Lcap <= MGR_RESCORE_MAX_LABELS is the longest expanded hypothesis the workspace holds.  The
+ * workspace keeps the class-major emissions and alpha and beta of every slot: B K T 2 (Lcap + 1) 8 bytes beside the small blocks -
+ * about 0.6 GB at B = 64, K = 8, T = 1900, Lcap = 40 (computed).  Its size does not depend on the lexicon (the query takes it for
+ * symmetry with the call, as K13 / K14).  No atomics: deterministic, and a sample's rows do not depend on the rest of the batch.
+ * B <= 65535. */
+#define MGR_RISK_MAX_SLOTS 32
+size_t mgr_ctc_risk_ws_bytes(int B, int T, int C, int K, int Lcap, int G, const int32_t* phrase_off);
+int mgr_ctc_risk_grad(mgr_ctx* ctx, const float* P, const int32_t* input_len, int B, int T, int C, int skip, int blank, float eps,
+                      const int32_t* phrase_off, const int32_t* phrase_words, int G, const int32_t* hyp, const int32_t* hyp_len, int K,
+                      int Lh, int Lcap, const int32_t* risk, float risk_scale, float post_scale, float gscale, int accumulate,
+                      double* logp, float* weight, float* exp_risk, float* dLogits, void* ws, size_t ws_bytes);
+
 /* ---- K12: scoring decodes: the weighted edit distance of n_pairs pairs of label sequences, with the substitution /
  * deletion / insertion split of HTK's HResults, in one launch.  All pointers are device memory.
  * hyp [n_hyp,Lh], ref [n_ref,Lr] int32, rows padded with -1; hyp_len [n_hyp] / ref_len [n_ref] int32 or NULL: NULL = the whole row,

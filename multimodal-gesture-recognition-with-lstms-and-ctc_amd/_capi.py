@@ -132,6 +132,9 @@ SIGNATURES = {
                                      sz]),
     "mgr_ctc_rescore_ws_bytes": (sz, [i32, i32, i32, i32, vp]),
     "mgr_ctc_rescore": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, sz]),
+    "mgr_ctc_risk_ws_bytes": (sz, [i32, i32, i32, i32, i32, i32, vp]),
+    "mgr_ctc_risk_grad": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, i32, i32, i32, vp, C.c_float, C.c_float,
+                                C.c_float, i32, vp, vp, vp, vp, vp, sz]),
     "mgr_edit_distance_ws_bytes": (sz, [i32, i32, i32, i32]),
     "mgr_edit_distance": (i32, [vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, u64, vp, vp, vp, vp, vp, vp, sz]),
     "mgr_conv_pool_fwd": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),

@@ -1,8 +1,8 @@
 """Decode for the audio network (reference audio_network/sequence_decoding.py:19-69): word-level classes, thr .75."""
 import numpy as np
 
-from ..decoding import (HTK_COSTS, decode_beam_mlf, decode_lexicon_mlf, decode_score_map, greedy_decode, greedy_decode_argmax,
-                        greedy_segments, write_mlf)
+from ..decoding import (HTK_COSTS, decode_beam_mlf, decode_lexicon_mlf, decode_score_map, expected_risk_map, greedy_decode,
+                        greedy_decode_argmax, greedy_segments, write_mlf)
 from .data_generator import class_2_words
 
 _words = ["oov", "Vattene", "Vieni", "qui", "Perfetto", "E'", "un", "furbo", "Che", "due", "palle", "vuoi", "Vanno",
@@ -72,3 +72,10 @@ def decode_score(hyp_ids, ref_ids, costs=HTK_COSTS, confusion=True):
     """HResults-style counts (H, S, D, I, corr, acc, confusion matrix) of decoded label ids against reference label ids on the device,
     "sil" dropped from both (decoding.decode_score_map with this module's class map)."""
     return decode_score_map(hyp_ids, ref_ids, map_gest, costs=costs, confusion=confusion)
+
+
+def expected_risk(pred_out, paths_or_arrays, ref_ids, costs=HTK_COSTS, **kwargs):
+    """The expected edit distance of N-best lists to the reference label ids under the network's own posterior over them, and its
+    gradient w.r.t. the Dense logits - the loss of minimum-risk fine-tuning (decoding.expected_risk_map with this module's class map:
+    "sil" dropped from both sides, HResults' costs)."""
+    return expected_risk_map(pred_out, paths_or_arrays, ref_ids, map_gest, costs=costs, **kwargs)

@@ -1,6 +1,6 @@
 // The CTC lattice, once: what every kernel that walks the extended label sequence l' = [blank, l1, blank, ..., lL, blank] shares - the
-// loss (ctc.hip), forced alignment (align.hip), hypothesis scoring (rescore.hip) - and the smaller pieces the lexicon decode
-// (lexicon.hip) and the edit distance (edit.hip) take from the same place.  Every numerics decision of the loss lives here: base-2 raw
+// loss (ctc.hip), forced alignment (align.hip), hypothesis scoring (rescore.hip), the expected-risk gradient (risk.hip) - and the
+// smaller pieces the lexicon decode (lexicon.hip) and the edit distance (edit.hip) take from the same place.  Every numerics decision of the loss lives here: base-2 raw
 // exp / log, the -3e38 floor, DPP in place of ds_bpermute, the renormalisation, the skip onto a different label only.
 //
 // Form: the extended sequence lies across the lanes of ONE WAVE as (blank, label) PAIRS - pair p = lane * PPL + j holds states 2p (blank)
@@ -9,8 +9,9 @@
 // ahead of the recursion with 16-byte loads, so the serial chain per step is shift -> combine -> add.
 //
 // What is here is pieces, not a recursion: each kernel keeps its own loop - its chunk origin, its renormalisation cadence, what it stores
-// per step - because those decide the bits of its result.  The max / back-pointer step (align.hip) and the beta step (ctc.hip) have one
-// user each and live there.  Everything is force-inlined into its caller: a translation unit pays for what it uses.
+// per step - because those decide the bits of its result.  The max / back-pointer step (align.hip) and the beta steps (ctc.hip, whose
+// step is interleaved with its two-steps-a-time stores, and risk.hip) have one user each and live there.  Everything is force-inlined
+// into its caller: a translation unit pays for what it uses.
 #pragma once
 #include "common.h"
 
@@ -234,6 +235,56 @@ static inline int lex_arg_pack(LexArg* lex, const int32_t* phrase_off, const int
     lex->words[j] = (uint8_t)phrase_words[j];
   }
   return 0;
+}
+
+// the lexicon argument into the workgroup's LDS: s_off [MGR_LEXICON_MAX_PHRASES + 1], s_words [MGR_LEXICON_MAX_WORDS + 1] (the caller
+// synchronises)
+__device__ __forceinline__ void lex_to_lds(const LexArg& lex, int G, int* s_off, int* s_words, int tid, int nthreads) {
+  if (G <= 0) return;
+  for (int i = tid; i <= G; i += nthreads) s_off[i] = lex.off[i];
+  for (int i = tid; i <= MGR_LEXICON_MAX_WORDS; i += nthreads) s_words[i] = lex.words[i];
+}
+
+// One slot of an N-best list (hyp [.., Lh] / hyp_len as mgr_ctc_beam_search_lm writes out / out_len), expanded by ONE WAVE into the
+// labels the lattice runs over: without a lexicon (G = 0) the entries themselves, clipped into the class range as the loss clips them,
+// with one the words of its phrases - sixty-four entries a turn, a prefix sum of the phrase lengths across the wave.  s_lab holds
+// cap + 1 labels; what lies behind is counted and not written.  All members are wave-uniform.
+struct HypLabels {
+  int n;      // the slot's entries (clipped to Lh); < 0: no hypothesis in this slot
+  int L;      // the expanded count
+  bool bad;   // a phrase id outside [0, G)
+};
+__device__ __forceinline__ HypLabels hyp_expand(const int32_t* __restrict__ row, int n, int Lh, int G, const int* s_off, const int* s_words,
+                                                int C, int* s_lab, int cap, int lane) {
+  HypLabels h;
+  h.n = n > Lh ? Lh : n;
+  h.L = 0;
+  h.bad = false;
+  for (int base = 0; base < h.n; base += 64) {
+    const int i = base + lane;
+    int v = i < h.n ? row[i] : 0, len = 0, w0 = 0;
+    bool badl = false;
+    if (i < h.n) {
+      if (G > 0) {
+        if (v < 0 || v >= G) badl = true;
+        else { w0 = s_off[v]; len = s_off[v + 1] - w0; }
+      } else {
+        v = clip_label(v, C);   // (as the loss)
+        len = 1;
+      }
+    }
+    int x = len;   // inclusive prefix sum of the lengths over the wave
+    for (int o = 1; o < 64; o <<= 1) {
+      const int y = __shfl_up(x, o);
+      if (lane >= o) x += y;
+    }
+    const int start = h.L + x - len;
+    for (int q = 0; q < len; ++q)
+      if (start + q <= cap) s_lab[start + q] = G > 0 ? s_words[w0 + q] : v;
+    h.L += __shfl(x, 63);
+    h.bad = h.bad || __any(badl ? 1 : 0);
+  }
+  return h;
 }
 
 }  // namespace

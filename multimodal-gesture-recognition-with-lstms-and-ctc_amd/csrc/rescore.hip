@@ -6,8 +6,8 @@
 // and read by the sample's K hypotheses out of L2.  k_rescore: ONE WAVE per hypothesis, four hypotheses of a sample per workgroup - the
 // hardware deals a workgroup's waves round over the CU's four SIMDs, so the four chains do not share one (ctc.hip, round 6: chains on
 // one SIMD slow each other down).
-// Prologue: the wave expands its hypothesis into LDS - without a lexicon the labels themselves (clipped into the class range as the loss
-// clips them), with one the words of its phrases: sixty-four entries at a time, a prefix sum of the phrase lengths across the wave.
+// Prologue: the wave expands its hypothesis into LDS (hyp_expand of ctc_lattice.h, shared with risk.hip) - without a lexicon the labels
+// themselves, with one the words of its phrases.
 // Recursion: the loss's alpha, from the pieces of ctc_lattice.h - the (blank, label) pairs across the lanes, PPL pairs per lane, the
 // alpha step in base-2 units on the raw exp / log instructions, the renormalisation, emissions fetched a chunk (8 frames, 4 from
 // PPL = 3 on) ahead with 16-byte loads.  The wave picks PPL from its OWN expanded length (a wave-uniform branch: gesture hypotheses
@@ -71,45 +71,15 @@ __global__ __launch_bounds__(64 * WPB) void k_rescore(const float* __restrict__ 
   const int b = blockIdx.y, k = blockIdx.x * WPB + wave;
   const int To = T - skip;
   const size_t TS = rs_ts(To);
-  if (G > 0) {
-    for (int i = tid; i <= G; i += 64 * WPB) s_off[i] = lex.off[i];
-    for (int i = tid; i <= MGR_LEXICON_MAX_WORDS; i += 64 * WPB) s_words[i] = lex.words[i];
-  }
+  lex_to_lds(lex, G, s_off, s_words, tid, 64 * WPB);
   __syncthreads();
 
-  // ---- expansion: the hypothesis' entries (phrase ids with a lexicon, labels without) -> its labels in s_lab[wave], 64 entries a turn
+  // ---- expansion: the hypothesis' entries (phrase ids with a lexicon, labels without) -> its labels in s_lab[wave]
   const bool active = k < K;
-  int n = active ? hyp_len[(size_t)b * K + k] : -1;
-  if (n > Lh) n = Lh;
-  int L = 0;          // the expanded count (wave-uniform)
-  bool bad = false;   // a phrase id outside [0, G)
-  if (n > 0) {
-    const int32_t* row = hyp + ((size_t)b * K + k) * Lh;
-    for (int base = 0; base < n; base += 64) {
-      const int i = base + lane;
-      int v = i < n ? row[i] : 0, len = 0, w0 = 0;
-      bool badl = false;
-      if (i < n) {
-        if (G > 0) {
-          if (v < 0 || v >= G) badl = true;
-          else { w0 = s_off[v]; len = s_off[v + 1] - w0; }
-        } else {
-          v = clip_label(v, C);   // (as the loss)
-          len = 1;
-        }
-      }
-      int x = len;   // inclusive prefix sum of the lengths over the wave
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-      }
-      const int start = L + x - len;
-      for (int q = 0; q < len; ++q)
-        if (start + q <= MAXL) s_lab[wave][start + q] = G > 0 ? s_words[w0 + q] : v;
-      L += __shfl(x, 63);
-      bad = bad || __any(badl ? 1 : 0);
-    }
-  }
+  const HypLabels h = hyp_expand(hyp + ((size_t)b * K + (active ? k : 0)) * Lh, active ? hyp_len[(size_t)b * K + k] : -1, Lh, G, s_off,
+                                 s_words, C, s_lab[wave], MAXL, lane);
+  const int n = h.n, L = h.L;
+  const bool bad = h.bad;
   __syncthreads();   // (every wave arrives: nothing above returns)
   if (!active) return;
 

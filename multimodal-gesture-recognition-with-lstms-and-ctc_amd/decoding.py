@@ -885,6 +885,102 @@ def mbr_decode(paths, scores, scale=1.0, costs=(1, 1, 1), dev=None):
     return picks, ranks, risk
 
 
+# ---- minimum-risk training (K15): the expected edit distance over an N-best list and its gradient ----------------------
+RISK_MAX_SLOTS = 32       # MGR_RISK_MAX_SLOTS of include/mgr.h
+
+
+def risk_label_cap(hyp, hyp_len, lex_off=None):
+    """Lcap for mgr_ctc_risk_grad: the longest hypothesis of (hyp (N, K, Lh), hyp_len (N, K)) after expansion through the lexicon
+    offsets (None: labels), within the kernel's [1, RESCORE_MAX_LABELS] - a longer one is then "not scored", as in ctc_scores."""
+    n = np.clip(hyp_len, 0, hyp.shape[2])
+    if lex_off is None:
+        longest = int(n.max()) if n.size else 0
+    else:
+        G = len(lex_off) - 1
+        inside = (np.arange(hyp.shape[2])[None, None, :] < n[:, :, None]) & (hyp >= 0) & (hyp < G)
+        words = np.diff(lex_off)[np.clip(hyp, 0, G - 1)]
+        longest = int(np.where(inside, words, 0).sum(axis=2).max()) if n.size else 0
+    return max(1, min(RESCORE_MAX_LABELS, longest))
+
+
+def expected_risk(pred_out, paths_or_arrays, refs=None, risks=None, costs=(1, 1, 1), ignore=(), risk_scale=1.0, post_scale=1.0,
+                  lexicon=None, input_length=None, skip=2, eps=1e-8, grad=True, dev=None):
+    """The expected risk of N-best lists under the network's own CTC posterior over them, and its gradient w.r.t. the Dense logits
+    (mgr_ctc_risk_grad) - the loss of sequence-level minimum-risk training: per sample, over the live hypotheses (present,
+    scored, feasible), w = softmax(post_scale * logp), risk = sum_k w_k * risks_k * risk_scale, with logp what ctc_scores returns.
+    pred_out (N, T, C); paths_or_arrays / lexicon as ctc_scores takes them (at most 32 hypotheses per sample).  Exactly one of
+    refs - whatever pack_labels takes, one reference per sample: the risks are the edit distances (costs, ignore as edit_distances) of
+    hypothesis k of sample b to reference b, formed on the device (an absent slot counts as the empty hypothesis; with a lexicon the
+    references are phrase ids, as the hypotheses) - and risks - an integer array (N, K).
+    Returns (risk (N,) float32, weights (N, K) float32, logp (N, K) float64, risks (N, K) int32[, dlogits (N, T, C) float32 - the
+    gradient of sum_b risk_b; zero on the skipped frames, behind the input length, and where fewer than two hypotheses are live])."""
+    if (refs is None) == (risks is None):
+        raise ValueError("exactly one of refs and risks")
+    if not float(post_scale) > 0.0 or not np.isfinite(post_scale):
+        raise ValueError("post_scale = %r: a positive number" % (post_scale,))
+    P = _posteriors(pred_out)
+    N, T, Cn = P.shape
+    arrays = isinstance(paths_or_arrays, tuple) and len(paths_or_arrays) == 2 and np.ndim(paths_or_arrays[0]) == 3
+    hyp, hyp_len = paths_or_arrays if arrays else pack_nbest(paths_or_arrays)
+    hyp, hyp_len = np.ascontiguousarray(hyp, np.int32), np.ascontiguousarray(hyp_len, np.int32)
+    if hyp.shape[0] != N or hyp_len.shape != hyp.shape[:2]:
+        raise ValueError("hypotheses %s / lengths %s for %d samples" % (hyp.shape, hyp_len.shape, N))
+    K, Lh = hyp.shape[1], hyp.shape[2]
+    if not 1 <= K <= RISK_MAX_SLOTS:
+        raise ValueError("%d hypotheses per sample: 1 .. %d" % (K, RISK_MAX_SLOTS))
+    off, words = compile_lexicon(lexicon, Cn) if lexicon is not None else (None, None)
+    G = 0 if off is None else len(off) - 1
+    host = lambda a: None if a is None else a.ctypes.data
+    Lcap = risk_label_cap(hyp, hyp_len, off)
+    if refs is not None:
+        cs, cd, ci = check_costs(costs)
+        mask = ignore_mask(ignore)
+        rlab, _ = pack_labels(refs)
+        if rlab.shape[0] != N:
+            raise ValueError("%d references for %d samples" % (rlab.shape[0], N))
+    else:
+        r = np.asarray(risks)
+        if r.shape != (N, K) or not np.all(r == np.round(r)):
+            raise ValueError("risks %s: integers (%d, %d)" % (r.shape, N, K))
+        r = np.ascontiguousarray(r, np.int32)
+    dev = dev or default_device()
+    held = []
+
+    def keep(a):
+        held.append(a)
+        return a
+    try:
+        dP = keep(dev.array(P))
+        dil = keep(dev.array(np.full(N, T - skip, np.int32) if input_length is None else np.asarray(input_length).reshape(N).astype(np.int32)))
+        dh, dl = keep(dev.array(hyp)), keep(dev.array(hyp_len))
+        if refs is not None:
+            dref = keep(dev.array(rlab))
+            dph = keep(dev.array(np.arange(N * K, dtype=np.int32)))
+            dpr = keep(dev.array(np.repeat(np.arange(N, dtype=np.int32), K)))
+            drisk, dcnt, dlen = keep(dev.empty((N, K), np.int32)), keep(dev.empty((N * K, 4), np.int32)), keep(dev.empty((N * K, 2), np.int32))
+            dev.call("mgr_edit_distance", dh, dl, N * K, Lh, dref, None, N, rlab.shape[1], dph, dpr, N * K, cs, cd, ci, mask, drisk, dcnt,
+                     dlen, None, None, None, 0)
+        else:
+            drisk = keep(dev.array(r))
+        dlogp, dw, dr = keep(dev.empty((N, K), np.float64)), keep(dev.empty((N, K), np.float32)), keep(dev.empty((N,), np.float32))
+        dg = keep(dev.empty((N, T, Cn), np.float32)) if grad else None
+        ws = keep(dev.bytes(dev.lib.mgr_ctc_risk_ws_bytes(N, T, Cn, K, Lcap, G, host(off))))
+        dev.call("mgr_ctc_risk_grad", dP, dil, N, T, Cn, skip, Cn - 1, C.c_float(eps), host(off), host(words), G, dh, dl, K, Lh, Lcap, drisk,
+                 C.c_float(risk_scale), C.c_float(post_scale), C.c_float(1.0), 0, dlogp, dw, dr, dg, ws, ws.nbytes)
+        res = (dr.download(), dw.download(), dlogp.download(), drisk.download())
+        return res + ((dg.download(),) if grad else ())
+    finally:
+        for a in held:
+            a.free()
+
+
+def expected_risk_map(pred_out, paths_or_arrays, refs, map_gest, costs=HTK_COSTS, **kwargs):
+    """What the networks' expected_risk share: expected_risk against reference label ids with the distance decode_score_map scores by -
+    every id whose name is "sil" dropped from both sides, the alignment costs HResults' by default (kwargs: expected_risk's)."""
+    sil = [k for k, v in map_gest.items() if v == "sil" and k >= 0]
+    return expected_risk(pred_out, paths_or_arrays, refs=refs, costs=costs, ignore=sil, **kwargs)
+
+
 def decode_score_map(hyp_ids, ref_ids, map_gest, costs=HTK_COSTS, confusion=True, dev=None):
     """What the networks' decode_score share: score_sequences of label-id sequences (what greedy_decode / the beam decoders return,
     blank runs included) over a module's class map - every id whose name is "sil" is dropped from both sides, the confusion matrix

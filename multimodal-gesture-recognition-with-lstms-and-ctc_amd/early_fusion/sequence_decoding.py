@@ -2,7 +2,7 @@
 0.97 confidence threshold, the list.remove quirk, collapse, MLF."""
 import numpy as np
 
-from ..decoding import HTK_COSTS, decode_beam_mlf, decode_score_map, greedy_decode, greedy_segments, write_mlf
+from ..decoding import HTK_COSTS, decode_beam_mlf, decode_score_map, expected_risk_map, greedy_decode, greedy_segments, write_mlf
 from ..multimodal_fusion.sequence_decoding import ignore_list, map_gest
 
 THRESHOLD = 0.97
@@ -40,3 +40,10 @@ def decode_score(hyp_ids, ref_ids, costs=HTK_COSTS, confusion=True):
     """HResults-style counts (H, S, D, I, corr, acc, confusion matrix) of decoded label ids against reference label ids on the device,
     "sil" dropped from both (decoding.decode_score_map with this module's class map)."""
     return decode_score_map(hyp_ids, ref_ids, map_gest, costs=costs, confusion=confusion)
+
+
+def expected_risk(pred_out, paths_or_arrays, ref_ids, costs=HTK_COSTS, **kwargs):
+    """The expected edit distance of N-best lists to the reference label ids under the network's own posterior over them, and its
+    gradient w.r.t. the Dense logits - the loss of minimum-risk fine-tuning (decoding.expected_risk_map with this module's class map:
+    "sil" dropped from both sides, HResults' costs)."""
+    return expected_risk_map(pred_out, paths_or_arrays, ref_ids, map_gest, costs=costs, **kwargs)

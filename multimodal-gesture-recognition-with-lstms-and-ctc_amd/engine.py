@@ -45,6 +45,14 @@ class _Arena:
     def pinned(self, shape, dtype=np.float32):
         return self.dev.pinned(shape, dtype)   # (tiny; released with the Device)
 
+    def release(self, arrays):
+        """Free some of this arena's arrays before the rest."""
+        dead = set(id(a) for a in arrays)
+        for a in arrays:
+            a.free()
+        self.arrays = [a for a in self.arrays if id(a) not in dead]
+        self.dev._arrays = [a for a in self.dev._arrays if id(a) not in dead]
+
     def free_all(self):
         dead = set(id(a) for a in self.arrays)
         for a in self.arrays:
@@ -198,6 +206,7 @@ class Engine:
                 self.dev.call("mgr_stream_set_priority", self.ES, -1)
         self._adam_calls = 0  # optimizer steps enqueued; `iterations` (Keras) = those the update gate did not skip
         self.rng_step = 0     # advances per forward pass that draws randomness
+        self._risk = None     # set_risk: the minimum-risk training mode's settings and buffers
         self._build()
 
     # ------------------------------------------------------------------------------------------ build
@@ -1388,6 +1397,10 @@ class Engine:
         dev = self.dev
         dev.event_sync(self.EV_LOSS)
         v = float(self.loss_host[0])
+        self.last_risk = self.last_ctc_loss = None
+        if self._loss_parts is not None:      # a minimum-risk step: [0] the mean CTC loss (0 where it was not computed), [1] the mean risk
+            self.last_ctc_loss, self.last_risk = v, float(self.loss_host[1])
+            v = self.last_risk + self._loss_parts * self.last_ctc_loss
         step = self._step_id - 1
         self._synced_step = step
         self._check_scans(step=step, snapshot=self.status_host)   # raises if a persistent scan gave up: results would be garbage
@@ -1602,6 +1615,93 @@ class Engine:
             self._gate_words = (None, None)
         dev.stream(0)
 
+    RISK_DEFAULTS = dict(top_paths=8, beam_width=16, ctc_weight=0.1, costs=(1, 1, 1), post_scale=1.0, max_labels=None)
+    # set where a step is ENQUEUED, never by set_risk: the step enqueued last - the one whose loss read_loss reads, loss_host holds
+    # no other - was a minimum-risk step with this ctc_weight (None: a plain step)
+    _loss_parts = None
+    last_risk = last_ctc_loss = None
+
+    def set_risk(self, cfg):
+        """Minimum-risk fine-tuning: with cfg - a dict over RISK_DEFAULTS - the head of a training step is the separate
+        calls mgr_head_fwd_bwd equals, with the expected edit distance over the step's own N-best list added to the loss:
+        loss = mean risk + ctc_weight * mean CTC loss.  The N-best list is mgr_ctc_beam_search_lm's (no tables, top_paths, beam_width)
+        on the train-phase posteriors, its risks mgr_edit_distance's (costs) against the step's labels, the gradient
+        mgr_ctc_risk_grad's (post_scale; hypotheses of more than max_labels labels - default min(255, max(2 Lmax, 16)) - are not
+        scored; the risk workspace grows with it: B K T 2 (max_labels + 1) 8 bytes, 1.03 GiB at config F's default of 70).  read_loss
+        returns the combined loss and leaves the parts in last_risk / last_ctc_loss.  None: back to the one mgr_head_fwd_bwd call; the
+        mode's buffers are freed.  A cfg that is refused leaves the mode as it was.  The loss of a step
+        enqueued before the call is still read as that step's.  Everything behind the head is the same either way."""
+        if cfg is None:
+            self._release_risk()
+            return
+        if self.comm is not None:
+            raise NotImplementedError("minimum-risk training is single-GPU: data-parallel risk training is not implemented")
+        if self.inference_only:
+            raise ValueError("set_risk on an inference-only engine")
+        unknown = set(cfg) - set(self.RISK_DEFAULTS)
+        if unknown:
+            raise ValueError("unknown risk settings %s (known: %s)" % (sorted(unknown), sorted(self.RISK_DEFAULTS)))
+        cfg = dict(self.RISK_DEFAULTS, **cfg)
+        sp, lib, B, T = self.spec, self.lib, self.B, self.T
+        Cn, skip = sp.num_classes, int(sp.ctc["skip"])
+        K, W = int(cfg["top_paths"]), int(cfg["beam_width"])
+        if not 1 <= K <= 32 or not K <= W <= 32:
+            raise ValueError("top_paths = %d / beam_width = %d: 1 <= top_paths <= beam_width <= 32" % (K, W))
+        cs, cd, ci = (int(v) for v in cfg["costs"])
+        if min(cs, cd, ci) < 1 or max(cs, cd, ci) > 16384:
+            raise ValueError("costs %r: three integers in [1, 16384]" % (cfg["costs"],))
+        if not float(cfg["post_scale"]) > 0.0 or not float(cfg["ctc_weight"]) >= 0.0:
+            raise ValueError("post_scale > 0 and ctc_weight >= 0, got %r / %r" % (cfg["post_scale"], cfg["ctc_weight"]))
+        Lcap = min(255, max(2 * self.Lmax, 16)) if cfg["max_labels"] is None else int(cfg["max_labels"])
+        if not 1 <= Lcap <= 255:
+            raise ValueError("max_labels = %d: 1 .. 255" % Lcap)
+        cfg.update(top_paths=K, beam_width=W, costs=(cs, cd, ci), max_labels=Lcap)
+        self._release_risk()    # (the cfg is good: only now does the mode set before go)
+        dev = self.mem          # (the engine's arena: freed with it, or at set_risk(None))
+        r = dict(cfg=cfg,
+                 out=dev.empty((B, K, T - skip), np.int32), out_len=dev.empty((B, K), np.int32), score=dev.empty((B, K), np.float64),
+                 lctc=dev.empty((B, K), np.float64), ext=dev.zeros((Cn + 1, Cn), np.float64),
+                 ws_beam=dev.bytes(lib.mgr_ctc_beam_lm_ws_bytes(B, T, Cn, W, K)),
+                 pair_h=dev.empty((B * K,), np.int32).upload(np.arange(B * K)), pair_r=dev.empty((B * K,), np.int32).upload(np.repeat(np.arange(B), K)),
+                 dist=dev.empty((B, K), np.int32), counts=dev.empty((B * K, 4), np.int32), lens=dev.empty((B * K, 2), np.int32),
+                 logp=dev.empty((B, K), np.float64), weight=dev.empty((B, K), np.float32), exp_risk=dev.empty((B,), np.float32),
+                 ws_risk=dev.bytes(lib.mgr_ctc_risk_ws_bytes(B, T, Cn, K, Lcap, 0, None)))
+        r["bufs"] = [v for v in r.values() if isinstance(v, DeviceArray)]
+        self._risk = r
+
+    def _release_risk(self):
+        if self._risk is not None:
+            self.dev.sync()     # (a step that uses the buffers may be in flight)
+            self.mem.release(self._risk["bufs"])
+            self._risk = None
+
+    def _enqueue_risk_head(self, feat, ldf, hm, p_head, hseed, dA, ldda):
+        """The head of a minimum-risk step on the current stream (set_risk): Dropout / Dense / softmax, the CTC gradient scaled
+        ctc_weight / B, the N-best list, its edit distances, the risk gradient ADDED with 1 / B, the two means, Dense backward."""
+        sp, dev, B, T, r = self.spec, self.dev, self.B, self.T, self._risk
+        cfg = r["cfg"]
+        Cn, D, skip, eps = sp.num_classes, sp.head_width, int(sp.ctc["skip"]), float(sp.ctc["eps"])
+        K, cw = cfg["top_paths"], float(cfg["ctc_weight"])
+        dev.call("mgr_dense_softmax_fwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self._wview("dense/W"), self._wview("dense/b"), self.P,
+                 B, T, D, Cn)
+        if cw != 0.0:
+            dev.call("mgr_ctc_loss_grad", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1, eps, cw / B,
+                     self.loss_b, self.dLogits, self.ws_ctc, self.ws_ctc.nbytes)
+        dev.call("mgr_ctc_beam_search_lm", self.P, self.ilen_d, B, T, Cn, skip, Cn - 1, cfg["beam_width"], eps, r["ext"], None, K, r["out"],
+                 r["out_len"], r["score"], r["lctc"], r["ws_beam"], r["ws_beam"].nbytes)
+        dev.call("mgr_edit_distance", r["out"], r["out_len"], B * K, T - skip, self.labels_d, self.llen_d, B, self.Lmax, r["pair_h"],
+                 r["pair_r"], B * K, *cfg["costs"], 0, r["dist"], r["counts"], r["lens"], None, None, None, 0)
+        dev.call("mgr_ctc_risk_grad", self.P, self.ilen_d, B, T, Cn, skip, Cn - 1, eps, None, None, 0, r["out"], r["out_len"], K, T - skip,
+                 cfg["max_labels"], r["dist"], 1.0, float(cfg["post_scale"]), 1.0 / B, 1 if cw != 0.0 else 0, r["logp"], r["weight"],
+                 r["exp_risk"], self.dLogits, r["ws_risk"], r["ws_risk"].nbytes)
+        if cw != 0.0:
+            dev.call("mgr_mean", self.loss_b, B, self.loss_mean)
+        else:
+            self.loss_mean.zero()        # (the CTC loss was not computed: it is reported as 0)
+        dev.call("mgr_mean", r["exp_risk"], B, self.loss_mean.view(1, (1,)))
+        dev.call("mgr_dense_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self.dLogits, self._wview("dense/W"), self._gview("dense/W"),
+                 self._gview("dense/b"), dA, ldda, B, T, D, Cn, self.ws_dense, self.ws_dense.nbytes)
+
     def _enqueue_trainable_part(self, cur, rand, beside_scans, defer, late_ok, own_inputs, apply_update):
         """Steps 2 and 3 of a training step on stream 0 - fusion layer, head, CTC, the loss read-back point, the backward pass up to
         what `defer` / `late_ok` hold back - and the closure `finish(gate=None)` that enqueues the rest (held-back BPTT, dW / dU / db
@@ -1630,10 +1730,14 @@ class Engine:
         #  which is on the step's critical path)
         ctc_lds = {_capi.TUNE_CTC_CHAIN_LDS_KIB: 96, _capi.TUNE_CTC_FRAME_LDS_KIB: 64}
         with self._tuned(self._gate_words[0] is not None or self._gate_words[1] is not None, ctc_lds, keep_set=True):
-            dev.call("mgr_head_fwd_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self._wview("dense/W"), self._wview("dense/b"),
-                     self.labels_d, self.ilen_d, self.llen_d, B, T, D, Cn, self.Lmax, int(sp.ctc["skip"]), Cn - 1, float(sp.ctc["eps"]),
-                     1.0 / B, self.P, self.loss_b, self.loss_mean, self.dLogits, self._gview("dense/W"), self._gview("dense/b"),
-                     dA, ldda, self.ws_head, self.ws_head.nbytes)
+            if self._risk is not None:
+                self._enqueue_risk_head(feat, ldf, hm, p_head, hseed, dA, ldda)
+            else:
+                dev.call("mgr_head_fwd_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self._wview("dense/W"), self._wview("dense/b"),
+                         self.labels_d, self.ilen_d, self.llen_d, B, T, D, Cn, self.Lmax, int(sp.ctc["skip"]), Cn - 1, float(sp.ctc["eps"]),
+                         1.0 / B, self.P, self.loss_b, self.loss_mean, self.dLogits, self._gview("dense/W"), self._gview("dense/b"),
+                         dA, ldda, self.ws_head, self.ws_head.nbytes)
+        self._loss_parts = None if self._risk is None else float(self._risk["cfg"]["ctc_weight"])
         if self.comm is not None:
             dev.call("mgr_mean", self.loss_b, B, self.loss_slot)   # travels with the gradient all-reduce (apply_gradients)
         dev.record(self.EV_LAB[self._lab_slot])

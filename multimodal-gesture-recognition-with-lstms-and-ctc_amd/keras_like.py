@@ -212,6 +212,8 @@ class Model:
         self.seed = seed
         self._engine = None
         self._weights = None      # host copy (Keras layouts) until an engine exists
+        self._risk = None         # set_risk: the minimum-risk training mode's settings (carried over when the engine is rebuilt)
+        self.last_logs = {}       # train_on_batch: the scalars of its step ("loss"; with set_risk also "risk" and "ctc_loss")
         self._predict_view = False
         self._shared = None
         self.optimizer = None
@@ -380,6 +382,19 @@ class Model:
             self.spec.optimizer.update(optimizer.config())
         if self._engine is not None:
             self._engine.spec = self.spec
+        if "risk" in kwargs:
+            self.set_risk(kwargs["risk"])
+
+    def set_risk(self, cfg):
+        """Minimum-risk fine-tuning of a CTC-trained network (Engine.set_risk): cfg = dict(top_paths=8, beam_width=16,
+        ctc_weight=0.1, costs=(1, 1, 1), post_scale=1.0, max_labels=None) or a part of it - the training loss becomes the expected edit
+        distance over the step's own N-best list + ctc_weight x the CTC loss; train_on_batch leaves the parts in last_logs ("loss",
+        "risk", "ctc_loss"), fit_generator logs their epoch means.  None: plain CTC training again.  Single GPU only."""
+        if cfg is not None and self.comm is not None:
+            raise NotImplementedError("minimum-risk training is single-GPU: data-parallel risk training is not implemented")
+        self._risk = None if cfg is None else dict(cfg)
+        if self._engine is not None and not self._engine.inference_only:
+            self._engine.set_risk(self._risk)
 
     def distribute(self, comm, world):
         """Attach a data-parallel communicator (mgr_amd.parallel.RcclComm / HostComm) before the first batch.  The engine is
@@ -387,6 +402,8 @@ class Model:
         dropout / noise from a per-rank seed; every rank feeds ITS shard of the global batch (parallel.shard_batch)."""
         if self._engine is not None:
             raise RuntimeError("distribute() must be called before the first batch")
+        if self._risk is not None:
+            raise NotImplementedError("minimum-risk training is single-GPU: data-parallel risk training is not implemented")
         self.comm, self.world = comm, int(world)
         if getattr(comm, "dev", None) is not None:
             self.device = comm.dev
@@ -406,6 +423,8 @@ class Model:
         self._engine = Engine(self.spec, B, T, max(Lmax, 1), device=self.device, seed=self.seed + 7919 * rank, comm=self.comm,
                               world=self.world, inference_only=inference_only)
         self._engine.set_weights(w)
+        if self._risk is not None and not inference_only:
+            self._engine.set_risk(self._risk)
         if opt_state is not None and not inference_only:
             self._engine.m.upload(opt_state[0])
             self._engine.v.upload(opt_state[1])
@@ -444,7 +463,11 @@ class Model:
         nxt = self._cached_split(next_x) if next_x is not None else None
         nxt2 = self._cached_split(after_next_x) if (after_next_x is not None and nxt is not None) else None
         if not _lagged:
-            return e.train_step(ins, labels, x["input_length"], x["label_length"], rand=rand, next_inputs=nxt, after_next_inputs=nxt2)
+            loss = e.train_step(ins, labels, x["input_length"], x["label_length"], rand=rand, next_inputs=nxt, after_next_inputs=nxt2)
+            self.last_logs = {"loss": loss}
+            if e.last_risk is not None:      # (a minimum-risk step: set_risk)
+                self.last_logs.update(risk=e.last_risk, ctc_loss=e.last_ctc_loss)
+            return loss
         # fit_generator, world > 1: the global loss arrives with the gradient all-reduce at the END of the step; waiting for it
         # here would leave the device idle while the host assembles the next batch - pace on the local loss, collect the global
         # one a step later (Engine.read_global_loss)
@@ -509,7 +532,7 @@ class Model:
             for cb in callbacks:
                 if hasattr(cb, "on_epoch_begin"):
                     cb.on_epoch_begin(epoch, {})
-            losses = []
+            losses, parts = [], []
             lagged = self.world > 1 and self.comm is not None
             owed = None       # (data parallel) id of the step whose global loss has not been collected yet
             skipped0 = self._engine.updates_skipped if self._engine is not None else 0
@@ -527,9 +550,13 @@ class Model:
                     owed = r
                 else:
                     losses.append(r)
+                    if "risk" in self.last_logs:
+                        parts.append((self.last_logs["risk"], self.last_logs["ctc_loss"]))
             if owed is not None:
                 losses.append(self._engine.read_global_loss(owed))
             logs = {"loss": float(np.mean(losses)) if losses else float("nan")}
+            if parts:       # (minimum-risk training: set_risk)
+                logs.update(risk=float(np.mean([p[0] for p in parts])), ctc_loss=float(np.mean([p[1] for p in parts])))
             if self._engine is not None and self._engine.updates_skipped > skipped0:
                 import warnings
                 warnings.warn("%d optimizer update(s) of this epoch were skipped on the device (a scan of the step reported a non-finite "

@@ -1,7 +1,7 @@
 """Decode for the fusion network (reference multimodal_fusion/sequence_decoding.py:21-69)."""
 import numpy as np
 
-from ..decoding import HTK_COSTS, decode_beam_mlf, decode_score_map, greedy_decode, greedy_decode_argmax, greedy_segments, write_mlf
+from ..decoding import HTK_COSTS, decode_beam_mlf, decode_score_map, expected_risk_map, greedy_decode, greedy_decode_argmax, greedy_segments, write_mlf
 
 # gesture code -> class name; the blank (21) is emitted as "sil" (reference :26-29)
 map_gest = {0: "oov", 1: "VA", 2: "VQ", 3: "PF", 4: "FU", 5: "CP", 6: "CV", 7: "DC", 8: "SP", 9: "CN", 10: "FN",
@@ -56,3 +56,10 @@ def decode_score(hyp_ids, ref_ids, costs=HTK_COSTS, confusion=True):
     """HResults-style counts (H, S, D, I, corr, acc, confusion matrix) of decoded label ids against reference label ids on the device,
     "sil" dropped from both (decoding.decode_score_map with this module's class map)."""
     return decode_score_map(hyp_ids, ref_ids, map_gest, costs=costs, confusion=confusion)
+
+
+def expected_risk(pred_out, paths_or_arrays, ref_ids, costs=HTK_COSTS, **kwargs):
+    """The expected edit distance of N-best lists to the reference label ids under the network's own posterior over them, and its
+    gradient w.r.t. the Dense logits - the loss of minimum-risk fine-tuning (decoding.expected_risk_map with this module's class map:
+    "sil" dropped from both sides, HResults' costs)."""
+    return expected_risk_map(pred_out, paths_or_arrays, ref_ids, map_gest, costs=costs, **kwargs)

@@ -3,7 +3,7 @@ the reference's confidence threshold is commented out, so none applies - over th
 MLF writer with the ten-file ignore list."""
 import numpy as np
 
-from ..decoding import HTK_COSTS, confidence_filter_collapse, decode_beam_mlf, decode_score_map, greedy_segments, write_mlf
+from ..decoding import HTK_COSTS, confidence_filter_collapse, decode_beam_mlf, decode_score_map, expected_risk_map, greedy_segments, write_mlf
 from ..keras_like import Model
 from ..multimodal_fusion.sequence_decoding import ignore_list, map_gest  # noqa: F401  (the same 22 names and ignore list)
 from .cnn_lstm import load_model as _load_model
@@ -55,3 +55,10 @@ def decode_score(hyp_ids, ref_ids, costs=HTK_COSTS, confusion=True):
     """HResults-style counts (H, S, D, I, corr, acc, confusion matrix) of decoded label ids against reference label ids on the device,
     "sil" dropped from both (decoding.decode_score_map with this module's class map)."""
     return decode_score_map(hyp_ids, ref_ids, map_gest, costs=costs, confusion=confusion)
+
+
+def expected_risk(pred_out, paths_or_arrays, ref_ids, costs=HTK_COSTS, **kwargs):
+    """The expected edit distance of N-best lists to the reference label ids under the network's own posterior over them, and its
+    gradient w.r.t. the Dense logits - the loss of minimum-risk fine-tuning (decoding.expected_risk_map with this module's class map:
+    "sil" dropped from both sides, HResults' costs)."""
+    return expected_risk_map(pred_out, paths_or_arrays, ref_ids, map_gest, costs=costs, **kwargs)
