@@ -668,6 +668,31 @@ int mgr_ctc_risk_grad(mgr_ctx* ctx, const float* P, const int32_t* input_len, in
                       int Lh, int Lcap, const int32_t* risk, float risk_scale, float post_scale, float gscale, int accumulate,
                       double* logp, float* weight, float* exp_risk, float* dLogits, void* ws, size_t ws_bytes);
 
+/* ---- K16: CTC hypotheses by sampling alignments: a second filler for "a list of hypotheses per sample" beside the beam
+ * search - K frame paths per sample drawn from the network's own per-frame distribution, collapsed, equal labellings merged and
+ * counted.  One independent draw per (sample, draw, frame): nothing is serial over the frames.  P [B,T,C] float32 and input_len [B]
+ * (required) as every decode kernel takes them: Tp = input_len[b] clipped into [0, T - skip].
+ * The draw of sample b, draw k, frame t in [skip, skip + Tp) - every operation a single IEEE float32 operation, in this order:
+ *     w_c   = P[b,t,c] + eps
+ *     cum_c = cum_{c-1} + w_c   (cum_{-1} = 0; class order), S = cum_{C-1}
+ *     u     = (float)(r >> 8) * 2^-24,   r = the library's counter-based 32-bit generator (mgr_rand_u32 in csrc/common.h) at
+ *             seed and index (uint64_t)(b * K + k) * T + t
+ *     thr   = u * S
+ *     class = the first c with cum_c > thr; `blank` if there is none (S = 0)
+ * That is the distribution y = (P + eps) / sum_c (P + eps) of mgr_ctc_loss_grad, mgr_ctc_rescore and mgr_ctc_risk_grad; a class of
+ * weight 0 is never drawn; NaN input is unspecified.
+ * The labelling of a draw is the CTC collapse of its frame path: a frame equal to its predecessor is dropped, then the blanks are; its
+ * length lies in [0, Tp].  The UNIQUE labellings of a sample are written in order of first occurrence over k = 0 .. K - 1 (labellings
+ * are compared exactly, label by label): out [B,K,T-skip] int32 padded -1 (the beam kernels' layout), out_len [B,K] the labelling's
+ * length, count [B,K] the number of draws that collapsed to it, n_unique [B].  Slots j >= n_unique[b] are absent slots as K12, K14
+ * and K15 understand them: out_len -1, count 0, a row of -1.  sum_j count[b,j] = K always; Tp = 0 gives one labelling, the empty one,
+ * with count K.  path [B,K,T-skip] int32 or NULL: the class drawn at every frame in DRAW order (row k = draw k), -1 from Tp on.
+ * 2 <= C <= 64, 1 <= K <= MGR_SAMPLE_MAX_DRAWS, B <= 65535.  No workspace: the unique rows are compacted in out itself.  No atomics:
+ * deterministic - row b depends on its own posteriors, seed, b, K and T alone. */
+#define MGR_SAMPLE_MAX_DRAWS 32
+int mgr_ctc_sample_paths(mgr_ctx* ctx, const float* P, const int32_t* input_len, int B, int T, int C, int skip, int blank, float eps,
+                         uint64_t seed, int K, int32_t* out, int32_t* out_len, int32_t* count, int32_t* n_unique, int32_t* path);
+
 /* ---- K12: scoring decodes: the weighted edit distance of n_pairs pairs of label sequences, with the substitution /
  * deletion / insertion split of HTK's HResults, in one launch.  All pointers are device memory.
  * hyp [n_hyp,Lh], ref [n_ref,Lr] int32, rows padded with -1; hyp_len [n_hyp] / ref_len [n_ref] int32 or NULL: NULL = the whole row,

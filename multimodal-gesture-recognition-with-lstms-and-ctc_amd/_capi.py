@@ -135,6 +135,7 @@ SIGNATURES = {
     "mgr_ctc_risk_ws_bytes": (sz, [i32, i32, i32, i32, i32, i32, vp]),
     "mgr_ctc_risk_grad": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, i32, i32, i32, vp, C.c_float, C.c_float,
                                 C.c_float, i32, vp, vp, vp, vp, vp, sz]),
+    "mgr_ctc_sample_paths": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, u64, i32, vp, vp, vp, vp, vp]),
     "mgr_edit_distance_ws_bytes": (sz, [i32, i32, i32, i32]),
     "mgr_edit_distance": (i32, [vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, u64, vp, vp, vp, vp, vp, vp, sz]),
     "mgr_conv_pool_fwd": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),

@@ -1,7 +1,7 @@
 """Decode for the audio network (reference audio_network/sequence_decoding.py:19-69): word-level classes, thr .75."""
 import numpy as np
 
-from ..decoding import (HTK_COSTS, decode_beam_mlf, decode_lexicon_mlf, decode_score_map, expected_risk_map, greedy_decode,
+from ..decoding import (HTK_COSTS, decode_beam_mlf, decode_lexicon_mlf, decode_samples_map, decode_score_map, expected_risk_map, greedy_decode,
                         greedy_decode_argmax, greedy_segments, write_mlf)
 from .data_generator import class_2_words
 
@@ -66,6 +66,14 @@ def decode_lexicon(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, 
     lists, segment lists of (gesture id, first_frame, last_frame, confidence))."""
     return decode_lexicon_mlf(pred_out, f_list, GESTURE_LEXICON, gesture_names, ignore_list, "Sample%05d_audio", out_file, lm=lm,
                               lm_end=lm_end, alpha=alpha, beta=beta)
+
+
+def decode_samples(pred_out, f_list, draws=8, seed=0, **kwargs):
+    """A sampled hypothesis set per file (decoding.sample_hypotheses): pred_out (N, T, C) softmax - or the (paths, counts)
+    that Model.predict_generator(decode="sample", draws=draws, ...) drew on the device.  Returns (per file the name lists of its unique
+    sampled labellings in order of first occurrence, through the class map as decode_beam's N-best lists; per file the number of the
+    `draws` draws that gave each).  No MLF: a sampled set is no transcription (kwargs: sample_hypotheses')."""
+    return decode_samples_map(pred_out, f_list, map_gest, draws=draws, seed=seed, **kwargs)
 
 
 def decode_score(hyp_ids, ref_ids, costs=HTK_COSTS, confusion=True):

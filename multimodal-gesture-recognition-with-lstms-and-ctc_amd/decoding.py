@@ -93,6 +93,25 @@ def beam_lm_op(n_classes, skip, lm=None, lm_end=None, alpha=1.0, beta=0.0, beam_
                     hyp=(0, 1), uses_len=True)         # (a length of -1 - no hypothesis - counts as 0 in mgr_edit_distance)
 
 
+def sample_op(n_classes, skip, draws, seed, return_path=False, eps=1e-8):
+    """mgr_ctc_sample_paths (K16): `draws` frame paths per sample, collapsed, merged and counted.  launch takes one more keyword,
+    seed=: a caller that draws again for every batch (Engine.predict_stream) passes it there, the op's own seed is the default."""
+    Cn, K, seed0 = int(n_classes), int(draws), int(seed) & (2 ** 64 - 1)
+    if not 2 <= Cn <= SAMPLE_MAX_CLASSES or not 1 <= K <= SAMPLE_MAX_DRAWS:
+        raise ValueError("n_classes = %d (2 .. %d) / draws = %d (1 .. %d)" % (Cn, SAMPLE_MAX_CLASSES, K, SAMPLE_MAX_DRAWS))
+
+    def outputs(N, T, Lmax=None):
+        return (_i32(N, K, T - skip), _i32(N, K), _i32(N, K), _i32(N), _i32(N, K, T - skip) if return_path else None)
+
+    def launch(dev, P, input_len, outs, tables, ws, seed=None):
+        dev.call("mgr_ctc_sample_paths", P, input_len, P.shape[0], P.shape[1], Cn, skip, Cn - 1, C.c_float(eps),
+                 C.c_uint64(seed0 if seed is None else int(seed) & (2 ** 64 - 1)), K, *outs)
+
+    def result(out, out_len, count, n_unique, *path):
+        return samples_from_arrays(out, out_len, count) + path
+    return DecodeOp("sample", outputs, launch, result, hyp=(0, 1), uses_len=True)
+
+
 def lexicon_op(n_classes, skip, lexicon, lm=None, lm_end=None, alpha=1.0, beta=0.0, cap=256, return_path=False, eps=1e-8):
     Cn, cap = int(n_classes), int(cap)
     off, words = compile_lexicon(lexicon, Cn)        # (host arrays: the library reads and checks them at every call)
@@ -495,6 +514,42 @@ def decode_beam_mlf(pred_out, f_list, map_gest, ignore_list, name_fmt, out_file,
     if out_file is not None:
         write_mlf(out_file, ret, f_list, ignore_list, name_fmt)
     return ret, nbest
+
+
+# ---- sampled hypothesis sets (K16): frame paths drawn from the posteriors, collapsed, merged and counted ----------------
+SAMPLE_MAX_DRAWS, SAMPLE_MAX_CLASSES = 32, 64       # MGR_SAMPLE_MAX_DRAWS of include/mgr.h, and its C <= 64
+
+
+def samples_from_arrays(out, out_len, count):
+    """mgr_ctc_sample_paths' arrays ((B, K, T - skip), (B, K), (B, K)) -> (paths: per sample its unique labellings as label lists in
+    order of first occurrence, counts: per sample the number of draws that gave each)."""
+    B, K = out_len.shape
+    live = [[j for j in range(K) if out_len[b, j] >= 0] for b in range(B)]
+    return ([[[int(v) for v in out[b, j, :out_len[b, j]]] for j in live[b]] for b in range(B)],
+            [[int(count[b, j]) for j in live[b]] for b in range(B)])
+
+
+def sample_hypotheses(pred_out, draws=8, seed=0, input_length=None, skip=2, dev=None, return_path=False, eps=1e-8):
+    """A hypothesis set per sample by SAMPLING on the GPU (mgr_ctc_sample_paths): `draws` (1 .. 32) frame paths per sample
+    drawn from the per-frame distribution (P + eps) / sum (P + eps) - the loss's -, each collapsed to its labelling (blank = C - 1),
+    equal labellings merged.  A pure function of (pred_out, seed): the same call gives the same set.
+    Returns (paths, counts[, frame_paths]): paths[b] the unique labellings in order of first occurrence - what ctc_scores,
+    pool_hypotheses, nbest_attainable and expected_risk take as they take the beam search's lists -, counts[b] the number of draws that
+    gave each (they sum to `draws`; np.log(counts / draws) serves mbr_decode as scores, counts[b][j] / draws is the share of draws
+    that agree with labelling j), frame_paths (N, draws, T - skip) int32 the class drawn at every frame, in draw order, -1 past the
+    input length."""
+    P = _posteriors(pred_out)
+    return _run(sample_op(P.shape[2], skip, draws, seed, return_path, eps), P, skip, dev, input_length)
+
+
+def decode_samples_map(pred_out, f_list, map_gest, **kwargs):
+    """What the networks' decode_samples share: pred_out (N, T, C) softmax - sampled with sample_hypotheses(**kwargs) - or the (paths,
+    counts) that Model.predict_generator(decode="sample", ...) drew on the device.  Returns (per file the name lists of its unique
+    sampled labellings through the class map, as decode_beam returns its N-best lists; counts)."""
+    if len(f_list) != (len(pred_out[0]) if isinstance(pred_out, tuple) else len(pred_out)):
+        raise ValueError("%d files for %d samples" % (len(f_list), len(pred_out[0]) if isinstance(pred_out, tuple) else len(pred_out)))
+    paths, counts = pred_out[:2] if isinstance(pred_out, tuple) else sample_hypotheses(np.asarray(pred_out), **kwargs)[:2]
+    return [[[map_gest[i] for i in seq] for seq in hyps] for hyps in paths], counts
 
 
 # ---- rescoring N-best lists across modalities (K14, DESIGN 9j): CTC scores of pooled hypotheses, combined and re-ranked -----------

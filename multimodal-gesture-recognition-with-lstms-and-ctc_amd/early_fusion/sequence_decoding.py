@@ -2,7 +2,7 @@
 0.97 confidence threshold, the list.remove quirk, collapse, MLF."""
 import numpy as np
 
-from ..decoding import HTK_COSTS, decode_beam_mlf, decode_score_map, expected_risk_map, greedy_decode, greedy_segments, write_mlf
+from ..decoding import HTK_COSTS, decode_beam_mlf, decode_samples_map, decode_score_map, expected_risk_map, greedy_decode, greedy_segments, write_mlf
 from ..multimodal_fusion.sequence_decoding import ignore_list, map_gest
 
 THRESHOLD = 0.97
@@ -34,6 +34,14 @@ def decode_beam(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, bea
     map into the MLF; returns (1-best name lists, (paths, score, logp_ctc)) - with top_paths > 1 the ranked N-best lists."""
     return decode_beam_mlf(pred_out, f_list, map_gest, ignore_list, "Sample%05d", out_file, top_paths=top_paths, lm=lm, lm_end=lm_end,
                            alpha=alpha, beta=beta, beam_width=beam_width)
+
+
+def decode_samples(pred_out, f_list, draws=8, seed=0, **kwargs):
+    """A sampled hypothesis set per file (decoding.sample_hypotheses): pred_out (N, T, C) softmax - or the (paths, counts)
+    that Model.predict_generator(decode="sample", draws=draws, ...) drew on the device.  Returns (per file the name lists of its unique
+    sampled labellings in order of first occurrence, through the class map as decode_beam's N-best lists; per file the number of the
+    `draws` draws that gave each).  No MLF: a sampled set is no transcription (kwargs: sample_hypotheses')."""
+    return decode_samples_map(pred_out, f_list, map_gest, draws=draws, seed=seed, **kwargs)
 
 
 def decode_score(hyp_ids, ref_ids, costs=HTK_COSTS, confusion=True):

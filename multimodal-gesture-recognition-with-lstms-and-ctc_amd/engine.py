@@ -559,6 +559,14 @@ class Engine:
     def _seed(self, slot):
         return (self.seed * 1000003 + self.rng_step * 131 + slot) & 0xFFFFFFFFFFFFFFFF
 
+    SAMPLE_SLOT = 998     # the stream constant of the risk mode's sampled hypothesis sets (the head dropout's is 999)
+    _head_step = 0        # rng_step of the head pass enqueued last
+
+    def _sample_seed(self, base):
+        """_seed's derivation at the step counter the head pass enqueued last drew its dropout seed at, from `base` in the engine
+        seed's place (None: the engine's seed)."""
+        return ((self.seed if base is None else int(base)) * 1000003 + self._head_step * 131 + self.SAMPLE_SLOT) & 0xFFFFFFFFFFFFFFFF
+
     COPY_STREAM = 7
     EV_IN = (41, 42)     # last reader of input buffer set 0 / 1
     EV_LAB = (43, 44)    # last reader of label buffer set 0 / 1
@@ -870,6 +878,7 @@ class Engine:
         elif train and p_head > 0:
             self._head_seed = self._seed(999)
         self._head_args = (hm, p_head, self._head_seed)
+        self._head_step = self.rng_step      # (the counter this pass draws at: _sample_seed)
         if dense:
             dev.call("mgr_dense_softmax_fwd", feat, ldf, hm, p_head, C.c_uint64(self._head_seed),
                      self._wview("dense/W"), self._wview("dense/b"), self.P, B, T, D, Cn)
@@ -1016,7 +1025,7 @@ class Engine:
     EV_D1S = (57, 58)     # the depth-1 scans that read depth-1 Z set 0 / 1 are done (stream ES)
     LABELLED = ("loss", "align", "score")     # the predict_stream outputs whose batches come with labels (a training engine)
 
-    def decode_ops(self, beam_width=10, merge_repeated=True, threshold=None, top_paths=1, lexicon=None, **lm_args):
+    def decode_ops(self, beam_width=10, merge_repeated=True, threshold=None, top_paths=1, lexicon=None, draws=8, sample_seed=0, **lm_args):
         """predict_stream's decode outputs: name -> what builds decoding's description of its kernel with this engine's classes, frames
         and eps (nothing is validated before that is called).  Room for T - skip runs / phrases per sample, the most there can be: the
         count the kernel reports never exceeds what is downloaded."""
@@ -1027,10 +1036,12 @@ class Engine:
                 "beam": lambda: decoding.beam_op(Cn, skip, beam_width, merge_repeated, eps=eps),
                 "beam_lm": lambda: decoding.beam_lm_op(Cn, skip, beam_width=beam_width, top_paths=top_paths, eps=eps, **lm_args),
                 "lexicon": lambda: decoding.lexicon_op(Cn, skip, lexicon, cap=room, eps=eps, **lm_args),
+                "sample": lambda: decoding.sample_op(Cn, skip, draws, sample_seed, eps=eps),
                 "align": lambda: decoding.align_op(Cn, skip, return_path=True, eps=eps)}
 
     def predict_stream(self, batches, output="posteriors", train_phase=False, beam_width=10, merge_repeated=True, threshold=None,
-                       lm=None, lm_end=None, alpha=1.0, beta=0.0, top_paths=1, decode="greedy", ignore=None, costs=(1, 1, 1), lexicon=None):
+                       lm=None, lm_end=None, alpha=1.0, beta=0.0, top_paths=1, decode="greedy", ignore=None, costs=(1, 1, 1), lexicon=None,
+                       draws=8, sample_seed=0):
         """Batches of an inference / validation run are independent of each other: this generator keeps two of them in flight.
         Batch n + 1 is uploaded (copy stream) and runs its encoder pass (stream ES, into the other FEAT buffer) beside batch n's
         fusion layer / head / decode kernels (stream 0) and beside the download of batch n - 1's result (its own stream, into
@@ -1068,11 +1079,16 @@ class Engine:
                         (inputs, hyp (B, K, Lh) int32 padded -1, hyp_len (B, K) int32, -1 = no hypothesis) as decoding.pack_nbest lays
                         them out - with `lexicon` the entries are phrase ids -; K and Lh are those of the first batch.  The hypothesis
                         arrays go up through pinned double buffers on the output stream; an inference-only engine will do
+          "sample"      (paths: per sample the list of its unique sampled labellings in order of first occurrence, counts: per sample
+                        the number of draws that gave each): mgr_ctc_sample_paths on the device - `draws` (1 .. 32) alignments per
+                        sample drawn from the posteriors, collapsed and merged (decoding.sample_hypotheses of the
+                        posteriors).  The i-th batch of the stream draws with seed (sample_seed + i) mod 2^64; an inference-only
+                        engine will do
         Results are bit-identical to the one-batch-at-a-time calls (predict / loss_on_batch): same kernels, same order per batch."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         Cn, skip, eps = sp.num_classes, int(sp.ctc["skip"]), float(sp.ctc["eps"])
         # ("score" decodes one path; top_paths is read for "beam_lm" alone)
-        ops = self.decode_ops(beam_width, merge_repeated, threshold, top_paths if output == "beam_lm" else 1, lexicon,
+        ops = self.decode_ops(beam_width, merge_repeated, threshold, top_paths if output == "beam_lm" else 1, lexicon, draws, sample_seed,
                                lm=lm, lm_end=lm_end, alpha=alpha, beta=beta)
         if output not in ("posteriors", "loss", "score", "rescore") + tuple(ops):
             raise ValueError("unknown output %r" % (output,))
@@ -1304,6 +1320,8 @@ class Engine:
                         dev.h2d_async(d, pin)
                     host_labels[i] = (None, None)
                     op.launch(dev, pring[o], dil, dring[0], tables, ws, *dhyp)
+                elif output == "sample":
+                    op.launch(dev, pring[o], dil, dring[0], tables, ws, seed=int(sample_seed) + i)
                 elif op is not None and output != "align":
                     op.launch(dev, pring[o], dil, dring[0], tables, ws)
                 if output == "score":
@@ -1615,7 +1633,10 @@ class Engine:
             self._gate_words = (None, None)
         dev.stream(0)
 
-    RISK_DEFAULTS = dict(top_paths=8, beam_width=16, ctc_weight=0.1, costs=(1, 1, 1), post_scale=1.0, max_labels=None)
+    RISK_DEFAULTS = dict(top_paths=8, beam_width=16, ctc_weight=0.1, costs=(1, 1, 1), post_scale=1.0, max_labels=None, source="beam",
+                         sample_seed=None)
+    # the kernel seed of the sampled hypothesis set of the step enqueued last (source="sample"; None: no such step yet)
+    last_sample_seed = None
     # set where a step is ENQUEUED, never by set_risk: the step enqueued last - the one whose loss read_loss reads, loss_host holds
     # no other - was a minimum-risk step with this ctc_weight (None: a plain step)
     _loss_parts = None
@@ -1629,7 +1650,11 @@ class Engine:
         mgr_ctc_risk_grad's (post_scale; hypotheses of more than max_labels labels - default min(255, max(2 Lmax, 16)) - are not
         scored; the risk workspace grows with it: B K T 2 (max_labels + 1) 8 bytes, 1.03 GiB at config F's default of 70).  read_loss
         returns the combined loss and leaves the parts in last_risk / last_ctc_loss.  None: back to the one mgr_head_fwd_bwd call; the
-        mode's buffers are freed.  A cfg that is refused leaves the mode as it was.  The loss of a step
+        mode's buffers are freed.  source="sample" (DESIGN 9o): the hypothesis set is not searched for but SAMPLED - mgr_ctc_sample_paths
+        in the search's place, top_paths (1 .. 32) draws per sample, beam_width not read, no search workspace or tables held; the unique
+        sampled labellings are the slots, weighted as the N-best list's are (the counts take no part).  The step's kernel seed comes from
+        sample_seed (None: the engine's seed) and the step counter as the head dropout's does, with a stream constant of its own, and is
+        left in last_sample_seed.  A cfg that is refused leaves the mode as it was.  The loss of a step
         enqueued before the call is still read as that step's.  Everything behind the head is the same either way."""
         if cfg is None:
             self._release_risk()
@@ -1645,7 +1670,15 @@ class Engine:
         sp, lib, B, T = self.spec, self.lib, self.B, self.T
         Cn, skip = sp.num_classes, int(sp.ctc["skip"])
         K, W = int(cfg["top_paths"]), int(cfg["beam_width"])
-        if not 1 <= K <= 32 or not K <= W <= 32:
+        sampled = cfg["source"] == "sample"
+        if cfg["source"] not in ("beam", "sample"):
+            raise ValueError("source = %r: 'beam' or 'sample'" % (cfg["source"],))
+        if sampled:
+            if not 1 <= K <= 32 or not 2 <= Cn <= 64:
+                raise ValueError("top_paths = %d draws (1 .. 32) of %d classes (2 .. 64)" % (K, Cn))
+            if cfg["sample_seed"] is not None:
+                cfg["sample_seed"] = int(cfg["sample_seed"])
+        elif not 1 <= K <= 32 or not K <= W <= 32:
             raise ValueError("top_paths = %d / beam_width = %d: 1 <= top_paths <= beam_width <= 32" % (K, W))
         cs, cd, ci = (int(v) for v in cfg["costs"])
         if min(cs, cd, ci) < 1 or max(cs, cd, ci) > 16384:
@@ -1658,11 +1691,13 @@ class Engine:
         cfg.update(top_paths=K, beam_width=W, costs=(cs, cd, ci), max_labels=Lcap)
         self._release_risk()    # (the cfg is good: only now does the mode set before go)
         dev = self.mem          # (the engine's arena: freed with it, or at set_risk(None))
-        r = dict(cfg=cfg,
-                 out=dev.empty((B, K, T - skip), np.int32), out_len=dev.empty((B, K), np.int32), score=dev.empty((B, K), np.float64),
-                 lctc=dev.empty((B, K), np.float64), ext=dev.zeros((Cn + 1, Cn), np.float64),
-                 ws_beam=dev.bytes(lib.mgr_ctc_beam_lm_ws_bytes(B, T, Cn, W, K)),
-                 pair_h=dev.empty((B * K,), np.int32).upload(np.arange(B * K)), pair_r=dev.empty((B * K,), np.int32).upload(np.repeat(np.arange(B), K)),
+        r = dict(cfg=cfg, out=dev.empty((B, K, T - skip), np.int32), out_len=dev.empty((B, K), np.int32))
+        if sampled:     # (the sampler needs no workspace: the counts and the number of unique labellings are all it adds)
+            r.update(count=dev.empty((B, K), np.int32), n_unique=dev.empty((B,), np.int32))
+        else:
+            r.update(score=dev.empty((B, K), np.float64), lctc=dev.empty((B, K), np.float64), ext=dev.zeros((Cn + 1, Cn), np.float64),
+                     ws_beam=dev.bytes(lib.mgr_ctc_beam_lm_ws_bytes(B, T, Cn, W, K)))
+        r.update(pair_h=dev.empty((B * K,), np.int32).upload(np.arange(B * K)), pair_r=dev.empty((B * K,), np.int32).upload(np.repeat(np.arange(B), K)),
                  dist=dev.empty((B, K), np.int32), counts=dev.empty((B * K, 4), np.int32), lens=dev.empty((B * K, 2), np.int32),
                  logp=dev.empty((B, K), np.float64), weight=dev.empty((B, K), np.float32), exp_risk=dev.empty((B,), np.float32),
                  ws_risk=dev.bytes(lib.mgr_ctc_risk_ws_bytes(B, T, Cn, K, Lcap, 0, None)))
@@ -1687,8 +1722,13 @@ class Engine:
         if cw != 0.0:
             dev.call("mgr_ctc_loss_grad", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1, eps, cw / B,
                      self.loss_b, self.dLogits, self.ws_ctc, self.ws_ctc.nbytes)
-        dev.call("mgr_ctc_beam_search_lm", self.P, self.ilen_d, B, T, Cn, skip, Cn - 1, cfg["beam_width"], eps, r["ext"], None, K, r["out"],
-                 r["out_len"], r["score"], r["lctc"], r["ws_beam"], r["ws_beam"].nbytes)
+        if cfg["source"] == "sample":
+            self.last_sample_seed = self._sample_seed(cfg["sample_seed"])
+            dev.call("mgr_ctc_sample_paths", self.P, self.ilen_d, B, T, Cn, skip, Cn - 1, eps, C.c_uint64(self.last_sample_seed), K, r["out"],
+                     r["out_len"], r["count"], r["n_unique"], None)
+        else:
+            dev.call("mgr_ctc_beam_search_lm", self.P, self.ilen_d, B, T, Cn, skip, Cn - 1, cfg["beam_width"], eps, r["ext"], None, K, r["out"],
+                     r["out_len"], r["score"], r["lctc"], r["ws_beam"], r["ws_beam"].nbytes)
         dev.call("mgr_edit_distance", r["out"], r["out_len"], B * K, T - skip, self.labels_d, self.llen_d, B, self.Lmax, r["pair_h"],
                  r["pair_r"], B * K, *cfg["costs"], 0, r["dist"], r["counts"], r["lens"], None, None, None, 0)
         dev.call("mgr_ctc_risk_grad", self.P, self.ilen_d, B, T, Cn, skip, Cn - 1, eps, None, None, 0, r["out"], r["out_len"], K, T - skip,

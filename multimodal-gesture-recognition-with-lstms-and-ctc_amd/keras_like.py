@@ -389,12 +389,14 @@ class Model:
         """Minimum-risk fine-tuning of a CTC-trained network (Engine.set_risk): cfg = dict(top_paths=8, beam_width=16,
         ctc_weight=0.1, costs=(1, 1, 1), post_scale=1.0, max_labels=None) or a part of it - the training loss becomes the expected edit
         distance over the step's own N-best list + ctc_weight x the CTC loss; train_on_batch leaves the parts in last_logs ("loss",
-        "risk", "ctc_loss"), fit_generator logs their epoch means.  None: plain CTC training again.  Single GPU only."""
+        "risk", "ctc_loss"), fit_generator logs their epoch means.  source="sample" (with sample_seed=None: the engine's seed) draws the
+        hypothesis set - top_paths sampled alignments per sample, merged - where source="beam", the default, searches for it (DESIGN
+        9o).  None: plain CTC training again.  Single GPU only."""
         if cfg is not None and self.comm is not None:
             raise NotImplementedError("minimum-risk training is single-GPU: data-parallel risk training is not implemented")
-        self._risk = None if cfg is None else dict(cfg)
         if self._engine is not None and not self._engine.inference_only:
-            self._engine.set_risk(self._risk)
+            self._engine.set_risk(None if cfg is None else dict(cfg))      # (a cfg the engine refuses leaves the mode as it was)
+        self._risk = None if cfg is None else dict(cfg)
 
     def distribute(self, comm, world):
         """Attach a data-parallel communicator (mgr_amd.parallel.RcclComm / HostComm) before the first batch.  The engine is
@@ -592,7 +594,7 @@ class Model:
         return ({k: pad(v) for k, v in arrs.items()} if isinstance(arrs, dict) else pad(arrs)), n
 
     def predict_generator(self, generator, steps, verbose=0, decode=None, beam_width=10, threshold=None, lm=None, lm_end=None,
-                          alpha=1.0, beta=0.0, top_paths=1, lexicon=None, **kwargs):
+                          alpha=1.0, beta=0.0, top_paths=1, lexicon=None, draws=8, sample_seed=0, **kwargs):
         """keras Model.predict_generator (sequence_decoding.py:118-127): the batches of the run are pipelined through
         Engine.predict_stream - upload and encoder pass of batch n + 1 beside the fusion layer / head of batch n and the
         download of batch n - 1 - and give bit for bit what predict_on_batch gives one batch at a time.
@@ -605,7 +607,9 @@ class Model:
         bonus beta and top_paths hypotheses per sample: decoding.beam_search_lm_decode of the posteriors, computed on the device;
         decode="lexicon" returns (segments, score, logp) of mgr_ctc_lexicon_decode - per sample the best sequence of the phrases of
         `lexicon` as (phrase, first_frame, last_frame, confidence), with the phrase bigram lm / lm_end (decoding.phrase_lm_tables)
-        weighted alpha and the per-phrase bonus beta: decoding.lexicon_decode of the posteriors, computed on the device."""
+        weighted alpha and the per-phrase bonus beta: decoding.lexicon_decode of the posteriors, computed on the device;
+        decode="sample" returns (paths, counts) of mgr_ctc_sample_paths - per sample the unique labellings among `draws` sampled
+        alignments and how many draws gave each (decoding.sample_hypotheses of the posteriors; batch i draws with seed sample_seed + i)."""
         steps = int(steps)
         if steps <= 0:
             return np.zeros((0,))
@@ -632,7 +636,7 @@ class Model:
         outs = []
         for i, r in enumerate(e.predict_stream(feed(), output=decode or "posteriors", train_phase=bool(learning_phase()),
                                                beam_width=beam_width, threshold=threshold, lm=lm, lm_end=lm_end, alpha=alpha, beta=beta,
-                                               top_paths=top_paths, lexicon=lexicon)):
+                                               top_paths=top_paths, lexicon=lexicon, draws=draws, sample_seed=sample_seed)):
             # a result is one member or a tuple of members, a member a per-sample list or an array with leading dimension B: each is
             # trimmed to the batch's true sample count, and the batches are joined member by member
             outs.append(tuple(m[:counts[i]] for m in r) if isinstance(r, tuple) else r[:counts[i]])
