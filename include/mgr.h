@@ -566,6 +566,40 @@ int mgr_ctc_align(mgr_ctx* ctx, const float* P, const int32_t* labels, const int
 int mgr_greedy_segments(mgr_ctx* ctx, const float* P, int B, int T, int C, int skip, float thr, int cap, int32_t* n_runs, int32_t* lab,
                         int32_t* seg, float* conf);
 
+/* ---- K17 / K18: posterior gesture extents and the frame-overlap (Jaccard) counts. ---- */
+/* Forward-backward state posteriors of each sample's label sequence and extents read off them at a quantile: where mgr_ctc_align reports
+ * the frames of the single best alignment, this call weighs every alignment.  Conventions are those of mgr_ctc_loss_grad and
+ * mgr_ctc_align, argument for argument (P[:, skip:, :], y = softmax(log(P+eps)), labels [B,Lmax] padded -1 and clipped into the class
+ * range, input_len / label_len clipped), and alpha, beta and logp are the loss's own: the call runs the loss's emission and chain
+ * kernels inside the loss's workspace, ws >= mgr_ctc_ws_bytes(B, T, C, Lmax).  States are l' = [blank, l_1, blank, ..., l_L, blank],
+ * S = 2 * Lmax + 1 columns; gamma(t, s) = P(state s at frame t | labels, posteriors), each frame normalised by its own sum.
+ *   gamma [B,T-skip,S] float or NULL: 0 from input_len on and for states >= 2 * label_len + 1.
+ *   seg   [B,Lmax,2] int32: with cum(t, s) = sum_{s' >= s} gamma(t, s'), first_i = min{t : cum(t, 2i+1) >= q} (label i has begun with
+ *                           probability >= q) and last_i = max{t : cum(t, 2i+2) <= 1 - q} (it has not ended with probability >= q), as
+ *                           indices of the ORIGINAL sequence (t + skip), inclusive; q = quantile in (0, 0.5].  first_i <= last_i and
+ *                           first_i < first_{i+1}; below q = 0.5 neighbouring extents may overlap (they are credible intervals).
+ *                           cum is formed from the float32 values that go to gamma, added one at a time in float32 from state S - 1
+ *                           downwards and compared with (float)q and 1.0f - (float)q: seg is a function of gamma alone, and the same
+ *                           whether gamma is asked for or not.  -1 for i >= label_len.
+ *   occ   [B,Lmax] float:   sum_t gamma(t, 2i+1), the expected number of frames in label i, summed in ascending t; 0 for i >= label_len.
+ *   conf  [B,Lmax] float:   sum_t gamma(t, 2i+1) P[b,t+skip,l_i] / occ_i - mgr_ctc_align's conf weighted by the posterior.
+ *   logp  [B] double:       ln p(labels | posteriors) = -loss of mgr_ctc_loss_grad.
+ * Edge cases as mgr_ctc_align: label_len 0 gives no segments and all of gamma in state 0; a label sequence that does not fit its input,
+ * or an input length of 0, gives logp = -inf, seg -1, occ, conf and gamma 0 for that sample alone.  Deterministic; samples are
+ * independent of each other.  Lmax <= 255. */
+int mgr_ctc_occupancy(mgr_ctx* ctx, const float* P, const int32_t* labels, const int32_t* input_len, const int32_t* label_len, int B, int T,
+                      int C, int Lmax, int skip, int blank, float eps, float quantile, float* gamma, int32_t* seg, float* occ, float* conf,
+                      double* logp, void* ws, size_t ws_bytes);
+/* Per sample and class, the number of frames covered by the hypothesis segments and the reference segments of that class: their
+ * intersection, their union and each side's own count (all [B,C] int32, exact) - inter / uni is the Jaccard index of the class.
+ * hyp_lab [B,Sh], hyp_seg [B,Sh,2], ref_lab [B,Sr], ref_seg [B,Sr,2] (first and last frame, inclusive), n_frames [B], all device memory.
+ * A segment with a label outside [0, C), a label in ignore_mask (bit l = class l, as mgr_edit_distance's) or first < 0 is skipped;
+ * extents are clipped to [0, n_frames); segments of one class on one side are united, segments of different classes may overlap.
+ * C <= 64, Sh and Sr <= 4096.  Needs no workspace. */
+int mgr_segment_overlap(mgr_ctx* ctx, const int32_t* hyp_lab, const int32_t* hyp_seg, int Sh, const int32_t* ref_lab, const int32_t* ref_seg,
+                        int Sr, const int32_t* n_frames, int B, int C, uint64_t ignore_mask, int32_t* inter, int32_t* uni,
+                        int32_t* hyp_frames, int32_t* ref_frames);
+
 /* ---- K13: lexicon-constrained CTC decode: the best PHRASE sequence whose word expansion the posteriors support - HTK
  * HVite's token pass over a phrase lexicon composed with the CTC topology, with an optional prior over phrase sequences.  The audio
  * network's classes are words, its gestures phrases of words (audio_network/data_generator.py: class_2_words).

@@ -127,6 +127,8 @@ SIGNATURES = {
     "mgr_ctc_align_ws_bytes": (sz, [i32, i32, i32, i32]),
     "mgr_ctc_align": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, vp, sz]),
     "mgr_greedy_segments": (i32, [vp, vp, i32, i32, i32, i32, C.c_float, i32, vp, vp, vp, vp]),
+    "mgr_ctc_occupancy": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, sz]),
+    "mgr_segment_overlap": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, u64, vp, vp, vp, vp]),
     "mgr_ctc_lexicon_ws_bytes": (sz, [i32, i32, i32, i32, vp]),
     "mgr_ctc_lexicon_decode": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp,
                                      sz]),

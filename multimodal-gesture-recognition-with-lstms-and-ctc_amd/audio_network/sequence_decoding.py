@@ -1,7 +1,7 @@
 """Decode for the audio network (reference audio_network/sequence_decoding.py:19-69): word-level classes, thr .75."""
 import numpy as np
 
-from ..decoding import (HTK_COSTS, decode_beam_mlf, decode_lexicon_mlf, decode_samples_map, decode_score_map, expected_risk_map, greedy_decode,
+from ..decoding import (HTK_COSTS, decode_beam_mlf, decode_extents_lexicon_mlf, decode_lexicon_mlf, decode_samples_map, decode_score_map, expected_risk_map, greedy_decode,
                         greedy_decode_argmax, greedy_segments, write_mlf)
 from .data_generator import class_2_words
 
@@ -66,6 +66,15 @@ def decode_lexicon(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, 
     lists, segment lists of (gesture id, first_frame, last_frame, confidence))."""
     return decode_lexicon_mlf(pred_out, f_list, GESTURE_LEXICON, gesture_names, ignore_list, "Sample%05d_audio", out_file, lm=lm,
                               lm_end=lm_end, alpha=alpha, beta=beta)
+
+
+def decode_extents(pred_out, f_list, quantile=0.5, out_file="ctc_recout_gesture_extents.mlf", lm=None, lm_end=None, alpha=1.0, beta=0.0):
+    """decode_lexicon with extents in place of the Viterbi path's frames: decode_lexicon's phrases give each file's gesture
+    sequence, decoding.posterior_align the posterior extents of their word expansion at `quantile`; a gesture's extent runs from its
+    first word's first frame to its last word's last frame (grouped on the host).  Returns (gesture-name lists, segment lists of
+    (gesture id, first_frame, last_frame, confidence, occupancy))."""
+    return decode_extents_lexicon_mlf(pred_out, f_list, GESTURE_LEXICON, gesture_names, ignore_list, "Sample%05d_audio", out_file,
+                                      quantile=quantile, lm=lm, lm_end=lm_end, alpha=alpha, beta=beta)
 
 
 def decode_samples(pred_out, f_list, draws=8, seed=0, **kwargs):

@@ -20,6 +20,7 @@ enum : unsigned {
   MGR_ATTR_PROJ_SPLIT = 16u, MGR_ATTR_DW_SPLIT = 32u, MGR_ATTR_PROJ_NARROW = 2048u,                // gemm_split.hip (two), gemm.hip
   MGR_ATTR_CTC = 128u, MGR_ATTR_ALIGN = 512u, MGR_ATTR_SEGMENTS = 1024u, MGR_ATTR_ROI = 256u,      // ctc.hip, align.hip (two), roi.hip
   MGR_ATTR_LEXICON = 4096u, MGR_ATTR_RISK = 8192u,                                                 // lexicon.hip, risk.hip
+  MGR_ATTR_OVERLAP = 16384u,                                                                       // overlap.hip
 };
 
 struct mgr_ctx {

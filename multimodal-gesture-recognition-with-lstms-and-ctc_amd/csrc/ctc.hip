@@ -335,6 +335,169 @@ __global__ __launch_bounds__(256) void k_ctc_grad(const float* __restrict__ P, c
   ctc_phase2(s_, threadIdx.x, (int)blockIdx.x, smem, P, T, C, skip, blank, eps, gscale, 2 * (Lmax + 1), dead, dLogits);
 }
 
+// ---- K17: state posteriors and quantile extents.  gamma(t, s) = alpha(t, s) beta(t, s) / sum_s', from the loss's own chains.
+//
+// k_ctc_occupancy: one workgroup per sample, looping over tiles of FT frames (FT = 256, 128 or 64: what fits the LDS), three phases a tile:
+//   fill   the tile's alpha and beta rows are ONE contiguous stretch of the workspace each (rows lie two time steps a block): all 256
+//          threads read it front to back with 8-byte loads and put log2 alpha + log2 beta into an LDS row per FRAME of odd length
+//          2 (Lmax + 1) + 1, so that the walk below - a thread per frame, every lane at the same state - meets no bank twice; the
+//          frames' posteriors P go into a second tile (odd row length again) for conf;
+//   walk   a thread per frame: the row's maximum, the weights 2^(x - max) and their sum in ascending state order (k_ctc_grad's order),
+//          then from the last state down gamma = w * (1 / sum) and the running sum cum - one rounded multiplication and one rounded
+//          addition per state, never a fused one: seg is a function of the float32 gamma alone, which a sequential float32 sum on the
+//          host restates bit for bit.  gamma >= 0, so its sign bit carries the state's flag to the next phase: for a label state
+//          2i + 1 "cum >= q" (label i has begun), for the blank behind it 2i + 2 "cum <= 1 - q" (label i has not ended);
+//   labels a thread per label, over the tile's frames in ascending order: the first frame with the label state's flag, the last with the
+//          blank's, the sums of gamma and gamma * P[t, l_i] - no atomics, one fixed order.
+// gamma leaves the tile with contiguous stores.  Nothing here depends on whether gamma is asked for but those stores.
+constexpr int kOccLdsMax = 160 * 1024;
+__host__ __device__ inline int occ_row(int Lmax) { return 2 * (Lmax + 1) + 1; }
+static size_t occ_lds_bytes(int ft, int C, int Lmax) { return ((size_t)ft * (occ_row(Lmax) + (C | 1)) + (Lmax + 1)) * sizeof(float); }
+static int occ_frame_tile(int C, int Lmax) {
+  for (int ft = 256; ft >= 64; ft >>= 1)
+    if (occ_lds_bytes(ft, C, Lmax) <= (size_t)kOccLdsMax) return ft;
+  return 0;
+}
+
+// logp = -loss, the loss's float widened
+__global__ __launch_bounds__(256) void k_occ_logp(const float* __restrict__ loss, int B, double* __restrict__ logp) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b < B) logp[b] = -(double)loss[b];
+}
+
+__global__ __launch_bounds__(256) void k_ctc_occupancy(const float* __restrict__ P, const int32_t* __restrict__ labels,
+                                                       const int32_t* __restrict__ input_len, const int32_t* __restrict__ label_len, int B, int T,
+                                                       int C, int Lmax, int skip, int FT, float q, const double* __restrict__ logp,
+                                                       float* __restrict__ gamma, int32_t* __restrict__ seg, float* __restrict__ occ,
+                                                       float* __restrict__ conf, float* LY, float* AL, float* BE) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];  // [FT][RS] alpha + beta -> weights -> gamma | [FT][Cp] P | the label row
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int To = T - skip, S2 = 2 * (Lmax + 1), RS = occ_row(Lmax), Cp = C | 1, S = 2 * Lmax + 1;
+  float* tile = smem;
+  float* ptile = tile + (size_t)FT * RS;
+  const CtcSample s_ = ctc_sample(b, B, input_len, label_len, To, C, Lmax, LY, AL, BE, reinterpret_cast<int*>(ptile + (size_t)FT * Cp));
+  ctc_labels(s_, tid, 256, labels, C, Lmax);
+  const bool dead = !(logp[b] > -__builtin_huge_val());   // (no alignment fits, or no frames at all)
+  const int Tp = dead ? 0 : s_.Tp, L = s_.L;
+  const float omq = 1.0f - q;
+  int first = -1, last = -1;    // of label `tid`, in frames of P[:, skip:]
+  float so = 0.f, sc = 0.f;
+  for (int t0 = 0; t0 < To; t0 += FT) {
+    const int nf = Tp - t0 < 0 ? 0 : (Tp - t0 > FT ? FT : Tp - t0);
+    __syncthreads();   // (the labels; the tile's readers of the round before)
+    if (nf > 0) {
+      // frames t0 .. t0 + nf - 1 (t0 is even): blocks t0 / 2 .. of two rows each, S2 float2 a block - (p, step) at float2 2 p + step
+      const float2* a2 = reinterpret_cast<const float2*>(s_.ALb + (size_t)t0 * S2);
+      const float2* b2 = reinterpret_cast<const float2*>(s_.BEb + (size_t)t0 * S2);
+      const int n2 = ((nf + 1) >> 1) * S2;   // (an odd nf reads the half block behind it - inside the sample's rows - into a row nobody walks)
+      for (int i = tid; i < n2; i += 256) {
+        const int blk = i / S2, r = i - blk * S2;
+        const float2 a = a2[i], be = b2[i];
+        float* d = tile + (size_t)(2 * blk + (r & 1)) * RS + (r >> 1) * 2;
+        d[0] = a.x + be.x;
+        d[1] = a.y + be.y;
+      }
+      const float* prow = P + ((size_t)b * T + skip + t0) * C;
+      for (int i = tid; i < nf * C; i += 256) {
+        const int f = i / C;
+        ptile[(size_t)f * Cp + (i - f * C)] = prow[i];
+      }
+    }
+    __syncthreads();
+    if (tid < nf) {
+      float* row = tile + (size_t)tid * RS;
+      const int ns = 2 * L + 1;
+      // (each pass takes eight states at a time, the LDS reads first: a wave that is alone on its SIMD has nothing else to hide their
+      // latency behind.  The order of every sum is that of the plain loops.)
+      float vmax = kNegInf;
+      int s = 0;
+      for (; s + 8 <= ns; s += 8) {
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = row[s + k];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) vmax = fmaxf(vmax, v[k]);
+      }
+      for (; s < ns; ++s) vmax = fmaxf(vmax, row[s]);
+      float den = 0.f;
+      for (s = 0; s + 8 <= ns; s += 8) {
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = exp2_raw(row[s + k] - vmax);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          row[s + k] = v[k];
+          den += v[k];
+        }
+      }
+      for (; s < ns; ++s) {
+        const float w = exp2_raw(row[s] - vmax);
+        row[s] = w;
+        den += w;
+      }
+      const float iden = 1.f / den;   // sum_s alpha beta = p(l|x) at every t: each frame is normalised by its own sum
+      float cum = 0.f;
+      auto state = [&](int st, float w) {
+        const float g = __fmul_rn(w, iden);
+        cum = __fadd_rn(cum, g);
+        const bool flag = (st & 1) ? (cum >= q) : (st >= 2 && cum <= omq);
+        return flag ? __uint_as_float(__float_as_uint(g) | 0x80000000u) : g;
+      };
+      for (s = ns - 1; s >= 7; s -= 8) {
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = row[s - k];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = state(s - k, v[k]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) row[s - k] = v[k];
+      }
+      for (; s >= 0; --s) row[s] = state(s, row[s]);
+    }
+    __syncthreads();
+    if (tid < L) {
+      const int lab = s_.s_lab[tid];
+      auto frame = [&](int f, float v, float u, float pl) {
+        if ((__float_as_uint(v) >> 31) && first < 0) first = t0 + f;
+        if (__float_as_uint(u) >> 31) last = t0 + f;
+        const float g = fabsf(v);
+        so += g;
+        sc += g * pl;
+      };
+      const float* col = tile + 2 * tid + 1;
+      int f = 0;
+      for (; f + 4 <= nf; f += 4) {
+        float v[4], u[4], pl[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          v[k] = col[(size_t)(f + k) * RS];
+          u[k] = col[(size_t)(f + k) * RS + 1];
+          pl[k] = ptile[(size_t)(f + k) * Cp + lab];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) frame(f + k, v[k], u[k], pl[k]);
+      }
+      for (; f < nf; ++f) frame(f, col[(size_t)f * RS], col[(size_t)f * RS + 1], ptile[(size_t)f * Cp + lab]);
+    }
+    if (gamma) {
+      const int nfa = To - t0 > FT ? FT : To - t0;
+      float* out = gamma + ((size_t)b * To + t0) * S;
+      for (int i = tid; i < nfa * S; i += 256) {
+        const int f = i / S, s = i - f * S;
+        out[i] = (f < nf && s <= 2 * L) ? fabsf(tile[(size_t)f * RS + s]) : 0.f;
+      }
+    }
+  }
+  if (tid < Lmax) {
+    const bool ok = tid < L && Tp > 0;
+    const size_t o = (size_t)b * Lmax + tid;
+    seg[2 * o] = (ok && first >= 0) ? first + skip : -1;
+    seg[2 * o + 1] = (ok && last >= 0) ? last + skip : -1;
+    occ[o] = ok ? so : 0.f;
+    conf[o] = (ok && so > 0.f) ? sc / so : 0.f;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -348,35 +511,37 @@ static CtcWs ctc_ws_layout(void* ws, int B, size_t To, int C, int Lmax) {
 }
 size_t mgr_ctc_ws_bytes(int B, int T, int C, int Lmax) { return ctc_ws_layout(nullptr, B, (size_t)(T > 0 ? T : 1), C, Lmax).bytes; }
 
-int mgr_ctc_loss_grad(mgr_ctx* c, const float* P, const int32_t* labels, const int32_t* input_len,
-                      const int32_t* label_len, int B, int T, int C, int Lmax, int skip, int blank, float eps,
-                      float gscale, float* loss, float* dLogits, void* ws, size_t ws_bytes) {
-  MGR_REQUIRE(c && P && labels && input_len && label_len && loss, "null argument");
+// The argument checks the loss and the occupancies share.
+static int ctc_check_args(mgr_ctx* c, const float* P, const int32_t* labels, const int32_t* input_len, const int32_t* label_len, int B, int T, int C,
+                          int Lmax, int skip, int blank, void* ws, size_t ws_bytes) {
+  MGR_REQUIRE(c && P && labels && input_len && label_len, "null argument");
   mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   MGR_REQUIRE(B > 0 && T > skip && skip >= 0 && C > 1 && Lmax > 0, "bad shape B=%d T=%d C=%d Lmax=%d skip=%d", B, T, C, Lmax, skip);
   MGR_REQUIRE(blank >= 0 && blank < C, "blank %d out of range", blank);
   MGR_REQUIRE(Lmax + 1 <= 256, "Lmax %d too large (max 255)", Lmax);
   MGR_REQUIRE(ws && ws_bytes >= mgr_ctc_ws_bytes(B, T, C, Lmax), "workspace too small");
+  return 0;
+}
+
+// The emissions and the two chains of every sample: what mgr_ctc_loss_grad and mgr_ctc_occupancy both start with (the caller has opened
+// the profile family).  frame_kib > 0: the LDS the emission kernel asks for, see below.
+static int ctc_launch_chains(mgr_ctx* c, const float* P, const int32_t* labels, const int32_t* input_len, const int32_t* label_len, int B, int T,
+                             int C, int Lmax, int skip, int blank, float eps, float* loss, const CtcWs& L) {
   const size_t To = (size_t)T;
-  const CtcWs L = ctc_ws_layout(ws, B, To, C, Lmax);
   float *LY = L.LY, *AL = L.AL, *BE = L.BE;
   // two samples per workgroup (one chain per SIMD) from B = 2 on; MGR_TUNE_CTC_ONE_SAMPLE = 1: one sample per workgroup (rounds 1 - 5)
   const int spw = (B >= 2 && c->tune[MGR_TUNE_CTC_ONE_SAMPLE] == 0) ? 2 : 1;
-  size_t lds_grad = (size_t)256 * (C + 1) * sizeof(float) + (size_t)(Lmax + 1) * sizeof(int);
   size_t lds_chains = (size_t)spw * (Lmax + 1) * sizeof(int) + 16, lds_emis = 0;
-  MGR_REQUIRE(lds_grad <= 160 * 1024, "C=%d too large for the LDS occupancy tile", C);
   // KiB of LDS the recurrence / the per-frame kernels ask for at least.  Placement: a workgroup that asks for more than a persistent
   // scan workgroup leaves on its CU can only land on a CU without one (the engine sets them for the steps of its fused schedule,
   // where this call runs beside 208 whole-CU scan workgroups: 96 KiB = the 32 recurrence workgroups on a CU each)
   const int chain_kib = c->tune[MGR_TUNE_CTC_CHAIN_LDS_KIB], frame_kib = c->tune[MGR_TUNE_CTC_FRAME_LDS_KIB];
   if (chain_kib > 0 && lds_chains < (size_t)chain_kib * 1024) lds_chains = (size_t)chain_kib * 1024;
-  if (frame_kib > 0) {
-    if (lds_grad < (size_t)frame_kib * 1024) lds_grad = (size_t)frame_kib * 1024;
-    lds_emis = (size_t)frame_kib * 1024;
-  }
+  if (frame_kib > 0) lds_emis = (size_t)frame_kib * 1024;
   if (!(c->attr_done & MGR_ATTR_CTC)) {
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_emissions), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_grad), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_occupancy), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_chains<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_chains<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ctc_chains<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -390,7 +555,6 @@ int mgr_ctc_loss_grad(mgr_ctx* c, const float* P, const int32_t* labels, const i
   int npairs = Lmax + 1;
   int ppl = (npairs + 63) / 64;
   hipStream_t s = mgr_stream(c);
-  mgr_prof_begin(c, MGR_K_CTC);
   hipLaunchKernelGGL(k_ctc_emissions, dim3((unsigned)((To + 255) / 256), B), dim3(256), lds_emis, s, P, input_len, label_len, B, T, C, Lmax, skip, eps, LY, AL, BE);
 #define MGR_CTC_LAUNCH(N)                                                                                                              \
   do {                                                                                                                                 \
@@ -408,9 +572,46 @@ int mgr_ctc_loss_grad(mgr_ctx* c, const float* P, const int32_t* labels, const i
     default: MGR_CTC_LAUNCH(4); break;
   }
 #undef MGR_CTC_LAUNCH
+  return 0;
+}
+
+int mgr_ctc_loss_grad(mgr_ctx* c, const float* P, const int32_t* labels, const int32_t* input_len,
+                      const int32_t* label_len, int B, int T, int C, int Lmax, int skip, int blank, float eps,
+                      float gscale, float* loss, float* dLogits, void* ws, size_t ws_bytes) {
+  MGR_REQUIRE(loss, "null argument");
+  if (int rc = ctc_check_args(c, P, labels, input_len, label_len, B, T, C, Lmax, skip, blank, ws, ws_bytes)) return rc;
+  const CtcWs L = ctc_ws_layout(ws, B, (size_t)T, C, Lmax);
+  size_t lds_grad = (size_t)256 * (C + 1) * sizeof(float) + (size_t)(Lmax + 1) * sizeof(int);
+  MGR_REQUIRE(lds_grad <= 160 * 1024, "C=%d too large for the LDS occupancy tile", C);
+  const int frame_kib = c->tune[MGR_TUNE_CTC_FRAME_LDS_KIB];
+  if (frame_kib > 0 && lds_grad < (size_t)frame_kib * 1024) lds_grad = (size_t)frame_kib * 1024;
+  hipStream_t s = mgr_stream(c);
+  mgr_prof_begin(c, MGR_K_CTC);
+  if (int rc = ctc_launch_chains(c, P, labels, input_len, label_len, B, T, C, Lmax, skip, blank, eps, loss, L)) return rc;
   if (dLogits)
     hipLaunchKernelGGL(k_ctc_grad, dim3((unsigned)((T + 255) / 256), B), dim3(256), lds_grad, s, P, labels, input_len, label_len, B, T, C, Lmax, skip,
-                       blank, eps, gscale, loss, dLogits, LY, AL, BE);
+                       blank, eps, gscale, loss, dLogits, L.LY, L.AL, L.BE);
+  MGR_LAUNCH_CHECK();
+  mgr_prof_end(c, MGR_K_CTC);
+  return 0;
+}
+
+int mgr_ctc_occupancy(mgr_ctx* c, const float* P, const int32_t* labels, const int32_t* input_len, const int32_t* label_len, int B, int T,
+                      int C, int Lmax, int skip, int blank, float eps, float quantile, float* gamma, int32_t* seg, float* occ, float* conf,
+                      double* logp, void* ws, size_t ws_bytes) {
+  MGR_REQUIRE(seg && occ && conf && logp, "null argument");
+  if (int rc = ctc_check_args(c, P, labels, input_len, label_len, B, T, C, Lmax, skip, blank, ws, ws_bytes)) return rc;
+  MGR_REQUIRE(quantile > 0.f && quantile <= 0.5f, "quantile %g outside (0, 0.5]", (double)quantile);
+  const int ft = occ_frame_tile(C, Lmax);
+  MGR_REQUIRE(ft > 0, "C=%d too large for the LDS tiles at Lmax=%d", C, Lmax);
+  const CtcWs L = ctc_ws_layout(ws, B, (size_t)T, C, Lmax);
+  hipStream_t s = mgr_stream(c);
+  mgr_prof_begin(c, MGR_K_CTC);
+  // the chains write the loss as B floats: into the head of conf (B * Lmax >= B floats, all of them rewritten by k_ctc_occupancy)
+  if (int rc = ctc_launch_chains(c, P, labels, input_len, label_len, B, T, C, Lmax, skip, blank, eps, conf, L)) return rc;
+  hipLaunchKernelGGL(k_occ_logp, dim3((B + 255) / 256), dim3(256), 0, s, conf, B, logp);
+  hipLaunchKernelGGL(k_ctc_occupancy, dim3(B), dim3(256), occ_lds_bytes(ft, C, Lmax), s, P, labels, input_len, label_len, B, T, C, Lmax, skip, ft,
+                     quantile, logp, gamma, seg, occ, conf, L.LY, L.AL, L.BE);
   MGR_LAUNCH_CHECK();
   mgr_prof_end(c, MGR_K_CTC);
   return 0;

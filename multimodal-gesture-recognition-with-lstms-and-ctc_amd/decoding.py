@@ -144,6 +144,27 @@ def align_op(n_classes, skip, return_path=False, eps=1e-8):
                     ws_bytes=lambda lib, N, T, Lmax: lib.mgr_ctc_align_ws_bytes(N, T, Cn, Lmax), uses_len=True)
 
 
+def occupancy_op(n_classes, skip, quantile=0.5, return_gamma=False, eps=1e-8):
+    """mgr_ctc_occupancy (K17): state posteriors and quantile extents of given labels; it runs in the loss's workspace."""
+    Cn, q = int(n_classes), float(quantile)
+    if not 0.0 < q <= 0.5:
+        raise ValueError("quantile %r is not in (0, 0.5]" % (quantile,))
+
+    def outputs(N, T, Lmax):
+        return (_f32(N, T - skip, 2 * Lmax + 1) if return_gamma else None, _i32(N, Lmax, 2), _f32(N, Lmax), _f32(N, Lmax), _f64(N))
+
+    def launch(dev, P, input_len, outs, tables, ws, labels, label_len):
+        dev.call("mgr_ctc_occupancy", P, labels, input_len, label_len, P.shape[0], P.shape[1], Cn, labels.shape[1], skip, Cn - 1, C.c_float(eps),
+                 C.c_float(q), *outs, ws, ws.nbytes)
+
+    def result(*arrays):
+        lab, ll = arrays[-2:]
+        seg, occ, conf, logp = arrays[-6:-2]
+        clipped = np.clip(lab, 0, Cn - 1)     # (what the kernels align: out-of-range values clipped into the class range, as the loss)
+        return (extents_from_arrays(clipped, ll, seg, conf, occ, logp), logp) + ((arrays[0],) if return_gamma else ())
+    return DecodeOp("occupancy", outputs, launch, result, ws_bytes=lambda lib, N, T, Lmax: lib.mgr_ctc_ws_bytes(N, T, Cn, Lmax), uses_len=True)
+
+
 def rescore_op(n_classes, skip, lexicon=None, eps=1e-8):
     """mgr_ctc_rescore (K14): the hypothesis arrays (hyp (N, K, Lh), hyp_len (N, K)) travel where align passes its labels, so the
     `Lmax` the description's functions get is K."""
@@ -329,6 +350,33 @@ def forced_align(pred_out, labels, label_length=None, input_length=None, skip=2,
     if lab.shape[0] != P.shape[0]:
         raise ValueError("%d label rows for %d samples" % (lab.shape[0], P.shape[0]))
     return _run(align_op(P.shape[2], skip, return_path, eps), P, skip, dev, input_length, (lab, ll))
+
+
+def extents_from_arrays(lab, ll, seg, conf, occ, logp):
+    """mgr_ctc_occupancy's seg / conf / occ arrays -> per sample a list of (label, first_frame, last_frame, confidence, occupancy); a
+    sample whose labels do not fit its input (logp = -inf) has no segments."""
+    out = []
+    for b in range(lab.shape[0]):
+        n = 0 if not np.isfinite(logp[b]) else min(int(ll[b]), lab.shape[1])
+        out.append([(int(lab[b, k]), int(seg[b, k, 0]), int(seg[b, k, 1]), float(conf[b, k]), float(occ[b, k])) for k in range(n)])
+    return out
+
+
+def posterior_align(pred_out, labels, label_length=None, input_length=None, quantile=0.5, skip=2, dev=None, return_gamma=False, eps=1e-8):
+    """Posterior extents on the GPU (mgr_ctc_occupancy): where forced_align reports the frames of the single best alignment, this weighs
+    every CTC alignment of the labels.  gamma(t, s) is the posterior of lattice state s (l' = [blank, l_1, blank, ..., l_L, blank]) at
+    frame t; label i's extent runs from the first frame at which it has begun with probability >= quantile to the last frame at which it
+    has not ended with probability >= quantile.  quantile = 0.5 is the median extent, a smaller one a wider credible extent (neighbouring
+    extents may then overlap); first <= last and the firsts increase for every quantile in (0, 0.5].
+    Returns (segments, logp[, gamma]): per sample a list of (label, first_frame, last_frame, confidence, occupancy) - frames as indices
+    of the ORIGINAL sequence, inclusive; confidence the posterior-weighted mean of P[t, label]; occupancy the expected number of frames
+    spent in the label -, logp (N,) float64 = -loss (-inf and no segments where the labels do not fit), gamma (N, T - skip, 2 Lmax + 1)
+    float32.  A CTC network's posteriors stay peaky: the median extent sits near the Viterbi spikes, smaller quantiles widen it."""
+    P = _posteriors(pred_out)
+    lab, ll = pack_labels(labels, label_length)
+    if lab.shape[0] != P.shape[0]:
+        raise ValueError("%d label rows for %d samples" % (lab.shape[0], P.shape[0]))
+    return _run(occupancy_op(P.shape[2], skip, quantile, return_gamma, eps), P, skip, dev, input_length, (lab, ll))
 
 
 def beam_search_decode(pred_out, input_length=None, beam_width=10, skip=2, merge_repeated=True, dev=None, blank=None):
@@ -1042,3 +1090,159 @@ def decode_score_map(hyp_ids, ref_ids, map_gest, costs=HTK_COSTS, confusion=True
     covers the map's classes, the alignment costs default to HResults'."""
     sil = [k for k, v in map_gest.items() if v == "sil" and k >= 0]
     return score_sequences(hyp_ids, ref_ids, costs=costs, ignore=sil, confusion=confusion, n_classes=1 + max(map_gest), dev=dev)
+
+
+# ---- frame overlap of segment sets (K18, DESIGN 9p): mgr_segment_overlap and the Jaccard index built on its counts -------------------
+def pack_segments(segments):
+    """Per sample a list of (label, first, last, ...) tuples -> (int32 (N, S) labels padded -1, int32 (N, S, 2) extents padded -1)."""
+    S = max([len(r) for r in segments] + [1])
+    lab = -np.ones((len(segments), S), np.int32)
+    seg = -np.ones((len(segments), S, 2), np.int32)
+    for i, r in enumerate(segments):
+        for k, sg in enumerate(r):
+            lab[i, k], seg[i, k, 0], seg[i, k, 1] = int(sg[0]), int(sg[1]), int(sg[2])
+    return lab, seg
+
+
+def segment_overlap(hyp_segments, ref_segments, n_classes, n_frames, ignore=(), dev=None):
+    """Per sample and class the frames covered by both segment sets, by either, and by each (mgr_segment_overlap): four int32 (N,
+    n_classes) arrays (inter, union, hyp_frames, ref_frames), exact.  hyp_segments / ref_segments: per sample a list of (label, first,
+    last, ...) with inclusive frames - what forced_align, posterior_align, greedy_segments and lexicon_decode return; n_frames: an int or
+    one per sample, extents are clipped to [0, n_frames); ignore: label ids in [0, 64) dropped on both sides.  Segments of one class on
+    one side are united; a label outside [0, n_classes) or a negative first frame skips the segment."""
+    Cn = int(n_classes)
+    if not 1 <= Cn <= 64:
+        raise ValueError("n_classes = %d is not in [1, 64]" % Cn)
+    N = len(hyp_segments)
+    if len(ref_segments) != N:
+        raise ValueError("%d hypothesis samples for %d reference samples" % (N, len(ref_segments)))
+    mask = ignore_mask(ignore)
+    if N == 0:
+        return tuple(np.zeros((0, Cn), np.int32) for _ in range(4))
+    nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, np.int64), (N,)).astype(np.int32))
+    hl, hs = pack_segments(hyp_segments)
+    rl, rs = pack_segments(ref_segments)
+    dev = dev or default_device()
+    bufs = []
+    try:
+        bufs += [dev.array(a) for a in (hl, hs, rl, rs, nf)]
+        outs = [dev.empty((N, Cn), np.int32) for _ in range(4)]
+        bufs += outs
+        dev.call("mgr_segment_overlap", bufs[0], bufs[1], hl.shape[1], bufs[2], bufs[3], rl.shape[1], bufs[4], N, Cn, mask, *outs)
+        return tuple(o.download() for o in outs)
+    finally:
+        for a in bufs:
+            a.free()
+
+
+def jaccard_from_counts(inter, union, hyp_frames, ref_frames, false_positives=True):
+    """The Jaccard index from mgr_segment_overlap's counts, in float64 on the host.  Per sample: the mean of inter / union over the
+    classes present in the reference (false_positives=False) or on either side (True: a class only the hypothesis has scores 0 and
+    counts - the penalty as the ChaLearn 2014 challenge's text states it).  A sample with no class to average over is NaN and left out of
+    the mean.  Returns {"jaccard", "per_sample" (N,), "per_class" (C,) - over the samples in which the class counts, NaN where none -,
+    "inter", "union"}."""
+    inter, union = np.asarray(inter, np.int64), np.asarray(union, np.int64)
+    present = (np.asarray(ref_frames) > 0) | ((np.asarray(hyp_frames) > 0) if false_positives else False)
+    ratio = np.where(present, inter / np.maximum(union, 1).astype(np.float64), 0.0)
+    n_s, n_c = present.sum(axis=1), present.sum(axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        per_sample = np.where(n_s > 0, ratio.sum(axis=1) / n_s, np.nan)
+        per_class = np.where(n_c > 0, ratio.sum(axis=0) / n_c, np.nan)
+    ok = n_s > 0
+    return {"jaccard": float(per_sample[ok].mean()) if ok.any() else float("nan"), "per_sample": per_sample, "per_class": per_class,
+            "inter": inter, "union": union}
+
+
+def jaccard_index(hyp_segments, ref_segments, n_classes, n_frames, ignore=(), false_positives=True, dev=None):
+    """segment_overlap on the GPU, then jaccard_from_counts.  Parity with the ChaLearn challenge's own evaluation script is unpinned: the
+    script is not available to this project."""
+    return jaccard_from_counts(*segment_overlap(hyp_segments, ref_segments, n_classes, n_frames, ignore, dev), false_positives=false_positives)
+
+
+def read_mlf_segments(path, frame_period=FRAME_PERIOD_HTK):
+    """The timed lines write_mlf(..., segments=) writes -> {sample name: [(label name, first_frame, last_frame)]}: first = start /
+    frame_period, last = end / frame_period - 1 (the end is the end of the last frame).  Lines without times are refused."""
+    out, cur = {}, None
+    fp = int(frame_period)
+    with open(path) as f:
+        for line in f:
+            line = line.strip()
+            if not line or line == "#!MLF!#":
+                continue
+            if line.startswith('"'):
+                name = line.strip('"').split("/")[-1]
+                cur = out.setdefault(name.rsplit(".", 1)[0], [])
+            elif line == ".":
+                cur = None
+            elif cur is not None:
+                w = line.split()
+                if len(w) < 3 or not (w[0].isdigit() and w[1].isdigit()):
+                    raise ValueError("%s: %r is not a 'start end label' line" % (path, line))
+                cur.append((w[2], int(w[0]) // fp, int(w[1]) // fp - 1))
+    return out
+
+
+def score_mlf_overlap(ref_path, rec_path, names, ignore=("sil",), n_frames=None, **kw):
+    """The Jaccard index of two timed MLF files over the samples present in both.  names: the label names, a name's index is its class
+    id (at most 64; a label not in names is skipped); ignore: label NAMES dropped on both sides; n_frames: {sample name: frames}, an int,
+    or None = up to the last frame any segment of the sample reaches.  kw: frame_period, false_positives, dev.  Returns jaccard_index's
+    dict plus "n_samples" and "samples" (the sample names, in the order of per_sample)."""
+    fp = kw.pop("frame_period", FRAME_PERIOD_HTK)
+    ref, rec = read_mlf_segments(ref_path, fp), read_mlf_segments(rec_path, fp)
+    samples = sorted(set(ref) & set(rec))
+    ids = {n: i for i, n in enumerate(names)}
+    conv = lambda segs: [(ids.get(l, -1), a, b) for l, a, b in segs]
+    hyp, refs = [conv(rec[n]) for n in samples], [conv(ref[n]) for n in samples]
+    if n_frames is None:
+        nf = [max([b + 1 for _, _, b in h + r] + [0]) for h, r in zip(hyp, refs)]
+    elif isinstance(n_frames, dict):
+        nf = [int(n_frames[n]) for n in samples]
+    else:
+        nf = int(n_frames)
+    out = jaccard_index(hyp, refs, len(names), nf, ignore=[ids[n] for n in ignore if n in ids], **kw)
+    out["n_samples"], out["samples"] = len(samples), samples
+    return out
+
+
+def decode_extents_mlf(pred_out, f_list, map_gest, ignore_list, name_fmt, out_file, threshold, quantile=0.5, skip=2, dev=None):
+    """What the modules' decode_extents share: the greedy decode (threshold, as decode_batch) gives each file's label sequence - blank
+    runs dropped -, posterior_align its extents at `quantile`, the class map the names; every MLF line reads "start end name".  Returns
+    (label-name lists, segment lists of (label, first_frame, last_frame, confidence, occupancy))."""
+    P = _posteriors(pred_out)
+    blank = P.shape[2] - 1
+    ids = [[i for i in seq if i != blank] for seq in greedy_decode(P, threshold, skip=skip, dev=dev)]
+    segs, _ = posterior_align(P, ids, quantile=quantile, skip=skip, dev=dev)
+    ret = [[map_gest[s[0]] for s in sg] for sg in segs]
+    if out_file is not None:
+        write_mlf(out_file, ret, f_list, ignore_list, name_fmt, segments=segs)
+    return ret, segs
+
+
+def group_word_extents(word_segments, phrases, lexicon):
+    """Word extents of posterior_align -> one extent per phrase: from its first word's first frame to its last word's last frame; the
+    confidence is the occupancy-weighted mean of its words' confidences, the occupancy their sum.  phrases: the phrase ids whose word
+    expansion (over lexicon) the words are, in order."""
+    out, k = [], 0
+    for g in phrases:
+        ws = word_segments[k:k + len(lexicon[g])]
+        k += len(lexicon[g])
+        if len(ws) < len(lexicon[g]):
+            break               # (the words did not fit the input: no segments came back)
+        occ = sum(w[4] for w in ws)
+        out.append((int(g), ws[0][1], ws[-1][2], sum(w[3] * w[4] for w in ws) / occ if occ > 0 else 0.0, occ))
+    return out
+
+
+def decode_extents_lexicon_mlf(pred_out, f_list, lexicon, names, ignore_list, name_fmt, out_file, quantile=0.5, skip=2, dev=None, **kwargs):
+    """decode_extents for a network whose classes are words: lexicon_decode (kwargs: its lm, lm_end, alpha, beta) gives each file's
+    phrases, posterior_align the extents of their word expansion, group_word_extents - on the host - one extent per phrase."""
+    P = _posteriors(pred_out)
+    phr, _, _ = lexicon_decode(P, lexicon, skip=skip, dev=dev, **kwargs)
+    ids = [[s[0] for s in sg] for sg in phr]
+    words = [[int(w) for g in seq for w in lexicon[g]] for seq in ids]
+    wsegs, _ = posterior_align(P, words, quantile=quantile, skip=skip, dev=dev)
+    segs = [group_word_extents(ws, seq, lexicon) for ws, seq in zip(wsegs, ids)]
+    ret = [[names[s[0]] for s in sg] for sg in segs]
+    if out_file is not None:
+        write_mlf(out_file, ret, f_list, ignore_list, name_fmt, segments=segs)
+    return ret, segs

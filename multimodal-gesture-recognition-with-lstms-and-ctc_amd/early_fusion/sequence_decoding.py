@@ -2,7 +2,7 @@
 0.97 confidence threshold, the list.remove quirk, collapse, MLF."""
 import numpy as np
 
-from ..decoding import HTK_COSTS, decode_beam_mlf, decode_samples_map, decode_score_map, expected_risk_map, greedy_decode, greedy_segments, write_mlf
+from ..decoding import HTK_COSTS, decode_beam_mlf, decode_extents_mlf, decode_samples_map, decode_score_map, expected_risk_map, greedy_decode, greedy_segments, write_mlf
 from ..multimodal_fusion.sequence_decoding import ignore_list, map_gest
 
 THRESHOLD = 0.97
@@ -25,6 +25,14 @@ def decode_segments(pred_out, f_list, out_file="final_ctc_recout_timed.mlf"):
     if out_file is not None:
         write_mlf(out_file, ret, f_list, ignore_list, "Sample%05d", segments=segs)
     return ret, segs
+
+
+def decode_extents(pred_out, f_list, quantile=0.5, out_file="final_ctc_recout_extents.mlf"):
+    """decode_segments with extents in place of spikes: the greedy decode gives each file's gesture sequence (blank runs
+    dropped), decoding.posterior_align its posterior extents - at quantile 0.5 the median extent, near the frames decode_segments
+    reports; a smaller quantile widens them to credible extents, which may overlap.  Returns (label-name lists, segment lists of
+    (label, first_frame, last_frame, confidence, occupancy))."""
+    return decode_extents_mlf(pred_out, f_list, map_gest, ignore_list, "Sample%05d", out_file, THRESHOLD, quantile=quantile)
 
 
 def decode_beam(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, beam_width=10, top_paths=1, out_file="final_ctc_recout_beam.mlf"):

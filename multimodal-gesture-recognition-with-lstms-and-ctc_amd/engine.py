@@ -1023,9 +1023,11 @@ class Engine:
     EV_OUT = (50, 51)     # the result of the batch in output slot 0 / 1 has reached its pinned host buffer
     EV_D1P = (55, 56)     # the depth-1 projections into depth-1 Z set 0 / 1 are done (stream 0)
     EV_D1S = (57, 58)     # the depth-1 scans that read depth-1 Z set 0 / 1 are done (stream ES)
-    LABELLED = ("loss", "align", "score")     # the predict_stream outputs whose batches come with labels (a training engine)
+    LABELLED = ("loss", "align", "occupancy", "score")     # the predict_stream outputs whose batches come with labels (a training engine)
+    ALIGNED = ("align", "occupancy")     # ... whose kernel runs on stream 0 on the batch's own labels and lengths, like the loss
 
-    def decode_ops(self, beam_width=10, merge_repeated=True, threshold=None, top_paths=1, lexicon=None, draws=8, sample_seed=0, **lm_args):
+    def decode_ops(self, beam_width=10, merge_repeated=True, threshold=None, top_paths=1, lexicon=None, draws=8, sample_seed=0, quantile=0.5,
+                   **lm_args):
         """predict_stream's decode outputs: name -> what builds decoding's description of its kernel with this engine's classes, frames
         and eps (nothing is validated before that is called).  Room for T - skip runs / phrases per sample, the most there can be: the
         count the kernel reports never exceeds what is downloaded."""
@@ -1037,11 +1039,12 @@ class Engine:
                 "beam_lm": lambda: decoding.beam_lm_op(Cn, skip, beam_width=beam_width, top_paths=top_paths, eps=eps, **lm_args),
                 "lexicon": lambda: decoding.lexicon_op(Cn, skip, lexicon, cap=room, eps=eps, **lm_args),
                 "sample": lambda: decoding.sample_op(Cn, skip, draws, sample_seed, eps=eps),
-                "align": lambda: decoding.align_op(Cn, skip, return_path=True, eps=eps)}
+                "align": lambda: decoding.align_op(Cn, skip, return_path=True, eps=eps),
+                "occupancy": lambda: decoding.occupancy_op(Cn, skip, quantile, eps=eps)}
 
     def predict_stream(self, batches, output="posteriors", train_phase=False, beam_width=10, merge_repeated=True, threshold=None,
                        lm=None, lm_end=None, alpha=1.0, beta=0.0, top_paths=1, decode="greedy", ignore=None, costs=(1, 1, 1), lexicon=None,
-                       draws=8, sample_seed=0):
+                       draws=8, sample_seed=0, quantile=0.5):
         """Batches of an inference / validation run are independent of each other: this generator keeps two of them in flight.
         Batch n + 1 is uploaded (copy stream) and runs its encoder pass (stream ES, into the other FEAT buffer) beside batch n's
         fusion layer / head / decode kernels (stream 0) and beside the download of batch n - 1's result (its own stream, into
@@ -1049,7 +1052,7 @@ class Engine:
         predict_generator over the whole set (sequence_decoding.py:118-127) and with the validation loop of every epoch
         (multimodal.py:264-269), one blocking batch at a time.
 
-        batches: iterable of input dicts {stream name: (B, T, F)} - for output="loss", "align" and "score" of tuples (inputs, labels,
+        batches: iterable of input dicts {stream name: (B, T, F)} - for output="loss", "align", "occupancy" and "score" of tuples (inputs, labels,
         input_length, label_length).  Yields, in order, per batch:
           "posteriors"  P (B, T, C) float32                  (learning phase 0 unless train_phase)
           "argmax"      (best (B, T - skip) int32, prob (B, T - skip) float32): mgr_frame_argmax on the device, the (B, T, C)
@@ -1068,6 +1071,9 @@ class Engine:
                         where "argmax" runs mgr_frame_argmax - the greedy decode with its frame positions (decoding.greedy_segments)
           "align"       (segments: list of B lists of (label, first_frame, last_frame, confidence), logp (B,) float64, path
                         (B, T - skip) int32): mgr_ctc_align of each sample's labels to its posteriors (a training engine, like "loss")
+          "occupancy"   (segments: list of B lists of (label, first_frame, last_frame, confidence, occupancy), logp (B,) float64):
+                        mgr_ctc_occupancy at `quantile` where "align" runs mgr_ctc_align - the posterior extents of each sample's labels
+                        (decoding.posterior_align of the posteriors), in the engine's CTC workspace
           "score"       (loss (B,) float32, dist (B,) int32, counts (B, 4) int32 = (H, S, D, I), lens (B, 2) int32 = (m, n)): the CTC
                         loss exactly as "loss" computes it and, on the output stream, the decode kernel of decode = "greedy"
                         (mgr_greedy_segments with threshold) | "beam" | "beam_lm" (beam_width, lm, ... as above, one path) followed
@@ -1089,7 +1095,7 @@ class Engine:
         Cn, skip, eps = sp.num_classes, int(sp.ctc["skip"]), float(sp.ctc["eps"])
         # ("score" decodes one path; top_paths is read for "beam_lm" alone)
         ops = self.decode_ops(beam_width, merge_repeated, threshold, top_paths if output == "beam_lm" else 1, lexicon, draws, sample_seed,
-                               lm=lm, lm_end=lm_end, alpha=alpha, beta=beta)
+                               quantile, lm=lm, lm_end=lm_end, alpha=alpha, beta=beta)
         if output not in ("posteriors", "loss", "score", "rescore") + tuple(ops):
             raise ValueError("unknown output %r" % (output,))
         labelled = output in self.LABELLED
@@ -1147,18 +1153,21 @@ class Engine:
         if op is not None:
             # The op's device outputs, workspace and tables, each cached under what sizes it - so "segments" and "score" with the greedy
             # decode, or "beam_lm" and "score" at one path, share them.  One set of outputs: decode, comparison and copies of a batch are
-            # consecutive on the output stream - but two for "align", which runs on stream 0: one per output slot, like the losses below
+            # consecutive on the output stream - but two for "align" / "occupancy", which run on stream 0: one per output slot, like the losses below
             Lq = hshape[1] if hypo else self.Lmax       # ("rescore": K travels where the labelled ops get Lmax)
             shapes = op.outputs(B, T, Lq)
             dring = bufs((name, "out", shapes), lambda: [tuple(sh if sh is None else self.mem.empty(*sh) for sh in shapes)
-                                                        for _ in range(2 if name == "align" else 1)])
+                                                        for _ in range(2 if name in self.ALIGNED else 1)])
             nbytes = op.ws_bytes(self.lib, B, T, Lq) if op.ws_bytes else None
-            ws = None if nbytes is None else bufs((name, "ws", nbytes), lambda: self.mem.bytes(nbytes))
+            if name == "occupancy":     # (the loss's layout, on the loss's stream: the engine's CTC workspace serves it)
+                ws = self.ws_ctc
+            else:
+                ws = None if nbytes is None else bufs((name, "ws", nbytes), lambda: self.mem.bytes(nbytes))
             # (the tables are uploaded once per call, not per batch)
             tables = [t if t is None else bufs((name, "table", k, t.shape), lambda: self.mem.empty(t.shape, t.dtype)).upload(t)
                       for k, t in enumerate(op.tables)]
-            dil = None          # ("align" reads the lengths that came with the labels)
-            if op.uses_len and name != "align":
+            dil = None          # ("align" / "occupancy" read the lengths that came with the labels)
+            if op.uses_len and name not in self.ALIGNED:
                 dil = bufs("dil", lambda: self.mem.empty((B,), np.int32)).upload(np.full(B, T - skip, np.int32))
             if hypo:      # one device set (upload and kernel of a batch are consecutive on the output stream), two pinned ones
                 hspec = [(hshape, np.int32), (hshape[:2], np.int32)]
@@ -1178,7 +1187,7 @@ class Engine:
             src = lambda o: (lring[o],) + dscore
         else:
             pins = bufs((name, "pinned", shapes), lambda: sets(2, dev.pinned, [sh for sh in shapes if sh is not None]))
-            src = lambda o: [d for d in dring[o % len(dring)] if d is not None]     # (the one set, or "align"'s set of slot o)
+            src = lambda o: [d for d in dring[o % len(dring)] if d is not None]     # (the one set, or the set of slot o)
 
         spin = bufs("status16", lambda: [dev.pinned((16,), np.uint32) for _ in range(2)])
 
@@ -1293,18 +1302,18 @@ class Engine:
                 dev.wait_event(0, self.EV_OUT[o])               # batch i - 2's decode / download read the P buffer this pass overwrites
                 if labelled:
                     self._upload_labels(item[1], item[2], item[3])
-                if output == "align":
+                if output in self.ALIGNED:
                     host_labels[i] = (self._lab_pin[self._lab_slot][0].copy(), np.asarray(item[3]).reshape(B).astype(np.int32))
                 self.P = pring[o]
                 self._bind(self._pass_status[o])        # (batch i + 1's encoder pass, enqueued above, bound the other block)
                 self._enqueue_fusion_head(train_phase, None, ring[f], self.rng_step + (i - started[0]))
                 dev.stream(0)
-                if output == "align":
+                if output in self.ALIGNED:
                     op.launch(dev, self.P, self.ilen_d, dring[o], tables, ws, self.labels_d, self.llen_d)
                 elif labelled:
                     dev.call("mgr_ctc_loss_grad", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1,
                              eps, 1.0, lring[o], 0, self.ws_ctc, self.ws_ctc.nbytes)
-                if output in ("loss", "align"):       # ("score" reads the labels again on the output stream below)
+                if output in ("loss",) + self.ALIGNED:       # ("score" reads the labels again on the output stream below)
                     dev.record(self.EV_LAB[self._lab_slot])
                     self._lab_user[self._lab_slot] = 1 << 60
                 dev.record(self.EV_FUSED[f])
@@ -1322,7 +1331,7 @@ class Engine:
                     op.launch(dev, pring[o], dil, dring[0], tables, ws, *dhyp)
                 elif output == "sample":
                     op.launch(dev, pring[o], dil, dring[0], tables, ws, seed=int(sample_seed) + i)
-                elif op is not None and output != "align":
+                elif op is not None and output not in self.ALIGNED:
                     op.launch(dev, pring[o], dil, dring[0], tables, ws)
                 if output == "score":
                     dev.call("mgr_edit_distance", dring[0][op.hyp[0]], dring[0][op.hyp[1]], B, T - skip, self.labels_d, self.llen_d, B, self.Lmax,

@@ -686,12 +686,20 @@ class Model:
         logp, n_lab = (np.concatenate(m, axis=0) for m in zip(*outs))
         return (logp, n_lab) if return_counts else logp
 
-    def align_generator(self, generator, steps, return_path=False):
+    def align_generator(self, generator, steps, return_path=False, mode="viterbi", quantile=0.5):
         """Forced alignment over `steps` batches of a training generator (inputs with the_labels / input_length / label_length, as
         fit_generator takes them), pipelined like evaluate_generator: per sample the most probable CTC alignment of ITS labels to the
         network's posteriors for it - decoding.forced_align of predict_generator's output, without the posteriors leaving the device.
         Returns (segments, logp[, path]): per sample a list of (label, first_frame, last_frame, confidence), the paths' natural-log
-        probabilities (N,) float64, and with return_path the frame paths (N, T - skip) int32."""
+        probabilities (N,) float64, and with return_path the frame paths (N, T - skip) int32.
+        mode="posterior": mgr_ctc_occupancy where "viterbi" runs mgr_ctc_align, in the same pipelined pass - decoding.posterior_align of
+        predict_generator's output at `quantile`, bit for bit: the segments are (label, first_frame, last_frame, confidence, occupancy),
+        logp is the labels' log-likelihood over all alignments (-loss); there are no frame paths to return."""
+        if mode not in ("viterbi", "posterior"):
+            raise ValueError("unknown mode %r" % (mode,))
+        posterior = mode == "posterior"
+        if posterior and return_path:
+            raise ValueError("mode='posterior' has no frame path")
         steps = int(steps)
         if steps <= 0:
             return ([], np.zeros((0,))) + ((np.zeros((0, 0), np.int32),) if return_path else ())
@@ -716,11 +724,13 @@ class Model:
                 yield ins, lab, il, ll
 
         segs, logps, paths = [], [], []
-        for i, (sg, lp, pa) in enumerate(e.predict_stream(feed(), output="align", train_phase=bool(learning_phase()))):
+        stream = e.predict_stream(feed(), output="occupancy" if posterior else "align", train_phase=bool(learning_phase()), quantile=quantile)
+        for i, res in enumerate(stream):
             n = counts[i]
-            segs += sg[:n]
-            logps.append(lp[:n])
-            paths.append(pa[:n])
+            segs += res[0][:n]
+            logps.append(res[1][:n])
+            if not posterior:
+                paths.append(res[2][:n])
         out = (segs, np.concatenate(logps, axis=0))
         return out + (np.concatenate(paths, axis=0),) if return_path else out
 

@@ -3,7 +3,7 @@ the reference's confidence threshold is commented out, so none applies - over th
 MLF writer with the ten-file ignore list."""
 import numpy as np
 
-from ..decoding import HTK_COSTS, confidence_filter_collapse, decode_beam_mlf, decode_samples_map, decode_score_map, expected_risk_map, greedy_segments, write_mlf
+from ..decoding import HTK_COSTS, confidence_filter_collapse, decode_beam_mlf, decode_extents_mlf, decode_samples_map, decode_score_map, expected_risk_map, greedy_segments, write_mlf
 from ..keras_like import Model
 from ..multimodal_fusion.sequence_decoding import ignore_list, map_gest  # noqa: F401  (the same 22 names and ignore list)
 from .cnn_lstm import load_model as _load_model
@@ -39,6 +39,15 @@ def decode_segments(pred_out, f_list, out_file="ctc_recout_timed.mlf"):
     if out_file is not None:
         write_mlf(out_file, ret, nums, ignore_list, "Sample%05d", segments=segs)
     return ret, segs
+
+
+def decode_extents(pred_out, f_list, quantile=0.5, out_file="ctc_recout_extents.mlf"):
+    """decode_segments with extents in place of spikes: the best-path decode (no confidence filter, as decode_batch here)
+    gives each file's gesture sequence (blank runs dropped), decoding.posterior_align its posterior extents - at quantile 0.5 the
+    median extent, near the frames decode_segments reports; a smaller quantile widens them to credible extents, which may overlap.
+    Returns (label-name lists, segment lists of (label, first_frame, last_frame, confidence, occupancy))."""
+    nums = [int(str(f)[6:11]) if not isinstance(f, (int, np.integer)) else int(f) for f in f_list]
+    return decode_extents_mlf(pred_out, nums, map_gest, ignore_list, "Sample%05d", out_file, None, quantile=quantile)
 
 
 def decode_beam(pred_out, f_list, lm=None, lm_end=None, alpha=1.0, beta=0.0, beam_width=10, top_paths=1, out_file="ctc_recout_beam.mlf"):
