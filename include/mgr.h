@@ -483,6 +483,24 @@ size_t mgr_ctc_ws_bytes(int B, int T, int C, int Lmax);
 int mgr_ctc_loss_grad(mgr_ctx* ctx, const float* P, const int32_t* labels, const int32_t* input_len,
                       const int32_t* label_len, int B, int T, int C, int Lmax, int skip, int blank, float eps,
                       float gscale, float* loss, float* dLogits, void* ws, size_t ws_bytes);
+/* Entropy-regularised CTC (Liu et al., NeurIPS 2018): the loss and, beside it, the entropy H_b = -sum_pi q(pi) ln q(pi) of the
+ * distribution q(pi) = p(pi) / p(labels | x) over the feasible alignments pi of sample b's labels, in nats, with the gradient of
+ * loss_scale * loss - ent_scale * H.  Conventions, clipping of out-of-range arguments and edge cases are K6's, argument for argument.
+ *   loss    [B]: the bits mgr_ctc_loss_grad writes.
+ *   entropy [B]: H = ln p(labels | x) - E_q[ln p(pi)] >= 0; 0 for label_len 0 (one alignment).
+ *   dLogits [B,T,C] (may be NULL: the two values only) = loss_scale * dloss_b/dlogits - ent_scale * dH_b/dlogits, overwritten, zero on
+ *           dropped / out-of-length frames.  ent_scale == 0 skips the entropy term: dLogits is then mgr_ctc_loss_grad's with gscale =
+ *           loss_scale, bit for bit (entropy is still written).
+ * A label sequence that does not fit its input, or an input length of 0: loss = +inf, entropy = 0 and a zero gradient for that sample
+ * alone.  Lmax <= 255.  Deterministic; samples are independent of each other; no atomics.
+ * Workspace: ws_bytes >= 2 * mgr_ctc_ws_bytes(B, T, C, Lmax) - there is no query of its own.  The first half is the loss's layout
+ * (emissions, alpha, beta); the second half holds two more rows of alpha's size and format, the entropy of the prefixes into a state
+ * beside alpha and of the suffixes out of it beside beta.  With dLogits == NULL or ent_scale == 0 the first half is left as
+ * mgr_ctc_loss_grad leaves it; otherwise its alpha and beta rows hold each state's value relative to the frame's largest, with what the
+ * float32 recursion rounded away put back - the same occupancies, more digits of them.  Device time: profiling family MGR_K_CTC. */
+int mgr_ctc_entropy_grad(mgr_ctx* ctx, const float* P, const int32_t* labels, const int32_t* input_len, const int32_t* label_len, int B,
+                         int T, int C, int Lmax, int skip, int blank, float eps, float loss_scale, float ent_scale, float* loss,
+                         float* entropy, float* dLogits, void* ws, size_t ws_bytes);
 
 /* ---- K7: Adam(clipvalue) + maxnorm (multimodal_fusion/multimodal.py:159-168,206-213) ---------------- */
 /* g' = clip(g*gscale, +-clipvalue) (clipvalue<=0: no clip); m,v,p Keras-Adam update with step size lr_t. */

@@ -109,6 +109,7 @@ SIGNATURES = {
                                vp, vp, vp, vp, vp, vp, vp, i32, vp, sz]),
     "mgr_ctc_ws_bytes": (sz, [i32, i32, i32, i32]),
     "mgr_ctc_loss_grad": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, sz]),
+    "mgr_ctc_entropy_grad": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, sz]),
     "mgr_adam_step": (i32, [vp, vp, vp, vp, vp, sz, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     "mgr_maxnorm_cols": (i32, [vp, vp, i32, i32, C.c_float, C.c_float]),
     "mgr_add2d": (i32, [vp, vp, i32, vp, i32, vp, i32, sz, i32]),

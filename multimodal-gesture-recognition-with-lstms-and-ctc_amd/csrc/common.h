@@ -21,6 +21,7 @@ enum : unsigned {
   MGR_ATTR_CTC = 128u, MGR_ATTR_ALIGN = 512u, MGR_ATTR_SEGMENTS = 1024u, MGR_ATTR_ROI = 256u,      // ctc.hip, align.hip (two), roi.hip
   MGR_ATTR_LEXICON = 4096u, MGR_ATTR_RISK = 8192u,                                                 // lexicon.hip, risk.hip
   MGR_ATTR_OVERLAP = 16384u,                                                                       // overlap.hip
+  MGR_ATTR_CTC_ENT = 32768u,                                                                       // ctc.hip: the entropy call's variants
 };
 
 struct mgr_ctx {

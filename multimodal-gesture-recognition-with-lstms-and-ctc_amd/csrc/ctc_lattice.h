@@ -176,6 +176,149 @@ __device__ __forceinline__ void alpha_step(const Pairs<PPL>& pr, float (&ab)[PPL
   }
 }
 
+// ---- the entropy of the paths into a state, carried beside alpha / beta -------------------------------------------------
+
+// lse2 / lse3 that also hand out their maximum, their terms 2^(x - m), the terms' sum and its logarithm: the operations of lse2 / lse3
+// in their order, so the same bits.
+__device__ __forceinline__ float lse2_terms(float a, float b, float& m, float& ea, float& eb, float& s, float& lg) {
+  m = fmaxf(fmaxf(a, b), kLseFloor);
+  ea = exp2_raw(a - m);
+  eb = exp2_raw(b - m);
+  s = ea + eb;
+  lg = log2_raw(s);
+  return m + lg;
+}
+__device__ __forceinline__ float lse3_terms(float a, float b, float c, float& m, float& ea, float& eb, float& ec, float& s, float& lg) {
+  m = fmaxf(fmaxf(fmaxf(a, b), c), kLseFloor);
+  ea = exp2_raw(a - m);
+  eb = exp2_raw(b - m);
+  ec = exp2_raw(c - m);
+  s = ea + eb + ec;
+  lg = log2_raw(s);
+  return m + lg;
+}
+// The chain rule of the entropy over one log-sum-exp: with predecessors r of log-weight x_r, w_r = 2^(x_r - m) / s, and h_r the entropy
+// (base 2) of the paths into r,  h = sum_r w_r h_r - sum_r w_r log2 w_r = log2 s + sum_r w_r (h_r - (x_r - m)).  A predecessor of
+// weight 0 (log 0) is left out by SELECTION: its x_r - m is -inf, and 0 * -inf is not 0.  s = 0 (every predecessor dead): the caller selects the result away.
+// With d_r what the float32 recursion has rounded away from x_r (below), the weights that belong to the exact recursion are those of
+// x_r + d_r: to first order w_r (1 + ln 2 (d_r - D)), D = sum_r w_r d_r, with log2 of their normaliser log2 s + D.  The chain rule is
+// taken over THOSE weights - at |alpha| = 1600 neighbouring d differ by 1e-4, and weights off by that much leave as much in h at every
+// step.  D: the caller's sum_r w_r d_r.
+__device__ __forceinline__ float ent_term(float e, float h, float x, float m, float d, float D) {
+  return e > 0.f ? e * (1.f + (float)kLn2 * (d - D)) * ((h - d) - (x - m)) : 0.f;
+}
+__device__ __forceinline__ float ent_chain2(float m, float s, float lg, float D, float ea, float ha, float xa, float da, float eb, float hb,
+                                            float xb, float db) {
+  return (lg + D) + (ent_term(ea, ha, xa, m, da, D) + ent_term(eb, hb, xb, m, db, D)) * __builtin_amdgcn_rcpf(s);
+}
+__device__ __forceinline__ float ent_chain3(float m, float s, float lg, float D, float ea, float ha, float xa, float da, float eb, float hb,
+                                            float xb, float db, float ec, float hc, float xc, float dc) {
+  return (lg + D) + (ent_term(ea, ha, xa, m, da, D) + ent_term(eb, hb, xb, m, db, D) + ent_term(ec, hc, xc, m, dc, D)) * __builtin_amdgcn_rcpf(s);
+}
+// (a + b) - fl(a + b) exactly (Knuth's two-sum; s = fl(a + b)).  Not finite where an operand is not: the callers select such results away.
+__device__ __forceinline__ float add_err(float a, float b, float s) {
+  const float bv = s - a;
+  return (a - (s - bv)) + (b - bv);
+}
+// sum_r (e_r / s) x_r, a term of weight 0 left out by selection (its x_r may not be finite)
+__device__ __forceinline__ float wsel(float e, float x) { return e > 0.f ? e * x : 0.f; }
+
+// alpha_step with two more values per state:
+//   h(t, s)  the entropy of the distribution over the prefixes that end in s at t, i.e. log2 alpha(t, s) minus the expected
+//            log2-probability of such a prefix (the chain rule above).  h >= 0 grows by what the alignments add, not per frame: it needs
+//            no renormalisation and no offset;
+//   d(t, s)  what the float32 additions of the alpha recursion have rounded away on the way into s: alpha + d is, to first order, the
+//            recursion's value had its additions been exact - d = sum_r w_r d_r + the two-sum errors of the step's own two additions.
+// alpha's own operations are alpha_step's (the same bits); a dead state (alpha = log 0) keeps h = d = 0, so every stored value is finite.
+template <int PPL>
+__device__ __forceinline__ void alpha_step_ent(const Pairs<PPL>& pr, float (&ab)[PPL], float (&al)[PPL], float (&hb)[PPL], float (&hl)[PPL],
+                                               float (&db)[PPL], float (&dl)[PPL], float eb, const float (&el)[PPL]) {
+  const float carry = dpp_f32<DPP_WAVE_SHR1>(al[PPL - 1], kNegInf);   // (lane 0: log 0)
+  const float hcarry = dpp_f32<DPP_WAVE_SHR1>(hl[PPL - 1], 0.f);
+  const float dcarry = dpp_f32<DPP_WAVE_SHR1>(dl[PPL - 1], 0.f);
+  float nb[PPL], nl[PPL], nhb[PPL], nhl[PPL], ndb[PPL], ndl[PPL];
+#pragma unroll
+  for (int j = 0; j < PPL; ++j) {
+    const float up = (j > 0) ? al[j - 1] : carry;
+    const float hup = (j > 0) ? hl[j - 1] : hcarry;
+    const float dup = (j > 0) ? dl[j - 1] : dcarry;
+    const float skp = pr.cs[j] ? up : kNegInf;
+    float m, e0, e1, e2, s, lg;
+    {
+      const float lb = lse2_terms(ab[j], up, m, e0, e1, s, lg);
+      const float v = eb + lb;
+      nb[j] = pr.vb[j] ? v : kNegInf;
+      const bool dead = nb[j] == kNegInf;
+      const float D = (wsel(e0, db[j]) + wsel(e1, dup)) * __builtin_amdgcn_rcpf(s);
+      nhb[j] = dead ? 0.f : ent_chain2(m, s, lg, D, e0, hb[j], ab[j], db[j], e1, hup, up, dup);
+      ndb[j] = dead ? 0.f : D + (add_err(m, lg, lb) + add_err(eb, lb, v));
+    }
+    {
+      const float ll = lse3_terms(al[j], ab[j], skp, m, e0, e1, e2, s, lg);
+      const float v = el[j] + ll;
+      nl[j] = pr.vl[j] ? v : kNegInf;
+      const bool dead = nl[j] == kNegInf;
+      const float D = (wsel(e0, dl[j]) + wsel(e1, db[j]) + wsel(e2, dup)) * __builtin_amdgcn_rcpf(s);
+      nhl[j] = dead ? 0.f : ent_chain3(m, s, lg, D, e0, hl[j], al[j], dl[j], e1, hb[j], ab[j], db[j], e2, hup, skp, dup);
+      ndl[j] = dead ? 0.f : D + (add_err(m, lg, ll) + add_err(el[j], ll, v));
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < PPL; ++j) {
+    ab[j] = nb[j];
+    al[j] = nl[j];
+    hb[j] = nhb[j];
+    hl[j] = nhl[j];
+    db[j] = ndb[j];
+    dl[j] = ndl[j];
+  }
+}
+
+// renorm that also adds what its subtraction rounds away to d (nothing on dead states): the same wave-wide maximum, the same
+// subtraction, the same bits in ab / al.
+template <int PPL>
+__device__ __forceinline__ float renorm_ent(float (&ab)[PPL], float (&al)[PPL], float (&db)[PPL], float (&dl)[PPL]) {
+  float m = kNegInf;
+#pragma unroll
+  for (int j = 0; j < PPL; ++j) m = fmaxf(m, fmaxf(ab[j], al[j]));
+  m = wave_max_f32(m);
+  if (m == kNegInf) return 0.f;
+#pragma unroll
+  for (int j = 0; j < PPL; ++j) {
+    const float vb = ab[j] - m, vl = al[j] - m;
+    if (ab[j] != kNegInf) db[j] += add_err(ab[j], -m, vb);
+    if (al[j] != kNegInf) dl[j] += add_err(al[j], -m, vl);
+    ab[j] = vb;
+    al[j] = vl;
+  }
+  return m;
+}
+
+// What the entropy's gradient kernel reads in alpha's (beta's) rows when rel is set (wave-uniform): the state's value relative to the
+// step's wave-wide maximum with d put back, (v - max) + d - small for every state that matters, so that neither its own float32
+// rounding nor the recursion's is left in it.  A constant of the frame is of no account there: occupancies are normalised per frame,
+// and only differences between states enter the entropy's gradient.  rel off: v itself, the loss's rows.
+template <int PPL>
+__device__ __forceinline__ void ent_rows(bool rel, const float (&vb)[PPL], const float (&vl)[PPL], const float (&db)[PPL], const float (&dl)[PPL],
+                                         float (&sb)[PPL], float (&sl)[PPL]) {
+#pragma unroll
+  for (int j = 0; j < PPL; ++j) {
+    sb[j] = vb[j];
+    sl[j] = vl[j];
+  }
+  if (!rel) return;
+  float m = kNegInf;
+#pragma unroll
+  for (int j = 0; j < PPL; ++j) m = fmaxf(m, fmaxf(vb[j], vl[j]));
+  m = wave_max_f32(m);
+  if (m == kNegInf) return;
+#pragma unroll
+  for (int j = 0; j < PPL; ++j) {
+    sb[j] = (vb[j] - m) + db[j];   // (a dead state: -inf + 0)
+    sl[j] = (vl[j] - m) + dl[j];
+  }
+}
+
 // ---- emissions -------------------------------------------------------------------------------------------------------------------
 
 template <bool BASE2>

@@ -165,6 +165,24 @@ def occupancy_op(n_classes, skip, quantile=0.5, return_gamma=False, eps=1e-8):
     return DecodeOp("occupancy", outputs, launch, result, ws_bytes=lambda lib, N, T, Lmax: lib.mgr_ctc_ws_bytes(N, T, Cn, Lmax), uses_len=True)
 
 
+def entropy_op(n_classes, skip, grad=False, eps=1e-8):
+    """mgr_ctc_entropy_grad as a measurement: the entropy of the labels' alignments and logp, with grad also dH/dlogits
+    (loss_scale 0, ent_scale -1: the call writes loss_scale dloss - ent_scale dH).  Its workspace is twice the loss's."""
+    Cn = int(n_classes)
+
+    def outputs(N, T, Lmax):
+        return (_f32(N), _f32(N), _f32(N, T, Cn) if grad else None)
+
+    def launch(dev, P, input_len, outs, tables, ws, labels, label_len):
+        dev.call("mgr_ctc_entropy_grad", P, labels, input_len, label_len, P.shape[0], P.shape[1], Cn, labels.shape[1], skip, Cn - 1,
+                 C.c_float(eps), C.c_float(0.0), C.c_float(-1.0), *outs, ws, ws.nbytes)
+
+    def result(*arrays):
+        loss, H = arrays[0], arrays[1]
+        return (H, -loss.astype(np.float64)) + ((arrays[2],) if grad else ())
+    return DecodeOp("entropy", outputs, launch, result, ws_bytes=lambda lib, N, T, Lmax: 2 * lib.mgr_ctc_ws_bytes(N, T, Cn, Lmax), uses_len=True)
+
+
 def rescore_op(n_classes, skip, lexicon=None, eps=1e-8):
     """mgr_ctc_rescore (K14): the hypothesis arrays (hyp (N, K, Lh), hyp_len (N, K)) travel where align passes its labels, so the
     `Lmax` the description's functions get is K."""
@@ -377,6 +395,23 @@ def posterior_align(pred_out, labels, label_length=None, input_length=None, quan
     if lab.shape[0] != P.shape[0]:
         raise ValueError("%d label rows for %d samples" % (lab.shape[0], P.shape[0]))
     return _run(occupancy_op(P.shape[2], skip, quantile, return_gamma, eps), P, skip, dev, input_length, (lab, ll))
+
+
+def alignment_entropy(pred_out, labels, label_length=None, input_length=None, skip=2, eps=1e-8, grad=False, dev=None):
+    """The entropy of the distribution over the CTC alignments of each sample's labels, on the GPU (mgr_ctc_entropy_grad):
+    H = - sum_pi q(pi) ln q(pi) in nats, q(pi) = p(pi) / p(labels | posteriors) over the feasible alignments pi, under the loss's
+    conventions (frames skip .., y = softmax(log(P + eps)), blank = C - 1).  It is the quantity entropy-regularised CTC training
+    (Engine.set_entropy) raises, and a per-sample measure of how far posterior_align's extents can be trusted: H near 0 means one
+    alignment holds all of p(labels | x) - the posteriors are peaky and every quantile gives the Viterbi spikes -, a larger H that the
+    extents average over alignments that really differ.
+    Returns (H, logp[, dH/dlogits]): H (N,) float32 (0 without labels, and where the labels do not fit), logp (N,) float64 = -loss
+    (-inf where they do not fit), dH/dlogits (N, T, C) float32 with respect to the logits behind the posteriors (grad=True; zero on
+    dropped and out-of-length frames)."""
+    P = _posteriors(pred_out)
+    lab, ll = pack_labels(labels, label_length)
+    if lab.shape[0] != P.shape[0]:
+        raise ValueError("%d label rows for %d samples" % (lab.shape[0], P.shape[0]))
+    return _run(entropy_op(P.shape[2], skip, grad, eps), P, skip, dev, input_length, (lab, ll))
 
 
 def beam_search_decode(pred_out, input_length=None, beam_width=10, skip=2, merge_repeated=True, dev=None, blank=None):

@@ -207,6 +207,7 @@ class Engine:
         self._adam_calls = 0  # optimizer steps enqueued; `iterations` (Keras) = those the update gate did not skip
         self.rng_step = 0     # advances per forward pass that draws randomness
         self._risk = None     # set_risk: the minimum-risk training mode's settings and buffers
+        self._entropy = None  # set_entropy: the entropy-regularised training mode's weight and buffers
         self._build()
 
     # ------------------------------------------------------------------------------------------ build
@@ -1424,8 +1425,11 @@ class Engine:
         dev = self.dev
         dev.event_sync(self.EV_LOSS)
         v = float(self.loss_host[0])
-        self.last_risk = self.last_ctc_loss = None
-        if self._loss_parts is not None:      # a minimum-risk step: [0] the mean CTC loss (0 where it was not computed), [1] the mean risk
+        self.last_risk = self.last_ctc_loss = self.last_entropy = None
+        if isinstance(self._loss_parts, tuple):      # an entropy-regularised step: [0] the mean CTC loss, [1] the mean entropy
+            self.last_ctc_loss, self.last_entropy = v, float(self.loss_host[1])
+            v = self.last_ctc_loss - self._loss_parts[1] * self.last_entropy
+        elif self._loss_parts is not None:    # a minimum-risk step: [0] the mean CTC loss (0 where it was not computed), [1] the mean risk
             self.last_ctc_loss, self.last_risk = v, float(self.loss_host[1])
             v = self.last_risk + self._loss_parts * self.last_ctc_loss
         step = self._step_id - 1
@@ -1668,6 +1672,8 @@ class Engine:
         if cfg is None:
             self._release_risk()
             return
+        if self._entropy is not None:
+            raise ValueError("set_risk with the entropy mode on: the two training modes are not combined (set_entropy(None) first)")
         if self.comm is not None:
             raise NotImplementedError("minimum-risk training is single-GPU: data-parallel risk training is not implemented")
         if self.inference_only:
@@ -1751,6 +1757,60 @@ class Engine:
         dev.call("mgr_dense_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self.dLogits, self._wview("dense/W"), self._gview("dense/W"),
                  self._gview("dense/b"), dA, ldda, B, T, D, Cn, self.ws_dense, self.ws_dense.nbytes)
 
+    ENTROPY_DEFAULTS = dict(weight=0.2)
+    last_entropy = None
+
+    def set_entropy(self, cfg):
+        """Entropy-regularised CTC training (Liu et al., NeurIPS 2018): with cfg - a dict over ENTROPY_DEFAULTS - the training
+        loss is ctc - weight * H, H the entropy of the distribution over the alignments of each sample's labels, which keeps the network
+        from putting all of p(labels | x) on one alignment.  The head of a step is then the separate calls mgr_head_fwd_bwd equals, with
+        mgr_ctc_entropy_grad (scales 1 / B and weight / B) in the loss's place: mgr_dense_softmax_fwd, mgr_ctc_entropy_grad, the two means,
+        mgr_dense_bwd.  read_loss returns the combined loss and leaves the parts in last_ctc_loss / last_entropy.  None: back to the one
+        mgr_head_fwd_bwd call; the mode's buffers are freed.  Not combined with set_risk; single GPU.  A cfg that is refused leaves the
+        mode as it was; the loss of a step enqueued before the call is still read as that step's."""
+        if cfg is None:
+            self._release_entropy()
+            return
+        if self.comm is not None:
+            raise NotImplementedError("entropy-regularised training is single-GPU: data-parallel entropy training is not implemented")
+        if self.inference_only:
+            raise ValueError("set_entropy on an inference-only engine")
+        if self._risk is not None:
+            raise ValueError("set_entropy with the risk mode on: the two training modes are not combined (set_risk(None) first)")
+        unknown = set(cfg) - set(self.ENTROPY_DEFAULTS)
+        if unknown:
+            raise ValueError("unknown entropy settings %s (known: %s)" % (sorted(unknown), sorted(self.ENTROPY_DEFAULTS)))
+        cfg = dict(self.ENTROPY_DEFAULTS, **cfg)
+        weight = float(cfg["weight"])
+        if not weight >= 0.0 or not np.isfinite(weight):
+            raise ValueError("weight >= 0, got %r" % (cfg["weight"],))
+        self._release_entropy()
+        dev = self.mem          # (the engine's arena: freed with it, or at set_entropy(None))
+        B, T, Cn = self.B, self.T, self.spec.num_classes
+        e = dict(cfg=dict(weight=weight), H=dev.empty((B,), np.float32), ws=dev.bytes(2 * self.lib.mgr_ctc_ws_bytes(B, T, Cn, self.Lmax)))
+        e["bufs"] = [v for v in e.values() if isinstance(v, DeviceArray)]
+        self._entropy = e
+
+    def _release_entropy(self):
+        if self._entropy is not None:
+            self.dev.sync()     # (a step that uses the buffers may be in flight)
+            self.mem.release(self._entropy["bufs"])
+            self._entropy = None
+
+    def _enqueue_entropy_head(self, feat, ldf, hm, p_head, hseed, dA, ldda):
+        """The head of an entropy-regularised step on the current stream (set_entropy): Dropout / Dense / softmax, the CTC loss and the
+        alignment entropy with the gradient of (loss - weight H) / B, the two means, Dense backward."""
+        sp, dev, B, T, e = self.spec, self.dev, self.B, self.T, self._entropy
+        Cn, D, skip, eps = sp.num_classes, sp.head_width, int(sp.ctc["skip"]), float(sp.ctc["eps"])
+        dev.call("mgr_dense_softmax_fwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self._wview("dense/W"), self._wview("dense/b"), self.P,
+                 B, T, D, Cn)
+        dev.call("mgr_ctc_entropy_grad", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1, eps, 1.0 / B,
+                 e["cfg"]["weight"] / B, self.loss_b, e["H"], self.dLogits, e["ws"], e["ws"].nbytes)
+        dev.call("mgr_mean", self.loss_b, B, self.loss_mean)
+        dev.call("mgr_mean", e["H"], B, self.loss_mean.view(1, (1,)))
+        dev.call("mgr_dense_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self.dLogits, self._wview("dense/W"), self._gview("dense/W"),
+                 self._gview("dense/b"), dA, ldda, B, T, D, Cn, self.ws_dense, self.ws_dense.nbytes)
+
     def _enqueue_trainable_part(self, cur, rand, beside_scans, defer, late_ok, own_inputs, apply_update):
         """Steps 2 and 3 of a training step on stream 0 - fusion layer, head, CTC, the loss read-back point, the backward pass up to
         what `defer` / `late_ok` hold back - and the closure `finish(gate=None)` that enqueues the rest (held-back BPTT, dW / dU / db
@@ -1781,12 +1841,16 @@ class Engine:
         with self._tuned(self._gate_words[0] is not None or self._gate_words[1] is not None, ctc_lds, keep_set=True):
             if self._risk is not None:
                 self._enqueue_risk_head(feat, ldf, hm, p_head, hseed, dA, ldda)
+            elif self._entropy is not None:
+                self._enqueue_entropy_head(feat, ldf, hm, p_head, hseed, dA, ldda)
             else:
                 dev.call("mgr_head_fwd_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self._wview("dense/W"), self._wview("dense/b"),
                          self.labels_d, self.ilen_d, self.llen_d, B, T, D, Cn, self.Lmax, int(sp.ctc["skip"]), Cn - 1, float(sp.ctc["eps"]),
                          1.0 / B, self.P, self.loss_b, self.loss_mean, self.dLogits, self._gview("dense/W"), self._gview("dense/b"),
                          dA, ldda, self.ws_head, self.ws_head.nbytes)
         self._loss_parts = None if self._risk is None else float(self._risk["cfg"]["ctc_weight"])
+        if self._entropy is not None:      # (an entropy-regularised step; never together with the risk mode)
+            self._loss_parts = ("entropy", float(self._entropy["cfg"]["weight"]))
         if self.comm is not None:
             dev.call("mgr_mean", self.loss_b, B, self.loss_slot)   # travels with the gradient all-reduce (apply_gradients)
         dev.record(self.EV_LAB[self._lab_slot])

@@ -213,7 +213,9 @@ class Model:
         self._engine = None
         self._weights = None      # host copy (Keras layouts) until an engine exists
         self._risk = None         # set_risk: the minimum-risk training mode's settings (carried over when the engine is rebuilt)
-        self.last_logs = {}       # train_on_batch: the scalars of its step ("loss"; with set_risk also "risk" and "ctc_loss")
+        self._entropy = None      # set_entropy: the entropy-regularised training mode's settings (carried over likewise)
+        self.last_logs = {}       # train_on_batch: the scalars of its step ("loss"; with set_risk also "risk" and "ctc_loss", with
+                                  # set_entropy "ctc_loss" and "entropy")
         self._predict_view = False
         self._shared = None
         self.optimizer = None
@@ -384,6 +386,8 @@ class Model:
             self._engine.spec = self.spec
         if "risk" in kwargs:
             self.set_risk(kwargs["risk"])
+        if "entropy" in kwargs:
+            self.set_entropy(kwargs["entropy"])
 
     def set_risk(self, cfg):
         """Minimum-risk fine-tuning of a CTC-trained network (Engine.set_risk): cfg = dict(top_paths=8, beam_width=16,
@@ -394,9 +398,30 @@ class Model:
         9o).  None: plain CTC training again.  Single GPU only."""
         if cfg is not None and self.comm is not None:
             raise NotImplementedError("minimum-risk training is single-GPU: data-parallel risk training is not implemented")
+        if cfg is not None and self._entropy is not None:
+            raise ValueError("set_risk with the entropy mode on: the two training modes are not combined (set_entropy(None) first)")
         if self._engine is not None and not self._engine.inference_only:
             self._engine.set_risk(None if cfg is None else dict(cfg))      # (a cfg the engine refuses leaves the mode as it was)
         self._risk = None if cfg is None else dict(cfg)
+
+    def set_entropy(self, cfg):
+        """Entropy-regularised CTC training (Engine.set_entropy): cfg = dict(weight=0.2) or {} - the training loss becomes
+        the CTC loss - weight x the entropy of the distribution over the alignments of each sample's labels, which keeps the posteriors
+        from collapsing onto one alignment (what posterior_align's extents suffer from); train_on_batch leaves the parts in last_logs
+        ("loss", "ctc_loss", "entropy"), fit_generator logs their epoch means.  None: plain CTC training again.  Not combined with
+        set_risk; single GPU only."""
+        if cfg is not None and self.comm is not None:
+            raise NotImplementedError("entropy-regularised training is single-GPU: data-parallel entropy training is not implemented")
+        if cfg is not None and self._risk is not None:
+            raise ValueError("set_entropy with the risk mode on: the two training modes are not combined (set_risk(None) first)")
+        if cfg is not None:
+            from .engine import Engine
+            unknown = set(cfg) - set(Engine.ENTROPY_DEFAULTS)
+            if unknown or not float(dict(Engine.ENTROPY_DEFAULTS, **cfg)["weight"]) >= 0.0:
+                raise ValueError("entropy settings %r: dict(weight >= 0) (known: %s)" % (cfg, sorted(Engine.ENTROPY_DEFAULTS)))
+        if self._engine is not None and not self._engine.inference_only:
+            self._engine.set_entropy(None if cfg is None else dict(cfg))      # (a cfg the engine refuses leaves the mode as it was)
+        self._entropy = None if cfg is None else dict(cfg)
 
     def distribute(self, comm, world):
         """Attach a data-parallel communicator (mgr_amd.parallel.RcclComm / HostComm) before the first batch.  The engine is
@@ -406,6 +431,8 @@ class Model:
             raise RuntimeError("distribute() must be called before the first batch")
         if self._risk is not None:
             raise NotImplementedError("minimum-risk training is single-GPU: data-parallel risk training is not implemented")
+        if self._entropy is not None:
+            raise NotImplementedError("entropy-regularised training is single-GPU: data-parallel entropy training is not implemented")
         self.comm, self.world = comm, int(world)
         if getattr(comm, "dev", None) is not None:
             self.device = comm.dev
@@ -427,6 +454,8 @@ class Model:
         self._engine.set_weights(w)
         if self._risk is not None and not inference_only:
             self._engine.set_risk(self._risk)
+        if self._entropy is not None and not inference_only:
+            self._engine.set_entropy(self._entropy)
         if opt_state is not None and not inference_only:
             self._engine.m.upload(opt_state[0])
             self._engine.v.upload(opt_state[1])
@@ -469,6 +498,8 @@ class Model:
             self.last_logs = {"loss": loss}
             if e.last_risk is not None:      # (a minimum-risk step: set_risk)
                 self.last_logs.update(risk=e.last_risk, ctc_loss=e.last_ctc_loss)
+            elif e.last_entropy is not None:   # (an entropy-regularised step: set_entropy)
+                self.last_logs.update(ctc_loss=e.last_ctc_loss, entropy=e.last_entropy)
             return loss
         # fit_generator, world > 1: the global loss arrives with the gradient all-reduce at the END of the step; waiting for it
         # here would leave the device idle while the host assembles the next batch - pace on the local loss, collect the global
@@ -534,7 +565,7 @@ class Model:
             for cb in callbacks:
                 if hasattr(cb, "on_epoch_begin"):
                     cb.on_epoch_begin(epoch, {})
-            losses, parts = [], []
+            losses, parts, eparts = [], [], []
             lagged = self.world > 1 and self.comm is not None
             owed = None       # (data parallel) id of the step whose global loss has not been collected yet
             skipped0 = self._engine.updates_skipped if self._engine is not None else 0
@@ -554,11 +585,15 @@ class Model:
                     losses.append(r)
                     if "risk" in self.last_logs:
                         parts.append((self.last_logs["risk"], self.last_logs["ctc_loss"]))
+                    elif "entropy" in self.last_logs:
+                        eparts.append((self.last_logs["ctc_loss"], self.last_logs["entropy"]))
             if owed is not None:
                 losses.append(self._engine.read_global_loss(owed))
             logs = {"loss": float(np.mean(losses)) if losses else float("nan")}
             if parts:       # (minimum-risk training: set_risk)
                 logs.update(risk=float(np.mean([p[0] for p in parts])), ctc_loss=float(np.mean([p[1] for p in parts])))
+            if eparts:      # (entropy-regularised training: set_entropy)
+                logs.update(ctc_loss=float(np.mean([p[0] for p in eparts])), entropy=float(np.mean([p[1] for p in eparts])))
             if self._engine is not None and self._engine.updates_skipped > skipped0:
                 import warnings
                 warnings.warn("%d optimizer update(s) of this epoch were skipped on the device (a scan of the step reported a non-finite "
