@@ -19,6 +19,13 @@ MOVE_MEASURED = {
     "unimodal_tiny": {"kernel": 4.52e-04, "recurrent": 9.09e-04, "bias": 4.25e-04, "dense": 4.91e-05, "dense_bias": 1.03e-07},
     "fusion_bite": {"kernel": 3.06e-07, "recurrent": 7.44e-04, "bias": 2.65e-04, "dense": 2.68e-05, "dense_bias": 1.30e-08},
     "unimodal_layer_bound": {"kernel": 5.68e-05, "recurrent": 8.06e-04, "bias": 3.01e-04, "dense": 4.85e-05, "dense_bias": 1.79e-07},
+    # the device-RNG replay cases of tests/rng_cases.py over their first 3 (the pipelined one: 4) replayed steps
+    # (tests/test_cpu_rng_replay.py::test_movement_error_model re-measures them)
+    "rng_fusion_tiny_3": {"kernel": 1.85e-04, "recurrent": 7.43e-04, "bias": 3.74e-04, "dense": 4.92e-05, "dense_bias": 7.57e-08},
+    "rng_unimodal_tiny_3": {"kernel": 1.94e-04, "recurrent": 9.66e-04, "bias": 2.73e-04, "dense": 5.69e-05, "dense_bias": 8.31e-08},
+    "rng_split_wide_3": {"kernel": 1.45e-03, "recurrent": 9.50e-04, "bias": 5.39e-04, "dense": 6.87e-05, "dense_bias": 1.55e-05},
+    "rng_split_narrow_3": {"kernel": 5.47e-04, "recurrent": 1.95e-03, "bias": 4.05e-04, "dense": 5.94e-05, "dense_bias": 3.12e-06},
+    "rng_fusion_tiny_4": {"kernel": 1.88e-04, "recurrent": 8.07e-04, "bias": 2.92e-04, "dense": 4.50e-05, "dense_bias": 7.14e-08},
 }
 MOVE_FACTOR = 4.0
 
