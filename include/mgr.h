@@ -690,6 +690,68 @@ int mgr_ctc_rescore(mgr_ctx* ctx, const float* P, const int32_t* input_len, int 
                     const int32_t* phrase_off, const int32_t* phrase_words, int G, const int32_t* hyp, const int32_t* hyp_len, int K,
                     int Lh, double* logp, int32_t* n_lab, void* ws, size_t ws_bytes);
 
+/* ---- K19: joint decode over several CTC streams: a LABEL-synchronous prefix search - Graves' prefix search with the CTC
+ * prefix score - over gesture sequences that every stream scores at every step.  Streams may differ in frame count, frame rate and
+ * class set; nothing is frame-synchronous.
+ * Streams: 1 <= M <= MGR_JOINT_MAX_STREAMS entries of the struct below.  Stream m has posteriors P [B,T,C] float32 and input_len [B]
+ * (device), skip, blank, eps, a weight w_m > 0, and an optional lexicon phrase_off [G+1] / phrase_words (HOST memory, K13's rules, C <=
+ * 64; both NULL: none).  Hypotheses are sequences over G gesture ids, G <= MGR_LEXICON_MAX_PHRASES.  In a stream with a lexicon
+ * gesture g is its phrase's words (at most MGR_JOINT_MAX_PHRASE_WORDS of them: a longer phrase is refused, for the whole call); in a
+ * stream without one gesture g is class g, which needs G <= C, and g == blank is an extension of probability 0 in that stream.
+ * Emissions are K14's: frames skip .. skip + Tp - 1, Tp = input_len[b] clipped into [0, T - skip], ln y = ln((P + eps) / sum_c (P + eps)),
+ * formed in fp64.  struct_size = sizeof of the struct in the CALLER's header: the call refuses any other value.
+ * Score of a hypothesis Q = (g_1 .. g_n), n = 0 allowed:
+ *     score(Q) = sum_m w_m ln p_m(Q) + sum_i ext[(g_{i-1} + 1) * G + g_i] + fin[g_n + 1]
+ * ln p_m(Q) is K14's logp (all alignments, words expanded through the lexicon); ext [(G+1)*G] and fin [G+1] (or NULL) are doubles in
+ * device memory with K13's conventions: row / index 0 = start / empty, entries finite or -inf, THE CALLER refuses NaN and +inf.
+ * Prefix score: pre(Q) = the same sum with ln psi_m(Q) in place of ln p_m(Q) and without fin, psi_m(Q) the probability under stream m
+ * that the labelling BEGINS with the expansion of Q.
+ * Recursion per stream, natural-log fp64, lse(a, b) = max + log1p(exp(-|a - b|)) with lse(-inf, x) = x.  A prefix g has gn(t), gb(t):
+ * the log-probability of emitting exactly g over frames 0 .. t, ending in a label / in blank; the empty prefix has gn = -inf, gb(t) =
+ * sum_{tau <= t} ln y_tau(blank).  Extension h = g . c by a class c of the stream (never blank):
+ *     t = 0:  gn_h(0) = ln y_0(c) if g is empty, else -inf;  gb_h(0) = -inf;  psi = gn_h(0)
+ *     t >= 1: phi = lse(gb_g(t-1), last(g) != c ? gn_g(t-1) : -inf)            (the empty prefix: gb_g(t-1))
+ *             gn_h(t) = lse(gn_h(t-1), phi) + ln y_t(c);   gb_h(t) = lse(gb_h(t-1), gn_h(t-1)) + ln y_t(blank)
+ *             psi = lse(psi, phi + ln y_t(c))
+ *     ln p(h) = lse(gn_h(Tp-1), gb_h(Tp-1));  at Tp = 0 every non-empty h has psi = p = 0 (-inf) and the empty hypothesis ln p = 0
+ * A gesture of n_g words is n_g chained extensions; only the last word's gn, gb and psi are the gesture's.
+ * The search, per sample:
+ *   round 0        the live set is the empty prefix; the result list receives the empty hypothesis if its score is finite.
+ *   round n >= 1   candidates are (live prefix of rank r, gesture g) with finite ext; a candidate ranks by pre, pre = -inf is dropped;
+ *                  the `beam` best are kept, ties to the smaller r, then the smaller g; each kept candidate whose score is finite
+ *                  enters the result list, in rank order.
+ *   result list    the top_paths best scores; ties go to the entry found earlier (lower round, then better rank in the round).
+ *   stop           after round n when nothing is live, or n == max_len, or the list holds top_paths entries and the best live prefix
+ *                  has pre + U_n < the list's worst score, U_n = (max_len - n) * max(0, largest ext) + max(0, largest fin).
+ * Since psi_m(Q) >= p_m(Q') for every extension Q' of Q and the comparison is strict, the stop never changes the output: it equals
+ * the search that always runs max_len rounds.
+ * Outputs (device): out [B,top_paths,max_len] int32 padded -1; out_len [B,top_paths], -1 for an empty slot; score [B,top_paths] double,
+ * -inf for an empty slot; logp [B,top_paths,M] double, each stream's ln p_m unweighted (-inf in an empty slot); rounds [B] int32 or
+ * NULL: the rounds the sample ran.  A sample without a finite hypothesis gets all slots empty.
+ * 1 <= top_paths <= beam <= 32, 1 <= max_len <= MGR_RESCORE_MAX_LABELS, B <= 65535.  The workspace holds per stream the fp64 class-major
+ * emissions and two sets of `beam` prefix arrays (the kept candidates' chains are run again to store theirs: the arrays of all
+ * beam * G candidates are never stored), and the candidates' psi / ln p.  No atomics: deterministic, and a sample's rows do not
+ * depend on the rest of the batch.  An error is reported before anything is written. */
+#define MGR_JOINT_MAX_STREAMS 4
+#define MGR_JOINT_MAX_PHRASE_WORDS 8
+typedef struct mgr_joint_stream {
+  unsigned struct_size;
+  int T;
+  int C;
+  int skip;
+  int blank;
+  float eps;
+  double weight;
+  const float* P;
+  const int32_t* input_len;
+  const int32_t* phrase_off;
+  const int32_t* phrase_words;
+} mgr_joint_stream;
+size_t mgr_ctc_joint_ws_bytes(int B, int M, const mgr_joint_stream* streams, int G, int beam, int top_paths, int max_len);
+int mgr_ctc_joint_decode(mgr_ctx* ctx, int B, int M, const mgr_joint_stream* streams, int G, const double* ext, const double* fin, int beam,
+                         int top_paths, int max_len, int32_t* out, int32_t* out_len, double* score, double* logp, int32_t* rounds,
+                         void* ws, size_t ws_bytes);
+
 /* ---- K15: expected risk over an N-best list and its gradient: what sequence-level minimum-risk training (MWER / minimum
  * expected error) needs beside K11's N-best lists, K12's edit distances and K14's scores - the gradient through all K likelihoods of a
  * sample in one call.  Per sample: K hypothesis slots (hyp / hyp_len / the lexicon exactly as K14 takes them) and one integer risk

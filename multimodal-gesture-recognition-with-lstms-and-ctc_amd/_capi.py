@@ -135,6 +135,8 @@ SIGNATURES = {
                                      sz]),
     "mgr_ctc_rescore_ws_bytes": (sz, [i32, i32, i32, i32, vp]),
     "mgr_ctc_rescore": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, sz]),
+    "mgr_ctc_joint_ws_bytes": (sz, [i32, i32, vp, i32, i32, i32, i32]),
+    "mgr_ctc_joint_decode": (i32, [vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz]),
     "mgr_ctc_risk_ws_bytes": (sz, [i32, i32, i32, i32, i32, i32, vp]),
     "mgr_ctc_risk_grad": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, i32, i32, i32, vp, C.c_float, C.c_float,
                                 C.c_float, i32, vp, vp, vp, vp, vp, sz]),
@@ -172,6 +174,33 @@ class ScanBwdJob(C.Structure):
 class ScanLaunchOpts(C.Structure):
     """struct mgr_scan_launch_opts"""
     _fields_ = [("struct_size", C.c_uint), ("form", i32), ("seq_out", vp)]
+
+
+class JointStream(C.Structure):
+    """struct mgr_joint_stream (K19): struct_size is checked by mgr_ctc_joint_decode; phrase_off / phrase_words are HOST pointers or 0"""
+    _fields_ = [("struct_size", C.c_uint), ("T", i32), ("C", i32), ("skip", i32), ("blank", i32), ("eps", C.c_float), ("weight", C.c_double),
+                ("P", vp), ("input_len", vp), ("phrase_off", vp), ("phrase_words", vp)]
+
+
+JOINT_MAX_STREAMS, JOINT_MAX_PHRASE_WORDS = 4, 8       # MGR_JOINT_MAX_* of include/mgr.h
+
+
+def make_joint_streams(streams):
+    """streams: list of dicts with the mgr_joint_stream fields - P / input_len DeviceArrays (or device addresses), phrase_off /
+    phrase_words host int32 arrays or None (the caller keeps them alive for the call)."""
+    arr = (JointStream * len(streams))()
+    for a, s in zip(arr, streams):
+        a.struct_size = C.sizeof(JointStream)
+        for k in ("T", "C", "skip", "blank"):
+            setattr(a, k, int(s[k]))
+        a.eps, a.weight = float(s["eps"]), float(s["weight"])
+        for k in ("P", "input_len"):
+            v = s[k]
+            setattr(a, k, v.ptr if isinstance(v, DeviceArray) else (v or None))
+        for k in ("phrase_off", "phrase_words"):
+            v = s.get(k)
+            setattr(a, k, None if v is None else v.ctypes.data)
+    return arr
 
 
 # enums of include/mgr.h (mgr_scan_launch_opts.form)

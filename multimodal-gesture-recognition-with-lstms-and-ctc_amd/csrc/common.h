@@ -22,6 +22,7 @@ enum : unsigned {
   MGR_ATTR_LEXICON = 4096u, MGR_ATTR_RISK = 8192u,                                                 // lexicon.hip, risk.hip
   MGR_ATTR_OVERLAP = 16384u,                                                                       // overlap.hip
   MGR_ATTR_CTC_ENT = 32768u,                                                                       // ctc.hip: the entropy call's variants
+  MGR_ATTR_JOINT = 65536u,                                                                         // joint.hip
 };
 
 struct mgr_ctx {

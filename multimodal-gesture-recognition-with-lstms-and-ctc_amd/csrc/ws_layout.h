@@ -29,3 +29,22 @@ static inline mgr_beam_ws mgr_beam_ws_layout(void* ws, int B, size_t nodes) {
   mgr_ws_carver w(ws);
   return {bits, w.take<int32_t>((size_t)B * nodes), w.take<int32_t>((size_t)B * nodes), w.take<unsigned long long>((size_t)B << bits), w.off};
 }
+
+// joint.hip: per stream the fp64 class-major emissions E [B][C][row] and the two sets of `beam` prefix arrays A [B][2][beam][2][row]
+// (gn row, gb row), then every candidate's ln psi and ln p per stream: PSI, LP [B][M][beam * G].  row = mgr_joint_row(T): laid out
+// for T frames (the kernels use T - skip: they fit) plus the one entry the chains fetch ahead.
+constexpr int kJointMaxStreams = 4;   // MGR_JOINT_MAX_STREAMS
+constexpr size_t mgr_joint_row(int T) { return ((size_t)T + 1 + 1) / 2 * 2; }   // (constexpr: the kernels call it too)
+struct mgr_joint_ws { double *E[kJointMaxStreams], *A[kJointMaxStreams], *PSI, *LP; size_t bytes; };
+static inline mgr_joint_ws mgr_joint_ws_layout(void* ws, int B, int M, const int* T, const int* C, int G, int beam) {
+  mgr_ws_carver w(ws);
+  mgr_joint_ws L = {};
+  for (int m = 0; m < M && m < kJointMaxStreams; ++m) {
+    L.E[m] = w.take<double>((size_t)B * C[m] * mgr_joint_row(T[m]));
+    L.A[m] = w.take<double>((size_t)B * 2 * beam * 2 * mgr_joint_row(T[m]));
+  }
+  L.PSI = w.take<double>((size_t)B * M * beam * G);
+  L.LP = w.take<double>((size_t)B * M * beam * G);
+  L.bytes = w.off;
+  return L;
+}

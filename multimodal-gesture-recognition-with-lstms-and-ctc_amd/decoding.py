@@ -767,6 +767,99 @@ def rescore_nbest(streams, paths, weights=None, lm=None, lm_end=None, alpha=1.0,
     return ranked, total, np.take_along_axis(parts, order[:, :, None], axis=1), order
 
 
+# ---- joint decode over several streams (K19): a label-synchronous prefix search that every stream scores ---------------
+JOINT_MAX_STREAMS, JOINT_MAX_PHRASE_WORDS, JOINT_MAX_BEAM = 4, 8, 32       # MGR_JOINT_MAX_* of include/mgr.h, and its beam <= 32
+
+
+def joint_from_arrays(out, out_len, score, logp):
+    """mgr_ctc_joint_decode's arrays ((B, K, max_len), (B, K), (B, K), (B, K, M)) -> (paths: per sample its hypotheses best first,
+    score (B, K), parts (B, K, M)) - rescore_nbest's ranked shapes."""
+    B, K = out_len.shape
+    paths = [[[int(v) for v in out[b, k, :out_len[b, k]]] for k in range(K) if out_len[b, k] >= 0] for b in range(B)]
+    return paths, score.copy(), logp.copy()
+
+
+def joint_decode(streams, G=None, weights=None, lm=None, lm_end=None, alpha=1.0, beta=0.0, beam_width=10, top_paths=1, max_len=None,
+                 input_lengths=None, skip=2, dev=None, return_rounds=False):
+    """Joint decode over several CTC streams on the GPU (mgr_ctc_joint_decode): a prefix search over GESTURE sequences in
+    which every stream scores every extension with its CTC prefix probability - unlike rescore_nbest it can return a sequence that no
+    stream proposed on its own.  streams: a list of (posteriors (N, T, C) - a host array or a float32 DeviceArray -, dict(lexicon=,
+    input_length=, skip=, eps=) or None), the pairs rescore_nbest takes; T, C and the frame rate may differ from stream to stream, the
+    blank is each stream's last class.  A stream with a lexicon (whatever compile_lexicon takes, phrases of at most 8 words) reads
+    gesture g as its phrase's words, one without reads it as class g.  G: the number of gestures (default: the lexicons' phrase count,
+    without a lexicon the first stream's C - 1).  A hypothesis ranks by
+        sum_m weights[m] * ln p_m + alpha * (lm over its gesture pairs + lm_end[last + 1]) + beta * len
+    with the tables of phrase_lm_tables.  beam_width <= 32 prefixes are kept per round, top_paths <= beam_width hypotheses returned;
+    max_len (default: the shortest stream's frames, at most 255) bounds the gestures per hypothesis.  input_lengths: per stream None or
+    (N,) lengths (a stream's dict may hold its own).
+    Returns (paths: per sample its at most top_paths hypotheses best first, score (N, top_paths) float64 with -inf in empty slots,
+    parts (N, top_paths, M): each stream's ln p, unweighted) - what pool_hypotheses, mbr_decode, nbest_attainable, ctc_scores and
+    expected_risk take from rescore_nbest[, rounds (N,): the rounds each sample's search ran]."""
+    dev = dev or default_device()
+    M = len(streams)
+    if not 1 <= M <= JOINT_MAX_STREAMS:
+        raise ValueError("%d streams: the decoder takes 1 .. %d" % (M, JOINT_MAX_STREAMS))
+    w = np.ones(M) if weights is None else np.asarray(weights, np.float64).reshape(-1)
+    if w.shape != (M,) or not np.all(np.isfinite(w)) or not np.all(w > 0):
+        raise ValueError("weights %r for %d streams: positive finite numbers" % (weights, M))
+    if input_lengths is not None and len(input_lengths) != M:
+        raise ValueError("input_lengths for %d streams, not %d" % (M, len(input_lengths)))
+    held, keep_alive, descs = [], [], []
+
+    def keep(a):
+        held.append(a)
+        return a
+    try:
+        N = None
+        for m, (post, opts) in enumerate(streams):
+            opts = dict(opts or {})
+            dP = post if isinstance(post, _capi.DeviceArray) else keep(dev.array(_posteriors(post)))
+            if len(dP.shape) != 3 or dP.dtype != np.float32:
+                raise ValueError("stream %d: posteriors %s %s, not (N, T, C) float32" % (m, dP.shape, dP.dtype))
+            n, T, Cn = dP.shape
+            if N is not None and n != N:
+                raise ValueError("stream %d holds %d samples, stream 0 %d" % (m, n, N))
+            N = n
+            sk = int(opts.get("skip", skip))
+            il = opts.get("input_length", None if input_lengths is None else input_lengths[m])
+            il = np.full(N, T - sk, np.int32) if il is None else np.asarray(il).reshape(N).astype(np.int32)
+            off = words = None
+            if opts.get("lexicon") is not None:
+                off, words = compile_lexicon(opts["lexicon"], Cn)
+                if int(np.diff(off).max()) > JOINT_MAX_PHRASE_WORDS:
+                    raise ValueError("stream %d: a phrase of %d words, the joint decoder takes %d" % (m, int(np.diff(off).max()), JOINT_MAX_PHRASE_WORDS))
+                keep_alive += [off, words]
+            descs.append(dict(T=T, C=Cn, skip=sk, blank=Cn - 1, eps=opts.get("eps", 1e-8), weight=w[m], P=dP, input_len=keep(dev.array(il)),
+                              phrase_off=off, phrase_words=words))
+        counts = set(len(d["phrase_off"]) - 1 for d in descs if d["phrase_off"] is not None)
+        if len(counts) > 1:
+            raise ValueError("the streams' lexicons hold %s phrases" % sorted(counts))
+        G = int(G) if G is not None else (counts.pop() if counts else descs[0]["C"] - 1)
+        if counts and G not in counts:
+            raise ValueError("G = %d for lexicons of %s phrases" % (G, sorted(counts)))
+        for m, d in enumerate(descs):
+            if d["phrase_off"] is None and G > d["C"]:
+                raise ValueError("stream %d: G = %d gestures for %d classes without a lexicon" % (m, G, d["C"]))
+        W, NP = int(beam_width), int(top_paths)
+        if not 1 <= NP <= W <= JOINT_MAX_BEAM:
+            raise ValueError("top_paths = %d / beam_width = %d: 1 <= top_paths <= beam_width <= %d" % (NP, W, JOINT_MAX_BEAM))
+        Lmax = min(RESCORE_MAX_LABELS, min(d["T"] - d["skip"] for d in descs)) if max_len is None else int(max_len)
+        if not 1 <= Lmax <= RESCORE_MAX_LABELS:
+            raise ValueError("max_len = %d: 1 .. %d" % (Lmax, RESCORE_MAX_LABELS))
+        ext, fin = phrase_lm_tables(G, lm, lm_end, alpha, beta)
+        arr = _capi.make_joint_streams(descs)
+        dext, dfin = keep(dev.array(ext)), None if fin is None else keep(dev.array(fin))
+        out, out_len = keep(dev.empty((N, NP, Lmax), np.int32)), keep(dev.empty((N, NP), np.int32))
+        score, logp, rounds = keep(dev.empty((N, NP), np.float64)), keep(dev.empty((N, NP, M), np.float64)), keep(dev.empty((N,), np.int32))
+        ws = keep(dev.bytes(dev.lib.mgr_ctc_joint_ws_bytes(N, M, arr, G, W, NP, Lmax)))
+        dev.call("mgr_ctc_joint_decode", N, M, arr, G, dext, dfin, W, NP, Lmax, out, out_len, score, logp, rounds, ws, ws.nbytes)
+        res = joint_from_arrays(out.download(), out_len.download(), score.download(), logp.download())
+        return res + ((rounds.download(),) if return_rounds else ())
+    finally:
+        for a in held:
+            a.free()
+
+
 def edit_distance(a, b):
     la, lb = len(a), len(b)
     d = list(range(lb + 1))

@@ -6,7 +6,7 @@ frame rate nor synchronous gestures."""
 import numpy as np
 
 from ..audio_network.sequence_decoding import GESTURE_LEXICON
-from ..decoding import beam_search_lm_decode, lexicon_decode, pool_hypotheses, rescore_nbest, write_mlf
+from ..decoding import beam_search_lm_decode, joint_decode, lexicon_decode, pool_hypotheses, rescore_nbest, write_mlf
 from .sequence_decoding import ignore_list, map_gest
 
 
@@ -30,6 +30,21 @@ def decode_rescoring(skeletal_post, audio_post, f_list, top_paths=10, beam_width
         paths = pool_hypotheses(nbest, [[[s[0] for s in sg]] for sg in segs])
     streams = [(skeletal_post, {}), (audio_post, {"lexicon": GESTURE_LEXICON})]
     ranked, total, parts, _ = rescore_nbest(streams, paths, weights, lm, lm_end, alpha, beta)
+    ret = [[map_gest[g] for g in (r[0] if r else [])] for r in ranked]
+    if out_file is not None:
+        write_mlf(out_file, ret, f_list, ignore_list, "Sample%05d")
+    return ret, (ranked, total, parts)
+
+
+def decode_joint(skeletal_post, audio_post, f_list, top_paths=1, beam_width=10, weights=(1.0, 1.0), lm=None, lm_end=None, alpha=1.0, beta=0.0,
+                 max_len=None, out_file="ctc_recout_joint.mlf"):
+    """Late fusion by JOINT decoding: one prefix search over gesture sequences in which both networks score every
+    extension - the skeletal network gesture g as its class g, the audio network as the words of GESTURE_LEXICON[g] -, so the result
+    need not be a sequence either network proposed on its own (decode_rescoring can only re-rank such a pool).  Arguments as
+    decode_rescoring's; the same class map, ignore list and MLF writing.
+    Returns (1-best name lists, (ranked paths, total, parts))."""
+    streams = [(skeletal_post, {}), (audio_post, {"lexicon": GESTURE_LEXICON})]
+    ranked, total, parts = joint_decode(streams, len(GESTURE_LEXICON), weights, lm, lm_end, alpha, beta, beam_width, top_paths, max_len)
     ret = [[map_gest[g] for g in (r[0] if r else [])] for r in ranked]
     if out_file is not None:
         write_mlf(out_file, ret, f_list, ignore_list, "Sample%05d")
