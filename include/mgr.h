@@ -188,6 +188,12 @@ int mgr_lstm_scan_fwd(mgr_ctx* ctx, const float* Z, const float* Up, float* Y, i
 typedef struct mgr_scan_job {
   const float* Z;
   const float* Up;
+  /* NULL together with a YT: write ONLY the transposed copy (a caller whose every reader takes YT - the pre-split / transposed
+   * projection and weight-gradient products - saves the scan a store stream of B T H floats in 16-byte pieces).  The K-split multi-CU
+   * kernels then skip their row store; every other kernel family still writes rows, because the transpose behind it reads them: into
+   * scratch from ws (mgr_lstm_scan_fwd_multi_ws_bytes counts it for exactly those jobs, mgr_lstm_scan_multi_ws_bytes for every job
+   * without Y).  ldy is not looked at.  Y == NULL and YT == NULL is an error; so is a workspace without room for the scratch - both
+   * are refused before anything is enqueued. */
   float* Y;
   const float* R;
   float* gates;
@@ -241,6 +247,10 @@ typedef struct mgr_scan_launch_opts {
 } mgr_scan_launch_opts;
 int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* ctx, int njobs, const mgr_scan_job* jobs, void* ws, size_t ws_bytes,
                                const mgr_scan_launch_opts* opts);
+/* The workspace mgr_lstm_scan_fwd_multi_ex needs for exactly this call in this context (its tune keys, opts->form): what
+ * mgr_lstm_scan_multi_ws_bytes says, less the row scratch of the jobs without Y whose kernel writes YT itself.  Plans the call with
+ * the launcher's own code and enqueues nothing.  0: a bad job list (mgr_last_error). */
+size_t mgr_lstm_scan_fwd_multi_ws_bytes(mgr_ctx* ctx, int njobs, const mgr_scan_job* jobs, const mgr_scan_launch_opts* opts);
 /* ABI guard for bindings that fill mgr_scan_job / mgr_scan_bwd_job / mgr_scan_launch_opts field by field: the sizes the LIBRARY was
  * built with (round 5 appended mgr_scan_bwd_job.dzmax and turned mgr_scan_job's reserved word into yt_split; revision 7 appended
  * mgr_scan_bwd_job.dbsum and the dbsum / proj_ws / HsT arguments of mgr_lstm_param_grads_dropout_ts - a caller built against

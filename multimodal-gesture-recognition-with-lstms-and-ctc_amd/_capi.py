@@ -61,6 +61,7 @@ SIGNATURES = {
     "mgr_lstm_scan_multi_ws_bytes": (sz, [i32, vp]),
     "mgr_lstm_scan_fwd_multi": (i32, [vp, i32, vp, vp, sz]),
     "mgr_lstm_scan_fwd_multi_ex": (i32, [vp, i32, vp, vp, sz, vp]),
+    "mgr_lstm_scan_fwd_multi_ws_bytes": (sz, [vp, i32, vp, vp]),
     "mgr_abi_struct_sizes": (i32, [vp]),
     "mgr_tune": (i32, [vp, i32, i32]),
     "mgr_tune_get": (i32, [vp, i32, C.POINTER(i32)]),

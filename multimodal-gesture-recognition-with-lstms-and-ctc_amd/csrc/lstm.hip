@@ -40,6 +40,19 @@ size_t job_ws(const mgr_scan_job& j) {
   return mgr_align_up((size_t)nbg * 2 * img * sizeof(float), 256);
 }
 
+// Row-major output of a job that gave none (mgr.h: Y == NULL with a YT): a kernel family that does not write the transposed copy
+// itself is followed by a transpose FROM the rows, so its rows go to this scratch, packed [B][T][H].
+size_t job_rows_scratch(const mgr_scan_job& j) {
+  return (!j.Y && j.YT) ? mgr_align_up((size_t)j.B * j.T * j.H * sizeof(float), 256) : 0;
+}
+
+// header + exchange images: what the cluster kernels need whatever the jobs ask for
+size_t base_ws(int njobs, const mgr_scan_job* jobs) {
+  size_t s = kScanHdrBytes;
+  for (int i = 0; i < njobs; ++i) s += job_ws(jobs[i]);
+  return s;
+}
+
 // Choose per-job configurations: minimise the slowest job's per-step MFMA time subject to all workgroups
 // being co-resident (sum <= CUs).  Jobs that cannot run on the cluster kernel are left to the other families.
 void make_plan(const mgr_ctx* c, int njobs, const mgr_scan_job* jobs, Plan& P) {
@@ -220,9 +233,11 @@ size_t mgr_lstm_scan_ws_bytes(int B, int T, int H) {
   return std::max(std::max(fallback, job_ws(j) + kScanHdrBytes), mgr_lstm_scan_bwd_multi_ws_bytes(1, &bj));
 }
 
+// (an upper bound that needs no context: row scratch for EVERY job without Y; mgr_lstm_scan_fwd_multi_ws_bytes leaves out the jobs
+// whose kernel writes the transposed copy itself)
 size_t mgr_lstm_scan_multi_ws_bytes(int njobs, const mgr_scan_job* jobs) {
-  size_t s = kScanHdrBytes;
-  for (int i = 0; i < njobs; ++i) s += job_ws(jobs[i]);
+  size_t s = base_ws(njobs, jobs);
+  for (int i = 0; i < njobs; ++i) s += job_rows_scratch(jobs[i]);
   return s;
 }
 
@@ -248,49 +263,79 @@ int mgr_lstm_scan_fwd_multi(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, voi
   return mgr_lstm_scan_fwd_multi_ex(c, njobs, jobs, ws, ws_bytes, nullptr);
 }
 
-int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, void* ws, size_t ws_bytes,
-                               const mgr_scan_launch_opts* opts) {
-  MGR_REQUIRE(c && jobs && njobs > 0 && njobs <= MGR_MAX_SCAN_JOBS, "bad job list");
-  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
-  int form;
-  unsigned* seq_out;
-  read_opts(opts, &form, &seq_out);
-  MGR_REQUIRE(form >= MGR_SCAN_FORM_AUTO && form <= MGR_SCAN_FORM_FUSED_ANY, "unknown scan form %d", form);
-  MGR_REQUIRE(form != 2, "scan form 2 (the pair form) is retired");
-  if (seq_out) *seq_out = MGR_SEQ_NONE;   // (until a launch of this call enters the residency ledger)
-  // the form of the split-f16 K-split launches: the caller's, or MGR_TUNE_SCAN_FORM (3 fused, anything else plain)
-  const bool want_fused = form == MGR_SCAN_FORM_AUTO ? c->tune[MGR_TUNE_SCAN_FORM] == MGR_SCAN_FORM_FUSED : form >= MGR_SCAN_FORM_FUSED;
-  const bool fused_any = form == MGR_SCAN_FORM_FUSED_ANY;
+// The forward multi-scan call.  need_out != nullptr: enqueue NOTHING - plan the call as it would run in this context with a workspace
+// that is large enough and report the bytes that plan needs (mgr_lstm_scan_fwd_multi_ws_bytes; ws is not looked at).
+static int scan_fwd_multi(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, void* ws, size_t ws_bytes, const mgr_scan_launch_opts* opts,
+                          size_t* need_out) {
+  const bool query = need_out != nullptr;
+  // (the job list is checked before the context: these checks are what keeps a store through a NULL row pointer off the device, and
+  //  they are plain host code a box without a GPU can run - tests/test_cpu_scan_no_rows.py)
+  MGR_REQUIRE(jobs && njobs > 0 && njobs <= MGR_MAX_SCAN_JOBS, "bad job list");
   for (int i = 0; i < njobs; ++i) {
     const mgr_scan_job& j = jobs[i];
-    MGR_REQUIRE(j.Z && j.Up && j.Y, "job %d: null argument", i);
-    MGR_REQUIRE(j.B > 0 && j.T > 0 && j.H > 0 && j.ldy >= j.H && (!j.R || j.ldr >= j.H), "job %d: bad shape", i);
+    MGR_REQUIRE(j.Z && j.Up, "job %d: null argument", i);
+    MGR_REQUIRE(j.Y || j.YT, "job %d: neither Y nor YT - a scan job writes its rows, the transposed copy, or both", i);
+    MGR_REQUIRE(j.B > 0 && j.T > 0 && j.H > 0 && (!j.Y || j.ldy >= j.H) && (!j.R || j.ldr >= j.H), "job %d: bad shape", i);
     MGR_REQUIRE(aligned16(j.Z) && aligned16(j.Up) && (!j.gates || aligned16(j.gates)), "job %d: Z/Up/gates must be 16-byte aligned", i);
     MGR_REQUIRE(!j.YT || (aligned16(j.YT) && j.ldt % 4 == 0 && j.ldt >= (j.T + 31) / 32 * 32 && j.ytb % 4 == 0 && j.ytb >= (long long)j.H * j.ldt),
                 "job %d: transposed output needs a 16-byte aligned YT, ldt %% 4 == 0, ldt >= T rounded up to 32, ytb >= H * ldt", i);
     MGR_REQUIRE(!j.YT || !j.yt_split || j.ldt % 8 == 0, "job %d: split rows need ldt %% 8 == 0", i);
   }
+  MGR_REQUIRE(c, "null context");
+  if (query) ws = nullptr;
+  if (!query) mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
+  int form;
+  unsigned* seq_out;
+  read_opts(opts, &form, &seq_out);
+  MGR_REQUIRE(form >= MGR_SCAN_FORM_AUTO && form <= MGR_SCAN_FORM_FUSED_ANY, "unknown scan form %d", form);
+  MGR_REQUIRE(form != 2, "scan form 2 (the pair form) is retired");
+  if (seq_out && !query) *seq_out = MGR_SEQ_NONE;   // (until a launch of this call enters the residency ledger)
+  // the form of the split-f16 K-split launches: the caller's, or MGR_TUNE_SCAN_FORM (3 fused, anything else plain)
+  const bool want_fused = form == MGR_SCAN_FORM_AUTO ? c->tune[MGR_TUNE_SCAN_FORM] == MGR_SCAN_FORM_FUSED : form >= MGR_SCAN_FORM_FUSED;
+  const bool fused_any = form == MGR_SCAN_FORM_FUSED_ANY;
   int hmax = 0;
   for (int i = 0; i < njobs; ++i) hmax = jobs[i].H > hmax ? jobs[i].H : hmax;
   const int family = hmax > 128 ? MGR_K_SCAN_FWD : MGR_K_SCAN_FWD_NARROW;
-  int r = mgr_prof_begin(c, family);
+  int r = query ? 0 : mgr_prof_begin(c, family);
   if (r) return r;
   Plan P;
   make_plan(c, njobs, jobs, P);
-  if (P.any && (!ws || ws_bytes < mgr_lstm_scan_multi_ws_bytes(njobs, jobs))) {
+  const size_t base_need = base_ws(njobs, jobs);
+  if (!query && P.any && (!ws || ws_bytes < base_need)) {
     // no workspace for the exchange: degrade to the non-cluster families
     for (int i = 0; i < njobs; ++i) P.cluster[i] = false;
     P.any = false;
   }
   unsigned* status = nullptr;
   bool yt_done[MGR_MAX_SCAN_JOBS] = {};
+  // Where each job's rows go: its Y - or, for a job that gave none and whose kernel does not write the transposed copy itself (the
+  // transpose behind the scans reads rows), scratch behind the exchange images, packed [B][T][H].  Decided, and the workspace checked
+  // against it, BEFORE anything is enqueued: a kernel that stores through a NULL row pointer faults the device.
+  float* rows[MGR_MAX_SCAN_JOBS];
+  int ldrows[MGR_MAX_SCAN_JOBS];
+  size_t need = base_need;
+  auto place_rows = [&]() -> int {
+    for (int i = 0; i < njobs; ++i) {
+      const mgr_scan_job& j = jobs[i];
+      rows[i] = j.Y;
+      ldrows[i] = j.ldy;
+      if (j.Y || yt_done[i]) continue;
+      rows[i] = ws ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + need) : nullptr;
+      ldrows[i] = j.H;
+      need += job_rows_scratch(j);
+    }
+    if (query) return 0;
+    MGR_REQUIRE(need == base_need || (ws && ws_bytes >= need),
+                "jobs without Y whose kernel does not write YT itself need %zu bytes of workspace for their rows (mgr_lstm_scan_fwd_multi_ws_bytes)",
+                need);
+    return 0;
+  };
   if (P.any) {
     ClusterLaunch L;
     memset(&L, 0, sizeof(L));
-    char* w = reinterpret_cast<char*>(ws);
-    status = reinterpret_cast<unsigned*>(w);
-    char* base = w;
-    w += kScanHdrBytes;
+    char* base = reinterpret_cast<char*>(ws);
+    status = reinterpret_cast<unsigned*>(base);
+    size_t off = kScanHdrBytes;
     // K-split launches (every job a 4-wave, one-tile-per-wave cluster with an exchange) lay their clusters out XCD-locally
     // (MGR_TUNE_SCAN_NO_XCD_LOCAL = 1 turns that off); the table of workgroup XCD ids lives in the launch header
     // the K-split step addresses Z and the residual input with 32-bit byte offsets per lane (LDS-DMA prefetch): launches with a
@@ -364,8 +409,8 @@ int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, 
       cj.ks = ks; cj.tpw = P.cfg[i].tpw; cj.nw = P.cfg[i].nw;
       cj.G_ = P.G[i]; cj.nbg = P.nbg[i];
       cj.cls_begin = cb[i]; cj.cls_nclusters = cn[i]; cj.cls_cluster0 = c0[i]; cj.cls_rot = cr[i];
-      cj.xbuf = reinterpret_cast<float*>(w);
-      w += mgr_align_up((size_t)P.nbg[i] * 2 * img * sizeof(float), 256);
+      cj.xbuf = base ? reinterpret_cast<float*>(base + off) : nullptr;
+      off += mgr_align_up((size_t)P.nbg[i] * 2 * img * sizeof(float), 256);
     }
     L.fused = fused ? 1 : 0;
     L.live_wgs = live;
@@ -379,6 +424,22 @@ int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, 
         ClusterJob& cj = L.job[k++];
         cj.YT = jobs[i].YT; cj.ytb = jobs[i].ytb; cj.ldt = jobs[i].ldt; cj.yt_split = jobs[i].yt_split;
         yt_done[i] = jobs[i].YT != nullptr;
+      }
+    }
+    r = place_rows();
+    if (r) return r;
+    if (query) {
+      *need_out = need;
+      return 0;
+    }
+    {   // (a K-split job without Y keeps its NULL: the kernel skips the row store; every other kernel stores through the pointer)
+      int k = 0;
+      for (int i = 0; i < njobs; ++i) {
+        if (!P.cluster[i]) continue;
+        ClusterJob& cj = L.job[k++];
+        cj.Y = rows[i];
+        cj.ldy = ldrows[i];
+        MGR_REQUIRE(cj.Y || (yt_done[i] && cj.YT), "job %d: no rows to write to", i);
       }
     }
     if (c->tune[MGR_TUNE_SCAN_PRINT_PLAN]) {
@@ -400,31 +461,48 @@ int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, 
       if (seq_out) *seq_out = L.cm.seq;
     }
     // exchange slots + status must be zero at every launch (epochs count from 1 within the call)
-    MGR_HIP(hipMemsetAsync(base, 0, (size_t)(w - base), mgr_stream(c)));
+    MGR_HIP(hipMemsetAsync(base, 0, off, mgr_stream(c)));
     r = mgr_cluster_launch(c, L, P.total, P.exchange);
     if (r) return r;
     if (P.exchange) {
       r = mgr_persist_commit(c, live, waves, per_cu, L.fused);
       if (r) return r;
     }
+  } else {
+    r = place_rows();
+    if (r) return r;
+    if (query) {
+      *need_out = need;
+      return 0;
+    }
   }
   for (int i = 0; i < njobs; ++i) {
     if (P.cluster[i]) continue;
     const mgr_scan_job& j = jobs[i];
-    r = mgr_scan_fwd_simple(c, j.Z, j.Up, j.Y, j.ldy, j.R, j.ldr, j.gates, j.cs, j.B, j.T, j.H, j.reverse);
+    r = mgr_scan_fwd_simple(c, j.Z, j.Up, rows[i], ldrows[i], j.R, j.ldr, j.gates, j.cs, j.B, j.T, j.H, j.reverse);
     if (r < 0) return r;
   }
   for (int i = 0; i < njobs; ++i) {   // transposed outputs the scan kernel did not write itself
     const mgr_scan_job& j = jobs[i];
     if (!j.YT || yt_done[i]) continue;
-    r = j.yt_split ? mgr_transpose_bt_split_strided(c, j.Y, j.ldy, j.YT, j.ldt, j.ytb, j.ldt, j.B, j.T, j.H)
-                   : mgr_transpose_bt_strided(c, j.Y, j.ldy, j.YT, j.ldt, j.ytb, j.ldt, j.B, j.T, j.H);
+    r = j.yt_split ? mgr_transpose_bt_split_strided(c, rows[i], ldrows[i], j.YT, j.ldt, j.ytb, j.ldt, j.B, j.T, j.H)
+                   : mgr_transpose_bt_strided(c, rows[i], ldrows[i], j.YT, j.ldt, j.ytb, j.ldt, j.B, j.T, j.H);
     if (r) return r;
   }
   r = mgr_prof_end(c, family);
   if (r) return r;
   if (status && c->tune[MGR_TUNE_SCAN_SYNC_CHECK]) return check_launch_status(c, status, "cluster scan");
   return 0;
+}
+
+int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, void* ws, size_t ws_bytes,
+                               const mgr_scan_launch_opts* opts) {
+  return scan_fwd_multi(c, njobs, jobs, ws, ws_bytes, opts, nullptr);
+}
+
+size_t mgr_lstm_scan_fwd_multi_ws_bytes(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, const mgr_scan_launch_opts* opts) {
+  size_t need = 0;
+  return scan_fwd_multi(c, njobs, jobs, nullptr, 0, opts, &need) == 0 ? need : 0;
 }
 
 int mgr_lstm_scan_fwd(mgr_ctx* c, const float* Z, const float* Up, float* Y, int ldy, const float* R, int ldr,

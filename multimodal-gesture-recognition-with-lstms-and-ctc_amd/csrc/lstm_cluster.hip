@@ -523,7 +523,7 @@ __device__ __forceinline__ void cluster_run_ks(const ClusterJob& jb, const Clust
       // (the pinned pointers lost their address space: name it, or hipcc emits flat_store - counted on lgkmcnt as well)
       typedef __attribute__((address_space(1))) float gfloat;
       typedef __attribute__((address_space(1))) f32x4 gf32x4;
-      ((gfloat*)Yp)[row * ldy + unit] = yo;
+      if (Yp) ((gfloat*)Yp)[row * ldy + unit] = yo;   // (no Y: only the transposed copy is wanted - mgr.h, mgr_scan_job)
       if (Gp) *(gf32x4*)(Gp + (row * H + unit) * 4) = (f32x4){g4.x, g4.y, g4.z, g4.w};
       if (Csp) ((gfloat*)Csp)[row * H + unit] = c;
       if (ytrow) {
@@ -875,7 +875,7 @@ __device__ __forceinline__ void cluster_run_k16(const ClusterJob& jb, const Clus
       const float yo = yv + rt;
       typedef __attribute__((address_space(1))) float gfloat;
       typedef __attribute__((address_space(1))) f32x4 gf32x4;
-      ((gfloat*)Yp)[row * ldy + unit] = yo;
+      if (Yp) ((gfloat*)Yp)[row * ldy + unit] = yo;   // (no Y: a pass over memory nobody reads is left out - mgr.h, mgr_scan_job)
       if (Gp) *(gf32x4*)(Gp + (row * H + unit) * 4) = (f32x4){g4.x, g4.y, g4.z, g4.w};
       if (Csp) ((gfloat*)Csp)[row * H + unit] = c;
       if (ytrow) {

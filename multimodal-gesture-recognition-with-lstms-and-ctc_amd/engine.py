@@ -140,6 +140,10 @@ class Schedule:
     du_split            (round 6) the recurrent weight gradient dU of a layer whose dW runs on pre-split rows is formed the same way - the
                         split rows of h_prev along time (one transposing pass over the layer's outputs) against the dZ^T rows the dW
                         product reads anyway - instead of by the f32 split-K product and its slab reduction
+    feat_rows_when_unread  the deepest encoder scans write the row-major FEAT rows even in a pass in which every reader of the encoder
+                        output takes the transposed copy FEAT^T (Engine._feat_rows_unread: a fusion layer whose projection and
+                        weight-gradient calls read FEAT^T, no trainable stream).  Default: such a pass hands its scans Y = 0 (mgr.h,
+                        mgr_scan_job) and the K-split scan step drops one 4-byte store per lane; bit-identical either way
     split_rows          (round 5) the transposed copies are written in the split row format (f16 hi / lo pairs) and the wide products
                         run as loader / matrix pipelines on pre-split operands (gemm_split.hip); False: f32 rows, converted by
                         every product that reads them (round 4's kernels)
@@ -154,7 +158,8 @@ class Schedule:
                  deepest_scan_after_fusion_proj=True, depth1_proj_ahead=True, bptt_yields_beside_scans=True,
                  fused_encoder_scans=True, fused_wide_tiles=True, bptt_direct_when_alone=False, fusion_scan_fused=True,
                  bptt_fused=False, chain_stream_priority=0, param_grads_two_streams=False, first_pass_on_encoder_stream=True,
-                 bptt_single_cu=False, du_split=True):
+                 bptt_single_cu=False, du_split=True, feat_rows_when_unread=False):
+        self.feat_rows_when_unread = bool(feat_rows_when_unread)
         self.bptt_single_cu = bool(bptt_single_cu)
         self.du_split = bool(du_split)
         self.first_pass_on_encoder_stream = bool(first_pass_on_encoder_stream)
@@ -346,6 +351,7 @@ class Engine:
         self.Y1T = {}
         self._featT = {}
         self._featT_ready = {}   # FEAT buffer -> its transposed copy was written by the scans of the current pass
+        self._feat_rows = {}     # FEAT buffer -> the current pass wrote its row-major contents (False: only FEAT^T, _feat_rows_unread)
         self._xt_split = {}      # transposed copy (device pointer) -> its rows are in the split row format (as last written)
         if self.schedule.transposed_inputs:   # (training: dropout-aware GEMMs; inference: the dense split-f16 projection reads it too)
             want = lambda p, F: bool(self.lib.mgr_lstm_input_proj_dropout_wants_transposed(self.dev.ctx, C.c_float(float(p)), int(F)))
@@ -647,14 +653,15 @@ class Engine:
         self.dev.call("mgr_transpose_bt_split" if split else "mgr_transpose_bt", X, ldx, XT, self.ldt, B, T, fin)
         self._xt_split[XT.ptr] = split
 
-    def _project_pair(self, X, ldx, pair, Ls, B, T, fin, H, XT=None, xt_ready=False):
+    def _project_pair(self, X, ldx, pair, Ls, B, T, fin, H, XT=None, xt_ready=False, x_rows=True):
         """Input projections of the two directions of one Bidirectional layer (pair = [mask, Wp, bp, Z] x 2).  With input
         dropout active the library runs each direction's K loops over the kept features only (from p >= 0.3 on) - from the
         transposed copy XT of the input where the engine keeps one (pre-split rows: the loader / matrix pipeline of gemm_split.hip;
         f32 rows: the kernels of gemm.hip); otherwise both directions go through one call that fuses them into one GEMM where that
-        saves tiles."""
-        masked = bool(pair[0]) and Ls[0].ws_sp is not None
-        unmasked_wide = not pair[0] and XT is not None and 128 <= fin <= 2048 and Ls[0].ws_sp is not None
+        saves tiles.  x_rows=False: the row-major X was not written (_feat_rows_unread) - a path that would read it is an error."""
+        masked, unmasked_wide = self._proj_kind(pair[0], XT, fin, Ls[0])
+        if not x_rows and (XT is None or not (masked or unmasked_wide) or not xt_ready):
+            raise RuntimeError("this projection reads row-major input the encoder pass left out")
         if XT is not None and (masked or unmasked_wide) and not xt_ready:   # (xt_ready: the scans that produced X wrote XT themselves, mgr_scan_job.YT)
             self._make_xt(X, ldx, XT, B, T, fin)
         split = XT is not None and self._xt_split.get(XT.ptr, False)
@@ -676,16 +683,57 @@ class Engine:
 
     def _prep_mask(self, L, train, rand, slot):
         """Returns the device pointer (or 0) of the [4,B,fin] input-dropout mask for this pass."""
-        if not train or L.p <= 0:
-            return 0
-        key = "%s/%s/mask" % (L.prefix, L.d)
+        if not self._mask_drawn(L, train, rand):
+            return 0  # (also: explicit randomness given but no mask for this layer: no dropout)
         if rand is not None:
-            if key in rand and rand[key] is not None:
-                L.mask.upload(np.asarray(rand[key], dtype=np.float32))
-                return L.mask.ptr
-            return 0  # explicit randomness given but no mask for this layer: no dropout
+            L.mask.upload(np.asarray(rand["%s/%s/mask" % (L.prefix, L.d)], dtype=np.float32))
+            return L.mask.ptr
         self.dev.call("mgr_dropout_mask", L.mask, L.mask.size, float(L.p), C.c_uint64(self._seed(slot)))
         return L.mask.ptr
+
+    @staticmethod
+    def _mask_drawn(L, train, rand):
+        """Whether a pass with this learning phase and this explicit randomness applies an input-dropout mask to direction L."""
+        if not train or L.p <= 0:
+            return False
+        key = "%s/%s/mask" % (L.prefix, L.d)
+        return rand is None or (key in rand and rand[key] is not None)
+
+    # What the products of a Bidirectional layer read their input from - decided HERE, for the calls that make them (_project_pair,
+    # _bilstm_backward) and for the encoder pass that leaves out the row-major FEAT nobody reads (_feat_rows_unread) alike.
+    @staticmethod
+    def _proj_kind(has_mask, XT, fin, L):
+        """(masked, unmasked_wide) of a projection: either one with a transposed copy XT reads XT, anything else the rows."""
+        masked = bool(has_mask) and L.ws_sp is not None
+        unmasked_wide = not has_mask and XT is not None and 128 <= fin <= 2048 and L.ws_sp is not None
+        return masked, unmasked_wide
+
+    def _pgrad_kind(self, has_mask, XinT, split, p, fin):
+        """The weight-gradient call of one direction: "ts" (pre-split rows of XinT), "t" (f32 rows of XinT) or "rows" (row-major)."""
+        if has_mask and XinT is not None and split:
+            return "ts"
+        if has_mask and XinT is not None and self.lib.mgr_lstm_param_grads_dropout_wants_transposed(
+                self.dev.ctx, C.c_float(float(p)), int(fin)):
+            return "t"
+        return "rows"
+
+    def _feat_rows_unread(self, train, rand, feat_buf, feat_split):
+        """True when nothing reads the row-major FEAT a pass with this learning phase / randomness writes into feat_buf, its scans
+        writing FEAT^T in the format feat_split says: the fusion projection and - in a pass that keeps state for a backward pass - the
+        fusion layer's weight-gradient calls take the transposed copy, and no stream is trainable (no residual add into FEAT, no
+        encoder backward over it, no dFEAT).  The deepest scans then get Y = 0 (mgr.h).  Schedule.feat_rows_when_unread keeps the rows."""
+        sp = self.spec
+        XT = self._featT.get(feat_buf.ptr)
+        if self.schedule.feat_rows_when_unread or not sp.fusion or XT is None or any(s["trainable"] for s in sp.streams):
+            return False
+        W = sp.concat_width
+        Ls = [self.dirs["fusion/fwd"], self.dirs["fusion/bwd"]]
+        drawn = [self._mask_drawn(L, train, rand) for L in Ls]
+        if not any(self._proj_kind(drawn[0], XT, W, Ls[0])):      # (_project_pair branches on the first direction's mask)
+            return False
+        if train and not self.inference_only:
+            return all(self._pgrad_kind(m, XT, feat_split, L.p, W) != "rows" for m, L in zip(drawn, Ls))
+        return True
 
     # ------------------------------------------------------------------------------------------ forward
     def _forward(self, train, rand):
@@ -749,6 +797,10 @@ class Engine:
         depth = max(len(s["layers"]) for s in sp.streams)
         feat_by_scans = True     # every stream's last layer writes FEAT (and its transposed copy) from its scan
         split_now = self._split_rows_wanted()   # the format of the transposed copies this pass's scans write
+        feat_split = bool(split_now and self._ts_shape(W))
+        # every reader of this pass's encoder output takes FEAT^T: the scans that write both leave the row-major copy out
+        no_rows = self._feat_rows_unread(train, rand, feat_buf, feat_split)
+        self._feat_rows[feat_buf.ptr] = not no_rows
         for k in range(depth):
             jobs = []
             for si, s in enumerate(sp.streams):
@@ -796,8 +848,10 @@ class Engine:
                             R, ldr = self.Y1[name].view(di * H, (1,)), 2 * H
                         if feat_buf.ptr in self._featT:
                             YT, ytb = self._featT[feat_buf.ptr].ptr + (col + di * H) * self.ldt * 4, W * self.ldt
-                            yt_fmt = int(split_now and self._ts_shape(W))
+                            yt_fmt = int(feat_split)
                             self._xt_split[self._featT[feat_buf.ptr].ptr] = bool(yt_fmt)
+                            if no_rows:
+                                Y, ldy = 0, 0
                     keep = save and L.trainable
                     jobs.append(dict(Z=Z, Up=L.Up, Y=Y, ldy=ldy, R=R, ldr=ldr, gates=L.gates if keep else 0,
                                      cs=L.cs if keep else 0, B=B, T=T, H=H, reverse=L.reverse, YT=YT, ytb=ytb,
@@ -850,7 +904,7 @@ class Engine:
             # pre-split products that fit on a CU beside a scan workgroup, not the 8-wave ones that wait for the scan to end)
             with self._narrow_tiles(self._beside_scans and not self._wide_ok):
                 self._project_pair(feat_buf, W, pair, Ls_pair, B, T, W, Hf, XT=self._featT.get(feat_buf.ptr),
-                                   xt_ready=self._featT_ready.get(feat_buf.ptr, False))
+                                   xt_ready=self._featT_ready.get(feat_buf.ptr, False), x_rows=self._feat_rows.get(feat_buf.ptr, True))
             dev.record(self.EV_FPROJ)   # (the next step's depth-1 scan is launched after these GEMMs, _enqueue_next_encoders)
             if self._gate_words[0] is not None:
                 # (Schedule.fused_encoder_scans: the fusion scan's 56 workgroups must land on the CUs the next batch's deepest encoder
@@ -937,12 +991,15 @@ class Engine:
         be in flight at the same time when steps are pipelined).  form: mgr.h MGR_SCAN_FORM_* (AUTO: the context's MGR_TUNE_SCAN_FORM);
         seq_word: address of the host word that receives the launch number (0: not wanted)."""
         arr = _capi.make_scan_jobs(jobs)
-        need = self.lib.mgr_lstm_scan_multi_ws_bytes(len(jobs), arr)
+        opts = _capi.make_launch_opts(form, seq_word)
+        # (what THIS launch needs: a job without Y gets row scratch only where its kernel does not write the transposed copy itself)
+        need = self.lib.mgr_lstm_scan_fwd_multi_ws_bytes(self.dev.ctx, len(jobs), arr, C.byref(opts))
+        if need == 0:
+            _capi.check(-1, self.lib)
         ws = getattr(self, wsname, None)
         if ws is None or ws.nbytes < need:
             ws = self.mem.bytes(need)
             setattr(self, wsname, ws)
-        opts = _capi.make_launch_opts(form, seq_word)
         _capi.check(self.lib.mgr_lstm_scan_fwd_multi_ex(self.dev.ctx, len(jobs), arr, ws.ptr, ws.nbytes, C.byref(opts)))
 
     def resident_wait_stats(self):
@@ -1873,7 +1930,7 @@ class Engine:
         if sp.fusion:
             Hf = sp.fusion["H"]
             bargs = ("fusion", self.dYF, 2 * Hf, self._featin, W, W, self.YF, 2 * Hf, self.dFEAT if any_tr_stream else None, W)
-            bkw = dict(defer_param_grads=defer, XinT=self._featT.get(self._featin.ptr))
+            bkw = dict(defer_param_grads=defer, XinT=self._featT.get(self._featin.ptr), xin_rows=self._feat_rows.get(self._featin.ptr, True))
             if defer and late_ok and not any_tr_stream:
                 late_bptt = lambda: self._bilstm_backward(*bargs, **bkw)
             else:
@@ -2013,11 +2070,12 @@ class Engine:
         dev.record(self.EV_ENC[self._feat_ring.index(nxt)])
         self._prefetched = nxt
 
-    def _bilstm_backward(self, prefix, dY, lddy, Xin, ldx, fin, Hbuf, ldh, dX, lddx, defer_param_grads=False, XinT=None):
+    def _bilstm_backward(self, prefix, dY, lddy, Xin, ldx, fin, Hbuf, ldh, dX, lddx, defer_param_grads=False, XinT=None, xin_rows=True):
         """BPTT + parameter grads of one Bidirectional layer (both directions in one persistent launch).
         defer_param_grads: return the dW/dU/db GEMM launches as a closure instead of enqueuing them now.
         XinT: the transposed copy of Xin the forward projection was fed (same step), if the engine keeps one - the
-        dropout-aware dW then reads both of its operands along time."""
+        dropout-aware dW then reads both of its operands along time.
+        xin_rows=False: the row-major Xin was not written (_feat_rows_unread) - a weight-gradient call that would read it is an error."""
         dev, B, T = self.dev, self.B, self.T
         jobs = []
         for di, dname in enumerate(("fwd", "bwd")):
@@ -2060,7 +2118,10 @@ class Engine:
                 mptr = self._masks.get((L.prefix, L.d), 0)
                 if two:
                     dev.stream(self.PG_STREAM if di == 1 else 0)
-                if mptr and XinT is not None and self._xt_split.get(XinT.ptr, False):
+                kind = self._pgrad_kind(mptr, XinT, XinT is not None and self._xt_split.get(XinT.ptr, False), L.p, fin)
+                if kind == "rows" and not xin_rows:
+                    raise RuntimeError("this weight-gradient call reads row-major input the encoder pass left out")
+                if kind == "ts":
                     # (the projection of this step left the kept lists of this very mask in its workspace: not built again)
                     pws = L.ws_sp if (L.ws_sp is not None and L.lists_mask == mptr) else 0
                     L.lists_mask = 0
@@ -2072,8 +2133,7 @@ class Engine:
                     with self._narrow_tiles(beside_scans and not wide_ok):
                         dev.call("mgr_lstm_param_grads_dropout_ts", XinT, self.ldt, mptr, float(L.p), Hbuf.view(di * H, (1,)), ldh, L.dZ,
                                  L.gWp, L.gUp, L.gbp, B, T, fin, H, L.reverse, L.ws_pg, L.ws_pg.nbytes, L.dzmax, L.dbsum, pws, hst)
-                elif mptr and XinT is not None and self.lib.mgr_lstm_param_grads_dropout_wants_transposed(
-                        dev.ctx, C.c_float(float(L.p)), int(fin)):
+                elif kind == "t":
                     need = self.lib.mgr_lstm_param_grads_dropout_t_ws_bytes(B, T, fin, H, self.ldt)
                     if L.ws_pg.nbytes < need:          # (+ the transposed dZ; first use only)
                         L.ws_pg = self.mem.bytes(need)
