@@ -93,6 +93,47 @@ int mgr_add_gaussian_noise(mgr_ctx* ctx, const float* X, float* Y, size_t n, flo
 /* mask[i] = (uniform(seed,i) >= p) ? 1/(1-p) : 0  - Keras dropout mask (inverted dropout) */
 int mgr_dropout_mask(mgr_ctx* ctx, float* mask, size_t n, float p, uint64_t seed);
 
+/* ---- K1b: train-time sequence augmentation: a length-preserving time warp shared by the S streams of a sample, time /
+ * feature masks per stream (SpecAugment), at most one blanked stream per sample (ModDrop), and K1's noise, in one pass per stream.
+ * Both calls are deterministic functions of their arguments: no atomics, no workspace.
+ *
+ * The PLAN is one int32 row of len = K + 2 + 2 S (n_t + n_f) per sample (that is what the _plan_len call returns; 0 for counts out
+ * of range):
+ *   [0 .. K]                        q_0 .. q_K, the warp's target boundaries.  The source boundaries are a_j = j (T - 1) / K (integer
+ *                                   division) and are not stored; q_j = a_j + d_j, d_j in [-D, D] for 0 < j < K, q_0 = 0, q_K = T - 1.
+ *                                   2 D < min_j (a_{j+1} - a_j) is required (targets strictly increasing); K = 1 or D = 0: identity.
+ *   [K + 1]                         the dropped stream's index, or -1
+ *   [K + 2 + 2 (n_t + n_f) s ...]   stream s: n_t (start, width) pairs of time masks, then n_f pairs of feature masks.  A stream
+ *                                   that uses fewer masks than the row has slots leaves the others at (0, 0).
+ * DRAW ORDER: entry p of sample b's row is drawn from the 32-bit output u of the stateless generator of K1 (top half of the 64-bit
+ * mix, as the dropout masks) at index b len + p under `seed`; entries that are not drawn (q_0, q_K, unused slots) leave their index
+ * unused.  An integer in [lo, hi] is lo + ((uint64) u (hi - lo + 1) >> 32).  d_j: [-D, D] at p = j.  A mask's width: [0, W] at its
+ * width entry; its start: [0, axis - width] at its start entry (axis T or the stream's F).  The dropped stream: r = u >> 8 at
+ * p = K + 1; dropped when r < drop_thresh = (uint32) (stream_drop 2^24), the stream (r S) / drop_thresh from the same r.  No float
+ * enters the plan.
+ * stream_cfg: HOST array [S][MGR_AUGMENT_STREAM_COLS] = F, time masks used (<= n_t), Wt (<= T), feature masks used (<= n_f),
+ * Wf (<= F) of each stream.  drop_thresh < 2^24, and 0 when S = 1.  T <= MGR_AUGMENT_MAX_T.
+ *
+ * The APPLY call, once per stream: Y[b, t, f] = noise(mask(warp(X))) over [B, T, F]; X != Y.  Frame t lies in the first segment j
+ * with t <= q_{j+1}: num = (t - q_j) (a_{j+1} - a_j), den = q_{j+1} - q_j, i0 = a_j + num / den, rem = num % den.  rem == 0: the
+ * value is X[b, i0, f] copied verbatim (-0.0, NaN payloads and denormals stay; row i0 + 1 is not read - at t = T - 1 there is none).
+ * Otherwise frac = (float) rem / (float) den and the value is x0 + frac * (x1 - x0), each of the four operations rounded to float32
+ * on its own (no fused multiply-add: a float32 restatement gives the same bits).  A frame inside a time mask of this stream, a
+ * feature inside a feature mask, or every element when this stream is the sample's dropped one, becomes `fill`.  stddev > 0 adds
+ * K1's noise under `seed`, keyed by the flat element index (b T + t) F + f with K1's pairing of elements 2i, 2i + 1 - each element of
+ * a pair resolves its own (b, t, f) - so apply at stddev is bit for bit K1 over apply at stddev 0; stddev == 0 adds nothing.
+ * T F < 2^31.  Device time of both calls: profiling family MGR_K_MISC. */
+#define MGR_AUGMENT_MAX_SEGMENTS 16
+#define MGR_AUGMENT_MAX_STREAMS 8
+#define MGR_AUGMENT_MAX_MASKS 8
+#define MGR_AUGMENT_MAX_T 32767
+#define MGR_AUGMENT_STREAM_COLS 5
+int mgr_augment_plan_len(int S, int K, int n_t, int n_f);
+int mgr_augment_plan(mgr_ctx* ctx, int B, int T, int S, int K, int D, int n_t, int n_f, const int32_t* stream_cfg, uint32_t drop_thresh,
+                     uint64_t seed, int32_t* plan);
+int mgr_augment_apply(mgr_ctx* ctx, const float* X, float* Y, const int32_t* plan, int B, int T, int F, int S, int K, int n_t, int n_f,
+                      int stream, float fill, float stddev, uint64_t seed);
+
 /* ---- K2/K3/K7: Bidirectional(LSTM) (multimodal_fusion/multimodal.py:109-118,159-168;
  *      audio_network/speech_lstm_ctc_words.py:56-77; skeletal_network/skeletal_lstm_ctc.py:309-335) ---- */
 /* Keras layout <-> packed layout for a [rows, 4H] matrix (W: rows=F, U: rows=H, b: rows=1). */

@@ -42,6 +42,9 @@ SIGNATURES = {
     "mgr_prof_reset": (i32, [vp]),
     "mgr_add_gaussian_noise": (i32, [vp, vp, vp, sz, C.c_float, u64]),
     "mgr_dropout_mask": (i32, [vp, vp, sz, C.c_float, u64]),
+    "mgr_augment_plan_len": (i32, [i32, i32, i32, i32]),
+    "mgr_augment_plan": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_uint32, u64, vp]),
+    "mgr_augment_apply": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, u64]),
     "mgr_lstm_pack": (i32, [vp, vp, vp, i32, i32, i32]),
     "mgr_transpose": (i32, [vp, vp, vp, i32, i32]),
     "mgr_lstm_input_proj": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32]),
@@ -184,6 +187,7 @@ class JointStream(C.Structure):
 
 
 JOINT_MAX_STREAMS, JOINT_MAX_PHRASE_WORDS = 4, 8       # MGR_JOINT_MAX_* of include/mgr.h
+AUGMENT_MAX_SEGMENTS, AUGMENT_MAX_STREAMS, AUGMENT_MAX_MASKS, AUGMENT_MAX_T, AUGMENT_STREAM_COLS = 16, 8, 8, 32767, 5   # MGR_AUGMENT_*
 
 
 def make_joint_streams(streams):
@@ -404,6 +408,13 @@ class Device:
 
     def bytes(self, nbytes):
         return self.empty((int(nbytes + 3) // 4,), np.float32)
+
+    def free(self, *arrays):
+        """Free some of this Device's arrays before the rest (temporaries of a call on a Device that lives on)."""
+        dead = set(id(a) for a in arrays)
+        for a in arrays:
+            a.free()
+        self._arrays = [a for a in self._arrays if id(a) not in dead]
 
     # -- streams / timing ------------------------------------------------------------------------
     def sync(self):

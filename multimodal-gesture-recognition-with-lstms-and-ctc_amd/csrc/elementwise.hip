@@ -1,6 +1,7 @@
 // HBM-bound elementwise / small reduction kernels: noise, dropout masks, weight packing, Adam+clip,
 // max-norm, mean, frame argmax.  All are grid-stride, coalesced, one launch each.
 #include "common.h"
+#include "noise.h"
 
 namespace {
 
@@ -13,18 +14,14 @@ static inline int grid_for(size_t n, int per_block = kBlock) {
 }
 
 __global__ void k_add_noise(const float* __restrict__ X, float* __restrict__ Y, size_t n, float stddev, uint64_t seed) {
-  // Box-Muller on two 24-bit uniforms per pair of elements
+  // Box-Muller on two 24-bit uniforms per pair of elements (noise.h)
   size_t npair = (n + 1) / 2;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npair; i += (size_t)gridDim.x * blockDim.x) {
-    uint64_t r = mgr_mix64(seed * 0xD1342543DE82EF95ull + i);
-    float u1 = ((float)((uint32_t)(r >> 40)) + 1.0f) * (1.0f / 16777216.0f);  // (0,1]
-    float u2 = (float)((uint32_t)(r >> 8) & 0xFFFFFF) * (1.0f / 16777216.0f);
-    float rad = sqrtf(-2.0f * logf(u1)) * stddev;
-    float s, c;
-    sincosf(6.283185307179586f * u2, &s, &c);
+    float rad, s, c;
+    mgr_noise_pair(seed, i, stddev, &rad, &c, &s);
     size_t e = 2 * i;
-    Y[e] = X[e] + rad * c;
-    if (e + 1 < n) Y[e + 1] = X[e + 1] + rad * s;
+    Y[e] = mgr_noise_add(X[e], rad, c);
+    if (e + 1 < n) Y[e + 1] = mgr_noise_add(X[e + 1], rad, s);
   }
 }
 

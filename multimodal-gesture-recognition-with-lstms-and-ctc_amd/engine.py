@@ -14,6 +14,7 @@ import math
 import numpy as np
 
 from . import _capi, decoding
+from . import augment as augment_mod
 from ._capi import Device, DeviceArray
 from .spec import frontend_layers, input_width
 
@@ -213,6 +214,7 @@ class Engine:
         self.rng_step = 0     # advances per forward pass that draws randomness
         self._risk = None     # set_risk: the minimum-risk training mode's settings and buffers
         self._entropy = None  # set_entropy: the entropy-regularised training mode's weight and buffers
+        self._augment = None  # set_augment: the train-time input augmentation's settings and buffers
         self._build()
 
     # ------------------------------------------------------------------------------------------ build
@@ -746,10 +748,10 @@ class Engine:
         if train:
             self.rng_step += 1
 
-    def _enqueue_encoders(self, train, rand, feat_buf, es, rng_step, hold_scans_for=None):
+    def _enqueue_encoders(self, train, rand, feat_buf, es, rng_step, hold_scans_for=None, augment=False):
         """Noise + every encoder depth (input-projection GEMMs, then all recurrences of the depth in one multi-scan
-        call), written into feat_buf.  Everything is enqueued on stream `es`."""
-        for tag, k in self._encoder_phases(train, rand, feat_buf, es, rng_step):
+        call), written into feat_buf.  Everything is enqueued on stream `es`.  augment: _encoder_phases'."""
+        for tag, k in self._encoder_phases(train, rand, feat_buf, es, rng_step, augment=augment):
             if tag != "projected":
                 continue
             if hold_scans_for is not None and k >= 1:
@@ -759,7 +761,7 @@ class Engine:
                 self.dev.stream(es)
                 self.dev.wait(es, hold_scans_for)
 
-    def _encoder_phases(self, train, rand, feat_buf, es, rng_step, first_stream=None, z_first=None, seq_words=None):
+    def _encoder_phases(self, train, rand, feat_buf, es, rng_step, first_stream=None, z_first=None, seq_words=None, augment=False):
         """Generator form of the encoder pass: yields ("projected", k) after the projection GEMMs of depth k are enqueued
         (before its scan) and ("scanned", k) after its multi-scan launch, so that a caller can interleave work of another
         stream at those points.  Re-selects stream `es` after every resume; self.rng_step is only switched to `rng_step`
@@ -769,7 +771,10 @@ class Engine:
         Zbuf - the caller orders `es` behind them before it resumes the generator.
         seq_words: dict {depth k: address of a host word} - the scan launch of depth k hands its launch number to that word (looked
         up when the launch is enqueued, so a caller may fill the dict while the generator is suspended).  The FORM of each scan
-        launch is self._enc_scan_form at the moment it is enqueued (MGR_SCAN_FORM_*: the schedule's choice for that launch)."""
+        launch is self._enc_scan_form at the moment it is enqueued (MGR_SCAN_FORM_*: the schedule's choice for that launch).
+        augment: this is the pass of a TRAINING STEP (only enqueue_train_step's passes say so: the train-phase passes of
+        loss_on_batch / forward_train_phase stay what they are) - with set_augment on, the plan of THIS pass's rng_step is drawn and
+        every stream goes through mgr_augment_apply, its noise included, in mgr_add_gaussian_noise's place."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         W = sp.concat_width
         save = train and not self.inference_only
@@ -782,11 +787,20 @@ class Engine:
             cols[s["name"]] = col
             col += sp.stream_width(s)
         dev.stream(es if first_stream is None else first_stream)
+        aug = self._augment if (augment and train and rand is None) else None
+        if aug is not None:
+            # one plan per pass, from the pass's own step counter: a prefetched pass draws the plan of the step that consumes it, and
+            # a stale pass that is redone draws the same plan again
+            augment_mod.enqueue_plan(dev, aug["cfg"], aug["table"], B, T, self._seed(augment_mod.PLAN_SLOT), aug["plan"])
         # GaussianNoise (K1) per stream
         for si, s in enumerate(sp.streams):
             name = s["name"]
             X = self.Xin[name]
-            if train and rand is None and s["noise"] > 0:
+            if aug is not None:
+                # warp, masks, dropped stream and the stream's noise in one pass; the resident input stays pristine
+                augment_mod.enqueue_apply(dev, aug["cfg"], si, X, self.X[name], aug["plan"], B, T, float(s["noise"]), self._seed(900 + si))
+                X = self.X[name]
+            elif train and rand is None and s["noise"] > 0:
                 # on device; the resident input stays pristine for the next step
                 dev.call("mgr_add_gaussian_noise", X, self.X[name], X.size, float(s["noise"]),
                          C.c_uint64(self._seed(900 + si)))
@@ -1539,6 +1553,9 @@ class Engine:
         until then (0.9 - 3.9 ms per step in the traces of round 5)."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         sch, ES = self.schedule, self.ES
+        if self._augment is not None and rand is not None:
+            raise ValueError("a training step with set_augment on was given `rand`: host-supplied randomness has no augmentation plan "
+                             "(set_augment(None) first)")
         self._bind()
         pipelined = prefetch_next and rand is None and self.can_pipeline and sch.pipeline
         depth = max(len(s_["layers"]) for s_ in sp.streams)
@@ -1588,7 +1605,7 @@ class Engine:
                 cur = self._feat_ring[self._feat_idx]
                 self._enc_scan_form = _capi.SCAN_FORM_FUSED
                 try:
-                    self._enqueue_encoders(True, None, cur, ES, self.rng_step)
+                    self._enqueue_encoders(True, None, cur, ES, self.rng_step, augment=True)
                 finally:
                     self._enc_scan_form = _capi.SCAN_FORM_AUTO
                 dev.wait(0, ES)
@@ -1597,7 +1614,7 @@ class Engine:
                 if upload:
                     self._upload_inputs(inputs, rand, True)
                 cur = self._feat_ring[self._feat_idx]
-                self._enqueue_encoders(True, rand, cur, 0, self.rng_step)
+                self._enqueue_encoders(True, rand, cur, 0, self.rng_step, augment=True)
         else:
             cur = have
             # this step's encoder pass (enqueued by the previous call) must be complete: the event behind its deepest scan - not
@@ -1868,6 +1885,52 @@ class Engine:
         dev.call("mgr_dense_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self.dLogits, self._wview("dense/W"), self._gview("dense/W"),
                  self._gview("dense/b"), dA, ldda, B, T, D, Cn, self.ws_dense, self.ws_dense.nbytes)
 
+    def set_augment(self, cfg):
+        """Train-time input augmentation (augment.py): with cfg - a dict over augment.DEFAULTS - the encoder pass of every
+        TRAINING STEP reads, in the place of the noised copy of its batch, Y = noise(mask(warp(X))): a length-preserving time warp
+        shared by the streams of a sample, time / feature masks per stream, at most one blanked stream per sample, then the stream's
+        GaussianNoise - one mgr_augment_plan per pass (seed slot 950 at the pass's step counter) and one mgr_augment_apply per stream
+        in mgr_add_gaussian_noise's place (slot 900 + i as before).  The resident inputs stay pristine; labels and lengths are not
+        touched (the warp keeps T).  loss_on_batch / forward_train_phase / predict / predict_stream are what they are without the
+        mode.  Combines with set_risk / set_entropy.  A training step given `rand` is refused while the mode is on.  None: the mode's
+        buffers are freed and a step makes exactly the calls it made before.  Single GPU; a cfg that is refused leaves the mode as
+        it was."""
+        if cfg is None:
+            self._release_augment()
+            return
+        if self.comm is not None:
+            raise NotImplementedError("input augmentation is single-GPU: data-parallel augmentation is not implemented")
+        if self.inference_only:
+            raise ValueError("set_augment on an inference-only engine")
+        norm = augment_mod.normalize_config(cfg, self.spec, self.T)
+        n = augment_mod.plan_len(norm)
+        self._release_augment()     # (the cfg is good: only now does the mode set before go)
+        self._drop_prefetched()     # (an encoder pass enqueued ahead of its step was made without the mode: it is redone under it)
+        dev, B, T = self.mem, self.B, self.T
+        a = dict(cfg=norm, table=augment_mod.stream_table(norm), plan=dev.empty((B, n), np.int32), own_x=[])
+        for s in self.spec.streams:
+            if s["name"] not in self.X:     # (a stream without GaussianNoise has had no copy to write into)
+                self.X[s["name"]] = dev.empty((B, T, s["F"]))
+                a["own_x"].append(s["name"])
+        a["bufs"] = [a["plan"]] + [self.X[k] for k in a["own_x"]]
+        self._augment = a
+
+    def _release_augment(self):
+        if self._augment is not None:
+            self._drop_prefetched()     # (an encoder pass enqueued ahead was made under the mode that goes: it is redone, same randomness)
+            self.dev.sync()     # (a step that uses the buffers may be in flight)
+            for k in self._augment["own_x"]:
+                del self.X[k]
+            self.mem.release(self._augment["bufs"])
+            self._augment = None
+
+    def _drop_prefetched(self):
+        """Forget the encoder pass a pipelined step enqueued for its successor: the next step runs its own (what a step does whose
+        caller did not come back with the announced batch)."""
+        if self._prefetched is not None:
+            self.dev.wait(0, self.ES)
+            self._prefetched = None
+
     def _enqueue_trainable_part(self, cur, rand, beside_scans, defer, late_ok, own_inputs, apply_update):
         """Steps 2 and 3 of a training step on stream 0 - fusion layer, head, CTC, the loss read-back point, the backward pass up to
         what `defer` / `late_ok` hold back - and the closure `finish(gate=None)` that enqueues the rest (held-back BPTT, dW / dU / db
@@ -1983,7 +2046,8 @@ class Engine:
             self._upload_inputs(next_inputs, None, True, stream=ES)
             self._xin_user[self._xin_slot] = consumer_step
         split_first = bool(split_first and self.Z1buf)
-        phases = self._encoder_phases(True, None, nxt, ES, rng_step, z_first=self.Z1buf if split_first else None, seq_words=seq_words)
+        phases = self._encoder_phases(True, None, nxt, ES, rng_step, z_first=self.Z1buf if split_first else None, seq_words=seq_words,
+                                      augment=True)
         for tag, k in phases:
             if tag == "projected" and k == 0 and split_first and depth > 1:
                 dev.stream(0)
@@ -2038,7 +2102,7 @@ class Engine:
             self._xin_user[self._xin_slot] = self._step_id   # (already advanced: the step that will consume it)
         if not defer:
             finish()
-            self._enqueue_encoders(True, None, nxt, ES, self.rng_step, hold_scans_for=0)
+            self._enqueue_encoders(True, None, nxt, ES, self.rng_step, hold_scans_for=0, augment=True)
         else:
             # The dW/dU GEMMs of THIS step and the optimizer are held back until the next step's deepest projection GEMMs are
             # done and then run beside its deepest encoder scan: GEMM next to GEMM gains nothing, whereas a big scan leaves
@@ -2048,7 +2112,7 @@ class Engine:
             # depth-1 scan is launched after this step's fusion projections (a persistent launch placed among chip-filling
             # GEMMs gets a poor CU set), and only the deepest scan - the one that overwrites the FEAT buffer the previous
             # step's dW GEMMs read - waits for that step.
-            for tag, k in self._encoder_phases(True, None, nxt, ES, self.rng_step):
+            for tag, k in self._encoder_phases(True, None, nxt, ES, self.rng_step, augment=True):
                 if tag != "projected":
                     continue
                 if ahead and k == 0 and not free_running:

@@ -214,6 +214,7 @@ class Model:
         self._weights = None      # host copy (Keras layouts) until an engine exists
         self._risk = None         # set_risk: the minimum-risk training mode's settings (carried over when the engine is rebuilt)
         self._entropy = None      # set_entropy: the entropy-regularised training mode's settings (carried over likewise)
+        self._augment = None      # set_augment: the train-time input augmentation's settings (carried over likewise)
         self.last_logs = {}       # train_on_batch: the scalars of its step ("loss"; with set_risk also "risk" and "ctc_loss", with
                                   # set_entropy "ctc_loss" and "entropy")
         self._predict_view = False
@@ -388,6 +389,24 @@ class Model:
             self.set_risk(kwargs["risk"])
         if "entropy" in kwargs:
             self.set_entropy(kwargs["entropy"])
+        if "augment" in kwargs:
+            self.set_augment(kwargs["augment"])
+
+    def set_augment(self, cfg):
+        """Train-time input augmentation (Engine.set_augment, augment.py): cfg = dict(segments=, max_shift=, time_masks=,
+        time_width=, feature_masks=, feature_width=, fill=, stream_drop=, streams={name: overrides}) or a part of it - every training
+        step's encoders read a time-warped, masked copy of the batch with at most one stream of a sample blanked, made on the device
+        from the step's own randomness; validation, predict and the decoders see the batch as it is.  Combines with set_risk /
+        set_entropy.  None: off.  Single GPU only; a cfg that is refused leaves the mode as it was."""
+        if cfg is not None and self.comm is not None:
+            raise NotImplementedError("input augmentation is single-GPU: data-parallel augmentation is not implemented")
+        if cfg is not None:
+            from . import augment
+            e = self._engine
+            augment.normalize_config(cfg, self.spec, e.T if e is not None else None)     # (refused here: nothing has changed)
+        if self._engine is not None and not self._engine.inference_only:
+            self._engine.set_augment(None if cfg is None else dict(cfg))
+        self._augment = None if cfg is None else dict(cfg)
 
     def set_risk(self, cfg):
         """Minimum-risk fine-tuning of a CTC-trained network (Engine.set_risk): cfg = dict(top_paths=8, beam_width=16,
@@ -433,6 +452,8 @@ class Model:
             raise NotImplementedError("minimum-risk training is single-GPU: data-parallel risk training is not implemented")
         if self._entropy is not None:
             raise NotImplementedError("entropy-regularised training is single-GPU: data-parallel entropy training is not implemented")
+        if self._augment is not None:
+            raise NotImplementedError("input augmentation is single-GPU: data-parallel augmentation is not implemented")
         self.comm, self.world = comm, int(world)
         if getattr(comm, "dev", None) is not None:
             self.device = comm.dev
@@ -456,6 +477,8 @@ class Model:
             self._engine.set_risk(self._risk)
         if self._entropy is not None and not inference_only:
             self._engine.set_entropy(self._entropy)
+        if self._augment is not None and not inference_only:
+            self._engine.set_augment(self._augment)
         if opt_state is not None and not inference_only:
             self._engine.m.upload(opt_state[0])
             self._engine.v.upload(opt_state[1])
