@@ -134,6 +134,22 @@ int mgr_augment_plan(mgr_ctx* ctx, int B, int T, int S, int K, int D, int n_t, i
 int mgr_augment_apply(mgr_ctx* ctx, const float* X, float* Y, const int32_t* plan, int B, int T, int F, int S, int K, int n_t, int n_f,
                       int stream, float fill, float stddev, uint64_t seed);
 
+/* ---- K1c: per-sample sequence lengths.  Zeroes buf[b, t, 0:row) for every t >= clip(seq_len[b], 0, T) of each job's
+ * [B, T, row] float32 buffer (consecutive frames ld >= row floats apart; the ld - row floats between rows are not written) and
+ * writes nothing else.  One launch per MGR_SEQ_MAX_JOBS jobs; its work is that of the tails: a sample with seq_len[b] >= T costs
+ * the read of its length.  16-byte stores where row % 4 == 0, ld % 4 == 0 and buf is 16-byte aligned, single floats otherwise.
+ * seq_len: DEVICE array of B int32, one for the call - every job has the same B (<= 65535); T may differ between jobs.
+ * njobs == 0, B == 0 and T == 0 enqueue nothing.  A NULL buf or seq_len, row <= 0, ld < row or differing B are refused before
+ * anything is enqueued.  What it is for: a reverse recurrence whose gate pre-activations Z [B, T, 4H] are zero in a sample's tail
+ * keeps h = c = 0 through it and starts the real frames as if the sequence ended there; with its saved gates [B, T, H, 4] zeroed
+ * there as well, the BPTT's dZ is exactly 0 in the tail.  No atomics, no workspace.  Profiling family MGR_K_MISC. */
+#define MGR_SEQ_MAX_JOBS 16
+typedef struct mgr_seq_fill_job {
+  float* buf;
+  int row, ld, B, T;
+} mgr_seq_fill_job;
+int mgr_seq_zero_tail(mgr_ctx* ctx, int njobs, const mgr_seq_fill_job* jobs, const int32_t* seq_len);
+
 /* ---- K2/K3/K7: Bidirectional(LSTM) (multimodal_fusion/multimodal.py:109-118,159-168;
  *      audio_network/speech_lstm_ctc_words.py:56-77; skeletal_network/skeletal_lstm_ctc.py:309-335) ---- */
 /* Keras layout <-> packed layout for a [rows, 4H] matrix (W: rows=F, U: rows=H, b: rows=1). */

@@ -45,6 +45,7 @@ SIGNATURES = {
     "mgr_augment_plan_len": (i32, [i32, i32, i32, i32]),
     "mgr_augment_plan": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_uint32, u64, vp]),
     "mgr_augment_apply": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, u64]),
+    "mgr_seq_zero_tail": (i32, [vp, i32, vp, vp]),
     "mgr_lstm_pack": (i32, [vp, vp, vp, i32, i32, i32]),
     "mgr_transpose": (i32, [vp, vp, vp, i32, i32]),
     "mgr_lstm_input_proj": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32]),
@@ -178,6 +179,20 @@ class ScanBwdJob(C.Structure):
 class ScanLaunchOpts(C.Structure):
     """struct mgr_scan_launch_opts"""
     _fields_ = [("struct_size", C.c_uint), ("form", i32), ("seq_out", vp)]
+
+
+class SeqFillJob(C.Structure):
+    """struct mgr_seq_fill_job (K1c)"""
+    _fields_ = [("buf", vp), ("row", i32), ("ld", i32), ("B", i32), ("T", i32)]
+
+
+def make_seq_fill_jobs(jobs):
+    """jobs: list of (buf, row, ld, B, T) - buf a DeviceArray or a device address."""
+    arr = (SeqFillJob * max(len(jobs), 1))()
+    for a, (buf, row, ld, B, T) in zip(arr, jobs):
+        a.buf = buf.ptr if isinstance(buf, DeviceArray) else (buf or None)
+        a.row, a.ld, a.B, a.T = int(row), int(ld), int(B), int(T)
+    return arr
 
 
 class JointStream(C.Structure):

@@ -10,6 +10,9 @@ Two sample stores provide per-file feature matrices and label rows:
                      (audio_network/feature_extraction.py) instead of read from HTK-made CSVs.
 The batch contract (dict keys, float64 arrays, np.ones initialisation, post-padding with zeros, labels padded with
 -1, the blank substitution for empty label rows, input_length = maxlen - 2) is the reference's.
+With ``true_lengths=True`` (not in the reference) a batch also carries ``seq_length`` - per sample the largest
+min(maxlen, frames) over its streams, maxlen for an all-ones fallback row - and input_length = max(0, seq_length - 2): the engine
+then computes what each sample would give alone at its own length, whatever the padding holds.
 """
 import os
 import random
@@ -158,9 +161,11 @@ class BaseDataGenerator(Callback):
     model_json_name = "model.json"
     model_weights_name = "weights.h5"
 
-    def _setup(self, minibatch_size, maxlen, nb_classes, dataset, val_split, absolute_max_sequence_len, store, rank=0, world=1):
+    def _setup(self, minibatch_size, maxlen, nb_classes, dataset, val_split, absolute_max_sequence_len, store, rank=0, world=1,
+               true_lengths=False):
         Callback.__init__(self)
         self.minibatch_size = minibatch_size
+        self.true_lengths = bool(true_lengths)
         # data parallel (not in the reference): `minibatch_size` stays the GLOBAL batch - file lists, split, wrap-around
         # and shuffles are those of the single-process generator on every rank - and get_batch assembles only this rank's
         # contiguous slice of it: rank-aware batch == parallel.shard_batch(full batch, rank, world)
@@ -228,6 +233,7 @@ class BaseDataGenerator(Callback):
         labels = np.ones([size, self.absolute_max_sequence_len])
         input_length = np.zeros([size, 1])
         label_length = np.zeros([size, 1])
+        seq_length = np.zeros([size, 1], np.int32)
         for i, fid in enumerate(batch):
             lab_seq = self.store.labels(fid) if self.dataset != 'final' else np.array([0], np.float32)
             lab_seq = self.expand_labels(np.asarray(lab_seq, np.float32))
@@ -239,6 +245,7 @@ class BaseDataGenerator(Callback):
                 row[0] = self.blank_label[0]
                 labels[i, :] = row
                 label_length[i] = 1
+                seq_length[i] = self.maxlen
             else:
                 for key, modality, attr in self.streams:
                     feats = np.asarray(self.store.features(fid, modality))
@@ -248,13 +255,17 @@ class BaseDataGenerator(Callback):
                         X[key][i, n:, :] = 0.0
                     else:
                         X[key][i, :, :] = 1.0
+                        n = self.maxlen
+                    seq_length[i] = max(int(seq_length[i, 0]), n)
                 label_length[i] = min(lab_seq.shape[0], self.absolute_max_sequence_len)
                 row = -np.ones(self.absolute_max_sequence_len)
                 n = int(label_length[i, 0])
                 row[:n] = lab_seq[-n:] if lab_seq.shape[0] > n else lab_seq   # pad_sequences truncates 'pre' by default
                 labels[i, :] = row
-            input_length[i] = self.maxlen - 2
+            input_length[i] = max(0, int(seq_length[i, 0]) - 2) if self.true_lengths else self.maxlen - 2
         inputs = dict(X)
+        if self.true_lengths:
+            inputs['seq_length'] = seq_length
         inputs['the_labels'] = labels
         inputs['input_length'] = input_length
         inputs['label_length'] = label_length

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _capi, decoding
 from . import augment as augment_mod
+from . import seqlen
 from ._capi import Device, DeviceArray
 from .spec import frontend_layers, input_width
 
@@ -316,6 +317,13 @@ class Engine:
         self._xin_copied = [False, False]   # EV_XIN_COPIED / EV_LAB_COPIED of set 0 / 1 have been recorded
         self._lab_copied = [False, False]
         self._lab_user = [-1, -1]
+        # per-sample sequence lengths (seqlen.KEY of an input dict): the device array of the batch in input set 0 / 1 (None:
+        # that batch came without lengths), and per FEAT buffer that of the batch whose encoder pass filled it last - what the fusion
+        # layer, the head and the backward pass of the step that consumes the buffer use, whichever call ran the encoder pass
+        self._xin_len = [None, None]
+        self._feat_len = {}
+        self._len_ring = None          # (allocated with the first batch that carries lengths)
+        self._len_next = 0
         self._step_id = 0              # training steps enqueued so far
         self._synced_step = -1         # the host has seen the loss of this step (everything before its CTC is complete)
         self.fe = {}       # stream name -> its CNN front-end: per conv layer (shape dict, pooled output, pool routing codes[, dX])
@@ -586,6 +594,7 @@ class Engine:
         """Host batch -> the input buffer set that is NOT the one read last, on the copy stream; `stream` (where the
         encoder pass that reads it will be enqueued) waits for the copies."""
         dev = self.dev
+        lens = seqlen.of(inputs, self.B, self.T)     # (refused before anything is enqueued)
         slot = self._xin_slot ^ 1
         dev.stream(self.COPY_STREAM)
         # the set was last read by step _xin_user[slot]; once the host has read a loss at or after that step the readers
@@ -617,6 +626,7 @@ class Engine:
             if train and nz is not None:
                 stage += np.asarray(nz, dtype=np.float32)
             dev.h2d_async(self._xin_ring[slot][s["name"]], stage)   # the host does not wait for the copy
+        self._xin_len[slot] = None if lens is None else self._upload_lengths(lens)
         dev.record(self.EV_XIN_COPIED[slot])
         self._xin_copied[slot] = True
         dev.wait(stream, self.COPY_STREAM)
@@ -624,6 +634,33 @@ class Engine:
         self._xin_user[slot] = 1 << 60     # set by the step that consumes it (enqueue_train_step)
         self.Xin = self._xin_ring[slot]
         dev.stream(stream)
+
+    LEN_RING = 8
+
+    def _upload_lengths(self, lens):
+        """The lengths of the batch being uploaded -> the next of LEN_RING small device arrays, on the current (copy) stream, through
+        page-locked staging of its own.  Not one per input set: the fusion layer and the backward pass of the step that consumes a
+        batch still read its lengths when the input set is refilled two uploads later (its encoder pass is all that reads the
+        inputs); eight uploads later every reader is behind a loss the host has read or an event an upload has waited for."""
+        if self._len_ring is None:
+            self._len_ring = [(self.dev.pinned((self.B,), np.int32), self.mem.empty((self.B,), np.int32)) for _ in range(self.LEN_RING)]
+        pin, d = self._len_ring[self._len_next]
+        self._len_next = (self._len_next + 1) % self.LEN_RING
+        pin[...] = lens
+        self.dev.h2d_async(d, pin)
+        return d
+
+    def _zero_tails(self, lens, bufs):
+        """One mgr_seq_zero_tail on the current stream over bufs = [(buffer, row, ld)], each [B, T, row]; nothing without lengths."""
+        if lens is None or not bufs:
+            return
+        arr = _capi.make_seq_fill_jobs([(b, row, ld, self.B, self.T) for b, row, ld in bufs])
+        self.dev.call("mgr_seq_zero_tail", len(bufs), arr, lens)
+
+    def _check_lengths(self, inputs, input_length=None, augment=False):
+        """seqlen.check_batch for this engine: raises ValueError before anything is enqueued; the lengths (host) or None."""
+        return seqlen.check_batch(inputs, self.B, self.T, int(self.spec.ctc["skip"]), input_length, data_parallel=self.comm is not None,
+                                  frontend=bool(self.fe), augment=augment)
 
     # Bound on the transposed activation copies the engine keeps (Y1T, FEAT^T), in the convention of mgr.h's x_absmax: NEGATIVE =
     # guaranteed by the producer, not checked.  Every such copy holds outputs of LSTM layers of this library - h = o * tanh(c) with
@@ -787,6 +824,8 @@ class Engine:
             cols[s["name"]] = col
             col += sp.stream_width(s)
         dev.stream(es if first_stream is None else first_stream)
+        # the lengths of the batch this pass reads (None: none) stay with the FEAT buffer it fills
+        lens = self._feat_len[feat_buf.ptr] = self._xin_len[self._xin_slot]
         aug = self._augment if (augment and train and rand is None) else None
         if aug is not None:
             # one plan per pass, from the pass's own step counter: a prefetched pass draws the plan of the step that consumes it, and
@@ -870,6 +909,8 @@ class Engine:
                     jobs.append(dict(Z=Z, Up=L.Up, Y=Y, ldy=ldy, R=R, ldr=ldr, gates=L.gates if keep else 0,
                                      cs=L.cs if keep else 0, B=B, T=T, H=H, reverse=L.reverse, YT=YT, ytb=ytb,
                                      ldt=self.ldt if YT else 0, yt_split=yt_fmt))
+            # (lengths: a reverse recurrence meets zero gate pre-activations in a sample's tail and keeps h = c = 0 through it)
+            self._zero_tails(lens, [(j["Z"], 4 * j["H"], 4 * j["H"]) for j in jobs if j["reverse"]])
             if k == 0:
                 dev.record(self.EV_IN[self._xin_slot])   # the inputs have been read (noise kernel / depth-1 projections)
             self.rng_step = saved_step
@@ -879,6 +920,8 @@ class Engine:
             dev.stream(es)
             # all recurrences of this depth in ONE call (one persistent multi-CU launch when H is large)
             self._scan_multi(jobs, "_ws_multi", form=self._enc_scan_form, seq_word=(seq_words or {}).get(k, 0))
+            # (... and its saved gates are zeroed there: the BPTT's dZ is exactly 0 in the tail)
+            self._zero_tails(lens, [(j["gates"], 4 * j["H"], 4 * j["H"]) for j in jobs if j["reverse"] and j["gates"]])
             self.rng_step = saved_step
             yield ("scanned", k)
             saved_step, self.rng_step = self.rng_step, rng_step
@@ -904,6 +947,7 @@ class Engine:
         dev.stream(0)
         feat, ldf = feat_buf, W
         self._featin = feat_buf
+        lens = self._feat_len.get(feat_buf.ptr)     # (of the batch whose encoder pass filled feat_buf)
         if sp.fusion:
             Hf = sp.fusion["H"]
             jobs = []
@@ -919,6 +963,7 @@ class Engine:
             with self._narrow_tiles(self._beside_scans and not self._wide_ok):
                 self._project_pair(feat_buf, W, pair, Ls_pair, B, T, W, Hf, XT=self._featT.get(feat_buf.ptr),
                                    xt_ready=self._featT_ready.get(feat_buf.ptr, False), x_rows=self._feat_rows.get(feat_buf.ptr, True))
+            self._zero_tails(lens, [(self.ZF[1], 4 * Hf, 4 * Hf)])
             dev.record(self.EV_FPROJ)   # (the next step's depth-1 scan is launched after these GEMMs, _enqueue_next_encoders)
             if self._gate_words[0] is not None:
                 # (Schedule.fused_encoder_scans: the fusion scan's 56 workgroups must land on the CUs the next batch's deepest encoder
@@ -931,6 +976,7 @@ class Engine:
                                  gates=L.gates if save else 0, cs=L.cs if save else 0, B=B, T=T, H=Hf,
                                  reverse=L.reverse))
             self._scan_multi(jobs, "_ws_multi_f", form=self._fusion_scan_form)
+            self._zero_tails(lens, [(j["gates"], 4 * Hf, 4 * Hf) for j in jobs if j["reverse"] and j["gates"]])
             feat, ldf = self.YF, 2 * Hf
         # head
         D, Cn = sp.head_width, sp.num_classes
@@ -951,6 +997,7 @@ class Engine:
         if dense:
             dev.call("mgr_dense_softmax_fwd", feat, ldf, hm, p_head, C.c_uint64(self._head_seed),
                      self._wview("dense/W"), self._wview("dense/b"), self.P, B, T, D, Cn)
+            self._zero_tails(lens, [(self.P, Cn, Cn)])      # (what a caller gets does not depend on the padding anywhere)
         self._feat = (feat, ldf)
         self.rng_step = saved_step
 
@@ -1075,6 +1122,7 @@ class Engine:
 
     def predict(self, inputs):
         """Softmax output (B,T,C) with learning phase 0 (sequence_decoding.py:81)."""
+        self._check_lengths(inputs)
         self._upload_inputs(inputs, None, False)
         blk = self._begin_pass()
         self._forward(False, None)
@@ -1083,6 +1131,7 @@ class Engine:
 
     def forward_train_phase(self, inputs, rand=None):
         """Softmax output with learning phase 1 (dropout / noise active) - no gradient."""
+        self._check_lengths(inputs)
         self._upload_inputs(inputs, rand, True)
         blk = self._begin_pass()
         self._forward(True, rand)
@@ -1162,7 +1211,11 @@ class Engine:
                         sample drawn from the posteriors, collapsed and merged (decoding.sample_hypotheses of the
                         posteriors).  The i-th batch of the stream draws with seed (sample_seed + i) mod 2^64; an inference-only
                         engine will do
-        Results are bit-identical to the one-batch-at-a-time calls (predict / loss_on_batch): same kernels, same order per batch."""
+        Results are bit-identical to the one-batch-at-a-time calls (predict / loss_on_batch): same kernels, same order per batch.
+        A batch whose input dict carries "seq_length"  is computed as each sample alone at its own length: its posteriors
+        are zero at t >= len, the outputs that take an input length decode len - skip frames (the labelled ones the input_length
+        given, checked against that), "argmax" marks the frames past it -1 / 0, and "segments" / "score" with the greedy decode -
+        whose kernel takes no length - refuse it."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         Cn, skip, eps = sp.num_classes, int(sp.ctc["skip"]), float(sp.ctc["eps"])
         # ("score" decodes one path; top_paths is read for "beam_lm" alone)
@@ -1217,7 +1270,7 @@ class Engine:
             raise ValueError("top_paths %d out of [1, beam_width = %d]" % (int(top_paths), int(beam_width)))
         elif output == "lexicon" and lexicon is None:
             raise ValueError("output='lexicon' needs a lexicon")
-        op, host_labels = None, {}
+        op, host_labels, dil = None, {}, None
         if hypo:
             op = decoding.rescore_op(Cn, skip, lexicon, eps)
         elif name in ops:
@@ -1263,6 +1316,10 @@ class Engine:
 
         spin = bufs("status16", lambda: [dev.pinned((16,), np.uint32) for _ in range(2)])
 
+        # per-sample lengths: batch i -> its lengths on the host, from its upload until its result is handed out
+        host_lens = {}
+        greedy = name == "segments"       # (mgr_greedy_segments takes no input length, and its confidence filter is not local in time)
+
         def collect(i):
             o = i & 1
             dev.event_sync(self.EV_OUT[o])
@@ -1270,6 +1327,13 @@ class Engine:
                 r = op.result(*pins[o], *host_labels.pop(i, ()))
             else:
                 r = pins[o] if output == "score" else pins[o][0]
+            bl = host_lens.pop(i, None)
+            if bl is not None and output == "argmax":
+                # (the frame argmax takes no input length: the frames past len - skip, the argmax of zero rows, are marked absent)
+                best, prob = (m.copy() for m in r)
+                for b, nfr in enumerate(seqlen.frames(bl, skip)):
+                    best[b, nfr:], prob[b, nfr:] = -1, 0.0
+                r = (best, prob)
             # the pinned buffers are reused two batches later: every array handed out is a copy (the lists hold Python numbers)
             own = lambda m: m.copy() if isinstance(m, np.ndarray) else m
             r = tuple(own(m) for m in r) if isinstance(r, tuple) else own(r)
@@ -1302,6 +1366,12 @@ class Engine:
             """Upload batch i and enqueue its noise / depth-1 projections on stream 0 (two_stage), or nothing yet; returns the
             generator that enqueues the rest of its encoder pass on ES."""
             inputs = item[0] if labelled or hypo else item
+            bl = self._check_lengths(inputs, item[2] if labelled else None)      # (raises before anything of this batch is enqueued)
+            if bl is not None:
+                if greedy:
+                    raise ValueError("the greedy segment decode takes no input length (its confidence filter counts frames over the "
+                                     "whole sequence): with %s use the argmax, beam or lexicon outputs" % seqlen.KEY)
+                host_lens[i] = bl
             f = i % len(ring)
             first = 0 if two_stage else ES
             self._upload_inputs(inputs, None, train_phase, stream=first)
@@ -1392,6 +1462,15 @@ class Engine:
                 # ---- decode kernels and the way back to pinned host memory: their own stream, beside batch i + 1's fusion layer
                 dev.stream(OUT)
                 dev.wait_event(OUT, self.EV_FUSED[f])
+                dil_i = dil
+                if dil is not None and i in host_lens:
+                    # this batch's own input lengths, len - skip (pinned set o: read last by batch i - 2's copy, like phyp below; one
+                    # device array: upload and kernel of a batch are consecutive on this stream)
+                    dlen = bufs("dil seq", lambda: self.mem.empty((B,), np.int32))
+                    plen = bufs("dil seq pinned", lambda: [dev.pinned((B,), np.int32) for _ in range(2)])
+                    plen[o][...] = seqlen.frames(host_lens[i], skip)
+                    dev.h2d_async(dlen, plen[o])
+                    dil_i = dlen
                 if hypo:
                     # (pinned set o was last read by batch i - 2's copies, behind EV_OUT[o], which collect(i - 2) has waited for)
                     if np.shape(item[1]) != hshape or np.shape(item[2]) != hshape[:2]:
@@ -1400,11 +1479,11 @@ class Engine:
                         pin[...] = a
                         dev.h2d_async(d, pin)
                     host_labels[i] = (None, None)
-                    op.launch(dev, pring[o], dil, dring[0], tables, ws, *dhyp)
+                    op.launch(dev, pring[o], dil_i, dring[0], tables, ws, *dhyp)
                 elif output == "sample":
-                    op.launch(dev, pring[o], dil, dring[0], tables, ws, seed=int(sample_seed) + i)
+                    op.launch(dev, pring[o], dil_i, dring[0], tables, ws, seed=int(sample_seed) + i)
                 elif op is not None and output not in self.ALIGNED:
-                    op.launch(dev, pring[o], dil, dring[0], tables, ws)
+                    op.launch(dev, pring[o], dil_i, dring[0], tables, ws)
                 if output == "score":
                     dev.call("mgr_edit_distance", dring[0][op.hyp[0]], dring[0][op.hyp[1]], B, T - skip, self.labels_d, self.llen_d, B, self.Lmax,
                              None, None, B, ecosts[0], ecosts[1], ecosts[2], emask, dscore[0], dscore[1], dscore[2], None, None, None, 0)
@@ -1460,6 +1539,7 @@ class Engine:
 
     def loss_on_batch(self, inputs, labels, input_length, label_length, rand=None, train_phase=True):
         """Per-sample CTC loss (validation inside fit_generator: learning phase stays 1, multimodal.py:66)."""
+        self._check_lengths(inputs, input_length)
         self._upload_inputs(inputs, rand, train_phase)
         self._upload_labels(labels, input_length, label_length)
         blk = self._begin_pass()
@@ -1476,7 +1556,10 @@ class Engine:
         """One optimizer step (Keras train_on_batch).  Returns the mean CTC loss of the local batch.
         next_inputs (optional): the inputs of the FOLLOWING call; when the encoders are frozen their pass for that batch
         is overlapped with this step's fusion / BPTT / Adam work (bit-identical results); after_next_inputs: those of the call
-        after that (the encoder stream gets the first part of its pass a call early)."""
+        after that (the encoder stream gets the first part of its pass a call early).
+        inputs["seq_length"] ((B,) or (B, 1) integers in [0, T]), in any of the three dicts: the batch's per-sample frame
+        counts - the step computes what each sample gives alone at its own length, whatever the padding holds.  Needs
+        input_length[b] <= max(0, seq_length[b] - skip); ValueError before anything is enqueued otherwise (seqlen.check_batch)."""
         self.enqueue_train_step(inputs, labels, input_length, label_length, rand, apply_update,
                                 prefetch_next=next_inputs is not None, next_inputs=next_inputs,
                                 prefetch_after_next=next_inputs is not None and after_next_inputs is not None,
@@ -1556,6 +1639,10 @@ class Engine:
         if self._augment is not None and rand is not None:
             raise ValueError("a training step with set_augment on was given `rand`: host-supplied randomness has no augmentation plan "
                              "(set_augment(None) first)")
+        if upload:
+            self._check_lengths(inputs, input_length, augment=self._augment is not None)
+        for ahead_inputs in (next_inputs, after_next_inputs):
+            self._check_lengths(ahead_inputs, augment=self._augment is not None)
         self._bind()
         pipelined = prefetch_next and rand is None and self.can_pipeline and sch.pipeline
         depth = max(len(s_["layers"]) for s_ in sp.streams)

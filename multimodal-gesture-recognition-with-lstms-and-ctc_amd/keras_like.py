@@ -491,8 +491,12 @@ class Model:
         names = [s["name"] for s in self.spec.streams]
         if isinstance(x, dict):
             # a stream may read several graph inputs concatenated on the feature axis (early fusion)
-            return {s["name"]: (np.concatenate([np.asarray(x[k]) for k in s["inputs"]], axis=2) if s.get("inputs")
-                                else x[s["name"]]) for s in self.spec.streams}
+            ins = {s["name"]: (np.concatenate([np.asarray(x[k]) for k in s["inputs"]], axis=2) if s.get("inputs")
+                               else x[s["name"]]) for s in self.spec.streams}
+            if x.get("seq_length") is not None:
+                # per-sample sequence lengths travel with the inputs they describe (Engine), prefetched batches included
+                ins["seq_length"] = np.asarray(x["seq_length"])
+            return ins
         if isinstance(x, (list, tuple)):
             return dict(zip(names, x))
         return {names[0]: x}
