@@ -10,13 +10,14 @@
 //            loop over t with the t - 1 values in registers (word j at t needs word j - 1 at t - 1: updated from the last word down).
 //            Emissions and the parent's values are fetched a step ahead.  Kept: ln psi and ln p, in the workspace.
 //   select   pre = sum_m w_m ln psi_m + the table terms in LDS; `beam` rounds of wave arg-max by wave 0, ties to the smaller
-//            candidate index r * G + g (k_beam_lm's loop).
+//            candidate index r * G + g (k_beam's loop).
 //   pass B   the <= beam kept chains run again, a wave per stream, and store their gn / gb into the other half of the ping-pong
 //            buffer: the arrays of all live * G candidates are never stored.  Skipped when the round is the last.
 // The empty prefix needs no arrays: its gb is the running sum of ln y(blank), which the chain carries anyway.
 // The result list (<= top_paths entries) lives in LDS, unordered with an arrival number; an entry replaces the worst when it is
 // strictly better; ranked at the end by (score, arrival).  Everything a decision reads is fp64.
 #include "ctc_lattice.h"
+#include "wave_f64.h"
 
 namespace {
 
@@ -25,17 +26,9 @@ constexpr int MAXG = MGR_LEXICON_MAX_PHRASES;
 constexpr int MAXM = MGR_JOINT_MAX_STREAMS;
 constexpr int MAXLEN = MGR_RESCORE_MAX_LABELS + 1;   // bytes per stored sequence
 constexpr int JNT = 512;                             // threads of k_joint: 8 waves, two per SIMD
-constexpr double kNegInfD = -__builtin_huge_val();
 
 static_assert(MAXM == kJointMaxStreams, "ws_layout.h");
 static_assert(MAXG <= 256 && MGR_LEXICON_MAX_WORDS <= 255, "gesture ids and lexicon offsets are kept as bytes");
-
-__device__ __forceinline__ double lse64(double a, double b) {
-  if (a == kNegInfD) return b;
-  if (b == kNegInfD) return a;
-  const double m = a > b ? a : b;
-  return m + log1p(exp(-fabs(a - b)));
-}
 
 struct JtStream {
   const double* E;   // [B][C][row]
@@ -163,13 +156,6 @@ __device__ __forceinline__ Chain jt_run(int nwmax, const double* Eb, size_t TS, 
   if (nwmax <= 2) return jt_chain<2, STORE>(Eb, TS, Tp, blank, wd, g, n, plast, pgn, pgb, ogn, ogb);
   if (nwmax <= 4) return jt_chain<4, STORE>(Eb, TS, Tp, blank, wd, g, n, plast, pgn, pgb, ogn, ogb);
   return jt_chain<MGR_JOINT_MAX_PHRASE_WORDS, STORE>(Eb, TS, Tp, blank, wd, g, n, plast, pgn, pgb, ogn, ogb);
-}
-
-__device__ __forceinline__ double shfl_xor_d(double v, int o) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __shfl_xor(lo, o);
-  hi = __shfl_xor(hi, o);
-  return __hiloint2double(hi, lo);
 }
 
 // grid B, JNT threads; dynamic LDS: ext [(G + 1) * G] and the candidates' pre [beam * G], doubles
@@ -307,12 +293,9 @@ __global__ __launch_bounds__(JNT) void k_joint(const JtArgs a, int M, int G, con
           }
         }
         for (int o = 32; o > 0; o >>= 1) {
-          const double ob = shfl_xor_d(best, o);
-          const int oi = __shfl_xor(bidx, o);
-          if (ob > best || (ob == best && oi < bidx)) {
-            best = ob;
-            bidx = oi;
-          }
+          const ScoreIdx q = wave_argmax_step_d(best, bidx, o);
+          best = q.v;
+          bidx = q.i;
         }
         if (best == kNegInfD) break;   // wave-uniform
         if (lane == (bidx & 63)) s_cpre[bidx] = kNegInfD;   // the owning lane retires the candidate

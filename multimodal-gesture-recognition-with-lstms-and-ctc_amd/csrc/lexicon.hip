@@ -26,6 +26,7 @@
 // Ties: the smaller back-pointer code wins (stay, then one state, then two; for a phrase entry stay, INIT, then the phrases in
 // order, Z(g') before the last word of g'); among the final states the smallest state index.
 #include "ctc_lattice.h"
+#include "wave_f64.h"
 
 namespace {
 
@@ -58,13 +59,6 @@ __host__ __device__ inline LexLds lex_lds(int NT, int G, int N, int To, bool wit
   L.bpe = o;    o += with_bp ? (size_t)lex_nb4(To) * G : 0;
   L.words = o;
   return L;
-}
-
-__device__ __forceinline__ double shfl_xor_d(double v, int o) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __shfl_xor(lo, o);
-  hi = __shfl_xor(hi, o);
-  return __hiloint2double(hi, lo);
 }
 
 // sum of one double per thread over the workgroup, in a fixed order (wave butterflies, then the waves in order); every thread gets it

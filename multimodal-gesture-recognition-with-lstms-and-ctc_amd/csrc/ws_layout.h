@@ -20,7 +20,7 @@ struct mgr_ws_carver {
   }
 };
 
-// beam.hip / beam_lm.hip: the trie (parent, label: [B][nodes]) and the (parent, label) hash table of [B] << bits entries, 1 << bits
+// beam.hip: the trie (parent, label: [B][nodes]) and the (parent, label) hash table of [B] << bits entries, 1 << bits
 // the first power of two >= 2 * nodes (and >= 64: the table is whole 256-byte lines as it is)
 struct mgr_beam_ws { int bits; int32_t *parent, *label; unsigned long long* table; size_t bytes; };
 static inline mgr_beam_ws mgr_beam_ws_layout(void* ws, int B, size_t nodes) {

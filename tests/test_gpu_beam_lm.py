@@ -1,8 +1,8 @@
-"""-m gpu: the beam search with a label bigram and an N-best list (mgr_ctc_beam_search_lm) against the existing beam kernel
+"""-m gpu: the beam search with a label bigram and an N-best list (mgr_ctc_beam_search_lm) against the plain entry point
 (zero tables: bit for bit), the fp64 reference tests/beam_lm_ref.py, exhaustive enumeration, and through the facade.
 
 Sequences are compared for equality only after the reference has shown that no decision of the search hangs on a score difference
-below 1e-9 (its `gap`); scores to 1e-12 relative, the project's bound for the existing beam kernel."""
+below 1e-9 (its `gap`); scores to 1e-12 relative, the project's bound for the plain beam search."""
 import ctypes as C
 import os
 import sys
@@ -47,9 +47,10 @@ def case(shape):
     return _CASES[shape]
 
 
-def run_nbest(device, P, il, ext, fin, W, NP, skip=2, eps=1e-8):
-    """The C call itself: the raw (out, out_len, score, logp_ctc) arrays."""
+def run_nbest(device, P, il, ext, fin, W, NP, skip=2, eps=1e-8, blank=None):
+    """The C call itself: the raw (out, out_len, score, logp_ctc) arrays.  blank: None = the last class."""
     N, T, Cn = P.shape
+    blank = Cn - 1 if blank is None else blank
     arrs = [device.array(np.ascontiguousarray(P, np.float32)), device.array(np.asarray(il, np.int32)),
             device.array(np.ascontiguousarray(ext, np.float64))]
     dfin = None
@@ -60,7 +61,7 @@ def run_nbest(device, P, il, ext, fin, W, NP, skip=2, eps=1e-8):
             device.empty((N, NP), np.float64)]
     ws = device.bytes(device.lib.mgr_ctc_beam_lm_ws_bytes(N, T, Cn, W, NP))
     try:
-        device.call("mgr_ctc_beam_search_lm", arrs[0], arrs[1], N, T, Cn, skip, Cn - 1, W, C.c_float(eps), arrs[2], dfin, NP, *outs, ws,
+        device.call("mgr_ctc_beam_search_lm", arrs[0], arrs[1], N, T, Cn, skip, blank, W, C.c_float(eps), arrs[2], dfin, NP, *outs, ws,
                     ws.nbytes)
         return [o.download() for o in outs]
     finally:
@@ -84,6 +85,7 @@ def assert_matches_reference(got, ref, NP, To):
 
 @pytest.mark.parametrize("shape", SHAPES)
 def test_zero_tables_equal_the_existing_beam_kernel_bit_for_bit(device, shape):
+    """Zero tables against the plain entry point: the LM = true and LM = false instantiations of the one k_beam body."""
     from mgr_amd import decoding
     N, T, Cn, W = shape
     P, il = case(shape)
@@ -122,6 +124,48 @@ def test_random_tables_equal_the_reference(device, shape, frac_inf):
                 s = out[b, k, :olen[b, k]].tolist()
                 bonus = sum(ext[p + 1, c] for p, c in zip([-1] + s, s))
                 assert abs(score[b, k] - (logp[b, k] + bonus)) <= 1e-12 * abs(score[b, k]) + 1e-12
+
+
+@pytest.mark.parametrize("frac_inf", [0.0, 0.2])
+@pytest.mark.parametrize("shape", [(2, 30, 44, 32), (2, 24, 64, 20)])
+def test_more_than_12_candidates_per_lane_equal_the_reference(device, shape, frac_inf):
+    """beam * (C + 1) > 768: the 34-candidates-per-lane form with the bigram terms, the instantiation that spills the most to scratch.
+    The posteriors of test_gpu_decode.py::test_beam_search_with_more_than_12_candidates_per_lane: 44 classes at the beam limit of 32,
+    and the class limit of 64."""
+    N, T, Cn, W = shape
+    assert W * (Cn + 1) > 768
+    rng = np.random.default_rng(N * 100 + Cn + W)
+    P = rng.random((N, T, Cn)) ** 6
+    P = (P / P.sum(-1, keepdims=True)).astype(np.float32)
+    il = np.full(N, T - 2)
+    il[0] = (T - 2) // 2
+    ext, fin = tables(Cn, 50 + Cn, frac_inf)
+    for NP in sorted({1, 3, W}):
+        ref = br.beam_search_lm(P, il, ext, fin, beam_width=W, top_paths=NP)
+        got = run_nbest(device, P, il, ext, fin, W, NP)
+        assert_matches_reference(got, ref, NP, T - 2)
+
+
+@pytest.mark.parametrize("frac_inf", [0.0, 0.2])
+def test_merge_mask_bit_63_equal_the_reference(device, frac_inf):
+    """64 classes with blank = 0 (the inputs of test_gpu_decode.py::test_beam_search_merge_mask_bit_63): class 63 is a label, and an
+    extension by it that lands on a live beam sets bit 63 of the merge mask.  The table never bans an extension by 5 or 63, so 63
+    stays reachable and occurs in what is returned."""
+    N, T, Cn, W, skip, blank = 2, 24, 64, 20, 2, 0
+    rng = np.random.default_rng(63)
+    P = rng.random((N, T, Cn)) ** 6 * 1e-3
+    P[:, :, [0, 5, 63]] = rng.random((N, T, 3)) + 0.2
+    P = (P / P.sum(-1, keepdims=True)).astype(np.float32)
+    il = np.array([T - skip, T - skip - 3])
+    ext, fin = tables(Cn, 50 + Cn, frac_inf)
+    for c in (5, 63):
+        ext[np.isneginf(ext[:, c]), c] = 0.0
+    for NP in sorted({1, 3, W}):
+        ref = br.beam_search_lm(P, il, ext, fin, beam_width=W, top_paths=NP, skip=skip, blank=blank)
+        assert any(63 in s for hyps in ref[0] for s in hyps)
+        got = run_nbest(device, P, il, ext, fin, W, NP, skip=skip, blank=blank)
+        assert_matches_reference(got, ref, NP, T - skip)
+        assert any(63 in got[0][b, k, :got[1][b, k]].tolist() for b in range(N) for k in range(NP) if got[1][b, k] >= 0)
 
 
 @pytest.mark.parametrize("with_inf", [False, True])

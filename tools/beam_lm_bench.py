@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Device time of mgr_ctc_beam_search_lm (csrc/beam_lm.hip) beside mgr_ctc_beam_search - the unchanged kernel it is measured against -
+"""Device time of mgr_ctc_beam_search_lm beside mgr_ctc_beam_search - the two entry points of the one search body in csrc/beam.hip -
 in one process on one GPU: N = 276 sequences of T = 1900 frames, beam 10, C = 22 (gesture networks) and C = 44 (audio network),
 posteriors run-structured and blank-dominated like a trained CTC network's (tools/decode_bench.py), device-resident.  Each form is
 timed with HIP events around ONE launch, `launches` times, the forms interleaved launch by launch after a warm-up of each; the median
-(and the minimum) per form and the ratios of the medians to the existing kernel's are reported.
+(and the minimum) per form and the ratios of the medians to the plain entry point's are reported.
   beam           mgr_ctc_beam_search(merge_repeated=0)
   lm_zero        mgr_ctc_beam_search_lm, all-zero ext, fin = NULL, top_paths = 1      (the same search bit for bit)
   lm_dense       ... a dense random ext ~ N(0, 1) and fin
