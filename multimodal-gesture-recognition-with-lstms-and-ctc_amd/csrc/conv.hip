@@ -264,8 +264,8 @@ __global__ void __launch_bounds__(kBlock) k_conv_pool_bwd_w_mfma(const float* __
       part[(size_t)blockIdx.x * nE + (size_t)k * s.Cout + co[t]] = tot[t][r];
     }
   }
-  if (blockIdx.y == 0 && (int)threadIdx.x < s.Cout) {
-    const int c = threadIdx.x;
+  if (blockIdx.y != 0) return;
+  for (int c = threadIdx.x; c < s.Cout; c += kBlock) {   // (Cout may exceed the block: every channel gets its partial sum)
     double tb = 0.0;
     for (int n = n0; n < n1; ++n) {
       float a = 0.0f;

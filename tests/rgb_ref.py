@@ -42,6 +42,18 @@ def conv_layer_routed(x, W, b, dY, code):
     return win.detach().numpy(), xt.grad.numpy(), Wt.grad.numpy(), bt.grad.numpy()
 
 
+def conv_windows(x, W, b):
+    """One layer's fp64 pre-activation windows (N, Hp, Wp, Cout, 4) alone, without autograd: what conv_layer_routed returns first.
+    Their ReLU maximum over the last axis is conv_pool's output."""
+    with torch.no_grad():
+        xt, Wt, bt = (torch.tensor(np.asarray(a, np.float64)) for a in (x, W, b))
+        y = torch.nn.functional.conv2d(xt.permute(0, 3, 1, 2), Wt.permute(3, 2, 0, 1), bt).permute(0, 2, 3, 1)
+        N, Ho, Wo, Cn = y.shape
+        Hp, Wp = Ho // 2, Wo // 2
+        win = y[:, :2 * Hp, :2 * Wp, :].reshape(N, Hp, 2, Wp, 2, Cn).permute(0, 1, 3, 5, 2, 4).reshape(N, Hp, Wp, Cn, 4)
+    return win.numpy()
+
+
 def reference_code(pre):
     """fp64 routing of pre-activation windows (N, Hp, Wp, C, 4) and each window's gap between its two largest ReLU values."""
     r = np.maximum(pre, 0.0)

@@ -3,6 +3,7 @@ a BiLSTM(512) layer on F = 768 inputs, whole RGB train steps against the fp64 or
 import numpy as np
 import pytest
 
+from tests.conv_harness import run_layer as _run_layer      # (guarded outputs, NaN-filled workspace: shared with test_gpu_conv_edges.py)
 from tests.helpers import rel_err
 from tests.rgb_ref import conv_layer, conv_layer_routed, loss_and_grads, reference_code
 
@@ -10,28 +11,6 @@ pytestmark = pytest.mark.gpu
 
 # (Hin, Cin, ks, Cout) of conv_1 / conv_3 / conv_5 at img_dim = 60
 LAYERS = {"conv_1": (60, 1, 5, 16), "conv_3": (28, 16, 5, 32), "conv_5": (12, 32, 4, 48)}
-
-
-def _run_layer(device, x, W, b, dY, ks):
-    import ctypes as C
-    N, Hin, Win, Cin = x.shape
-    Cout = W.shape[-1]
-    Hp, Wp = (Hin - ks + 1) // 2, (Win - ks + 1) // 2
-    dx_, dW_, db_ = device.array(x.reshape(-1)), device.array(W.reshape(-1)), device.array(b)
-    Y = device.empty((N * Hp * Wp * Cout,))
-    code = device.empty((N * Hp * Wp * Cout,), np.uint8)
-    device.call("mgr_conv_pool_fwd", dx_, N, Hin, Win, Cin, dW_, db_, ks, Cout, Y, code)
-    ddY = device.array(dY.reshape(-1))
-    dX = device.empty((x.size,))
-    device.call("mgr_conv_pool_bwd_data", ddY, code, dW_, N, Hin, Win, Cin, ks, Cout, dX)
-    ws = device.bytes(device.lib.mgr_conv_pool_bwd_weights_ws_bytes(N, Hin, Win, Cin, ks, Cout))
-    gW, gb = device.empty((W.size,)), device.empty((b.size,))
-    device.call("mgr_conv_pool_bwd_weights", dx_, ddY, code, N, Hin, Win, Cin, ks, Cout, gW, gb, ws, ws.nbytes)
-    out = (Y.download().reshape(N, Hp, Wp, Cout), dX.download().reshape(x.shape), gW.download().reshape(W.shape), gb.download(),
-           code.download())
-    rep = device.empty((W.size,))
-    device.call("mgr_conv_pool_bwd_weights", dx_, ddY, code, N, Hin, Win, Cin, ks, Cout, rep, gb, ws, ws.nbytes)
-    return out + (rep.download().reshape(W.shape),)
 
 
 def _layer_case(layer, N, seed, constant=False):
