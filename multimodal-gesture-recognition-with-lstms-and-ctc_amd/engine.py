@@ -85,7 +85,7 @@ class _LstmDir:
 
 
 class Schedule:
-    """How one training step is laid out over the context's streams (DESIGN.md 5b).  The default is the schedule bench.py
+    """How one training step is laid out over the context's streams (DESIGN.md 6).  The default is the schedule bench.py
     and fit_generator run; the switches exist so that tests can show every layout computes the same step.
 
     pipeline            with frozen encoders, the encoder pass of step n+1 runs on a second stream beside step n's
@@ -183,6 +183,27 @@ class Schedule:
         self.defer_param_grads = bool(defer_param_grads)
         self.encoders_run_ahead = bool(encoders_run_ahead)
         self.resident_wait_us = int(resident_wait_us)
+
+
+class StepLayout(collections.namedtuple("StepLayout", "beside_scans wide_ok enc_scan_form fusion_scan_form gate_fusion gate_bptt")):
+    """What the launches of ONE training step look like.  enqueue_train_step builds it once and hands it to whatever
+    enqueues for the step; closures that run later capture it.
+    beside_scans      the fusion layer's GEMMs run beside encoder scans of the next batch (a pipelined step)
+    wide_ok           ... of FUSED encoder scans, which share no CU with a GEMM: the library's own tile choice (Schedule.fused_wide_tiles)
+    enc_scan_form     form of the encoder scan launches (mgr.h MGR_SCAN_FORM_*; AUTO: the context's MGR_TUNE_SCAN_FORM)
+    fusion_scan_form  form of the fusion layer's scan launch
+    gate_fusion / gate_bptt  fused encoder scans: the host words through which the launches the fusion scan / the BPTT of the step
+                      wait for hand over their launch numbers (None: no wait)"""
+    __slots__ = ()
+
+    @property
+    def fused(self):
+        """A step of the fused schedule: one of its recurrences waits for an encoder scan to become resident."""
+        return self.gate_fusion is not None or self.gate_bptt is not None
+
+
+# everything that is not a pipelined training step: predict, loss_on_batch, predict_stream, a step on the plain schedule
+PLAIN = StepLayout(False, False, _capi.SCAN_FORM_AUTO, _capi.SCAN_FORM_AUTO, None, None)
 
 
 class Engine:
@@ -401,6 +422,18 @@ class Engine:
             self.ws_ctc = dev.bytes(self.lib.mgr_ctc_ws_bytes(B, T, Cn, self.Lmax))
             self.ws_dense = dev.bytes(self.lib.mgr_dense_bwd_ws_bytes(B, T, D, Cn))
             self.ws_head = dev.bytes(self.lib.mgr_head_ws_bytes(B, T, D, Cn, self.Lmax))
+        # The schedule, resolved once: what Schedule's switches, the spec and the communicator allow a step of this engine (each name
+        # narrows an earlier one; enqueue_train_step adds what only a call knows)
+        sch = self.schedule
+        self.depth = max(len(s["layers"]) for s in sp.streams)
+        self.frozen_fusion = self.can_pipeline and sch.pipeline      # steps announced ahead are pipelined
+        self.can_defer = self.frozen_fusion and sch.defer_param_grads and self.depth >= 2    # ... their dW / dU / db GEMMs held back
+        self.can_hold_bptt = self.can_defer and sch.bptt_beside_deepest_scan                  # ... and the fusion layer's BPTT with them
+        self.can_run_ahead = self.can_defer and sch.encoders_run_ahead      # the encoder stream waits for one scan's buffer, not a step
+        self.can_run_free = self.can_hold_bptt and self.can_run_ahead       # ... and takes the next pass before the step's fusion work
+        # (fused: not with a host-blocking all-reduce - HostComm holds the host inside finish(), the depth-1 scan the BPTT's wait is for
+        #  would only be enqueued after it, the wait would always run into its bound; such runs share a GPU and use small batches anyway)
+        self.can_fuse = self.can_run_free and sch.fused_encoder_scans and not getattr(self.comm, "host_blocking", False)
         self.dev.sync()
 
     def _build_frontend(self, s, train):
@@ -573,8 +606,9 @@ class Engine:
         self.iterations = 0
 
     # ------------------------------------------------------------------------------------------ helpers
-    def _seed(self, slot):
-        return (self.seed * 1000003 + self.rng_step * 131 + slot) & 0xFFFFFFFFFFFFFFFF
+    def _seed(self, slot, step):
+        """The kernel seed of random stream `slot` in the pass that draws at step counter `step`."""
+        return (self.seed * 1000003 + step * 131 + slot) & 0xFFFFFFFFFFFFFFFF
 
     SAMPLE_SLOT = 998     # the stream constant of the risk mode's sampled hypothesis sets (the head dropout's is 999)
     _head_step = 0        # rng_step of the head pass enqueued last
@@ -667,17 +701,17 @@ class Engine:
     # o in [0, 1], so |h| <= 1 - or the residual sum of two of them (encoder stacks, multimodal.py:111,117): <= 2 by construction,
     # whether the scans wrote the copy themselves or mgr_transpose_bt made it from such a buffer.  A diverged state is NaN, not large.
     XT_BOUND = -2.0
-    _fmt_train = True      # the learning phase of the pass being enqueued (decides the row format of new transposed copies)
 
     @staticmethod
     def _ts_shape(fin):
         """Layer widths the pre-split products handle (mgr_lstm_input_proj_dropout_ts / mgr_lstm_param_grads_dropout_ts)."""
         return 128 <= fin <= 2048
 
-    def _split_rows_wanted(self):
-        """The format new transposed activation copies are written in: split rows (f16 hi / lo pairs, mgr.h) for the pre-split
-        products on the f16 matrix pipe - unless MGR_TUNE_GEMM_F32 keeps the GEMMs on their f32 MFMA kernels (bench.py's second leg)."""
-        if not self.schedule.split_rows or self.inference_only or not self._fmt_train:
+    def _split_rows_wanted(self, train):
+        """The format a pass of learning phase `train` writes new transposed activation copies in: split rows (f16 hi / lo pairs,
+        mgr.h) for the pre-split products on the f16 matrix pipe - unless MGR_TUNE_GEMM_F32 keeps the GEMMs on their f32 MFMA kernels
+        (bench.py's second leg)."""
+        if not self.schedule.split_rows or self.inference_only or not train:
             # (learning phase 0 has no dropout mask: ONE dense K loop stages the A tile once for the four gates - k_gemm_nn_dense16 on
             #  f32 rows; the pre-split kernel would stage it once per gate: 20.3 against 19.4 ms per pipelined batch.  By PHASE, not by
             #  engine: predict on a training engine and on an inference engine give the same bits)
@@ -686,13 +720,13 @@ class Engine:
         self.dev.call("mgr_tune_get", _capi.TUNE_GEMM_F32, C.byref(v))
         return v.value == 0
 
-    def _make_xt(self, X, ldx, XT, B, T, fin):
-        """Transposed copy of a row-major activation buffer the scans did not write themselves, in the format wanted now."""
-        split = self._split_rows_wanted() and self._ts_shape(fin)
+    def _make_xt(self, X, ldx, XT, B, T, fin, train):
+        """Transposed copy of a row-major activation buffer the scans did not write themselves, in the format its pass wants."""
+        split = self._split_rows_wanted(train) and self._ts_shape(fin)
         self.dev.call("mgr_transpose_bt_split" if split else "mgr_transpose_bt", X, ldx, XT, self.ldt, B, T, fin)
         self._xt_split[XT.ptr] = split
 
-    def _project_pair(self, X, ldx, pair, Ls, B, T, fin, H, XT=None, xt_ready=False, x_rows=True):
+    def _project_pair(self, X, ldx, pair, Ls, B, T, fin, H, train, XT=None, xt_ready=False, x_rows=True):
         """Input projections of the two directions of one Bidirectional layer (pair = [mask, Wp, bp, Z] x 2).  With input
         dropout active the library runs each direction's K loops over the kept features only (from p >= 0.3 on) - from the
         transposed copy XT of the input where the engine keeps one (pre-split rows: the loader / matrix pipeline of gemm_split.hip;
@@ -702,7 +736,7 @@ class Engine:
         if not x_rows and (XT is None or not (masked or unmasked_wide) or not xt_ready):
             raise RuntimeError("this projection reads row-major input the encoder pass left out")
         if XT is not None and (masked or unmasked_wide) and not xt_ready:   # (xt_ready: the scans that produced X wrote XT themselves, mgr_scan_job.YT)
-            self._make_xt(X, ldx, XT, B, T, fin)
+            self._make_xt(X, ldx, XT, B, T, fin, train)
         split = XT is not None and self._xt_split.get(XT.ptr, False)
         if masked or unmasked_wide:
             # (no dropout - inference - on a wide layer whose input the engine keeps transposed: the same kernels without a mask)
@@ -720,14 +754,14 @@ class Engine:
         else:
             self.dev.call("mgr_lstm_input_proj_pair", X, ldx, *pair, B, T, fin, H)
 
-    def _prep_mask(self, L, train, rand, slot):
-        """Returns the device pointer (or 0) of the [4,B,fin] input-dropout mask for this pass."""
+    def _prep_mask(self, L, train, rand, slot, step):
+        """Returns the device pointer (or 0) of the [4,B,fin] input-dropout mask for this pass (drawn at step counter `step`)."""
         if not self._mask_drawn(L, train, rand):
             return 0  # (also: explicit randomness given but no mask for this layer: no dropout)
         if rand is not None:
             L.mask.upload(np.asarray(rand["%s/%s/mask" % (L.prefix, L.d)], dtype=np.float32))
             return L.mask.ptr
-        self.dev.call("mgr_dropout_mask", L.mask, L.mask.size, float(L.p), C.c_uint64(self._seed(slot)))
+        self.dev.call("mgr_dropout_mask", L.mask, L.mask.size, float(L.p), C.c_uint64(self._seed(slot, step)))
         return L.mask.ptr
 
     @staticmethod
@@ -785,10 +819,10 @@ class Engine:
         if train:
             self.rng_step += 1
 
-    def _enqueue_encoders(self, train, rand, feat_buf, es, rng_step, hold_scans_for=None, augment=False):
+    def _enqueue_encoders(self, train, rand, feat_buf, es, rng_step, hold_scans_for=None, augment=False, scan_form=_capi.SCAN_FORM_AUTO):
         """Noise + every encoder depth (input-projection GEMMs, then all recurrences of the depth in one multi-scan
-        call), written into feat_buf.  Everything is enqueued on stream `es`.  augment: _encoder_phases'."""
-        for tag, k in self._encoder_phases(train, rand, feat_buf, es, rng_step, augment=augment):
+        call), written into feat_buf.  Everything is enqueued on stream `es`.  augment, scan_form: _encoder_phases'."""
+        for tag, k in self._encoder_phases(train, rand, feat_buf, es, rng_step, augment=augment, scan_form=scan_form):
             if tag != "projected":
                 continue
             if hold_scans_for is not None and k >= 1:
@@ -798,25 +832,24 @@ class Engine:
                 self.dev.stream(es)
                 self.dev.wait(es, hold_scans_for)
 
-    def _encoder_phases(self, train, rand, feat_buf, es, rng_step, first_stream=None, z_first=None, seq_words=None, augment=False):
+    def _encoder_phases(self, train, rand, feat_buf, es, rng_step, first_stream=None, z_first=None, seq_words=None, augment=False,
+                        scan_form=_capi.SCAN_FORM_AUTO):
         """Generator form of the encoder pass: yields ("projected", k) after the projection GEMMs of depth k are enqueued
         (before its scan) and ("scanned", k) after its multi-scan launch, so that a caller can interleave work of another
-        stream at those points.  Re-selects stream `es` after every resume; self.rng_step is only switched to `rng_step`
-        while the generator body runs.
+        stream at those points.  Re-selects stream `es` after every resume; the pass draws its randomness at step counter
+        `rng_step`, whatever self.rng_step is by the time a part of it is enqueued.
         first_stream / z_first (pipelined inference): the noise kernels and the depth-1 projections are enqueued on stream
         `first_stream` instead, into the gate pre-activation buffers z_first[name] = (fwd, bwd) instead of the stream's shared
         Zbuf - the caller orders `es` behind them before it resumes the generator.
         seq_words: dict {depth k: address of a host word} - the scan launch of depth k hands its launch number to that word (looked
-        up when the launch is enqueued, so a caller may fill the dict while the generator is suspended).  The FORM of each scan
-        launch is self._enc_scan_form at the moment it is enqueued (MGR_SCAN_FORM_*: the schedule's choice for that launch).
+        up when the launch is enqueued, so a caller may fill the dict while the generator is suspended).  scan_form: the form of
+        the pass's scan launches (MGR_SCAN_FORM_*: StepLayout.enc_scan_form of the step that starts the pass).
         augment: this is the pass of a TRAINING STEP (only enqueue_train_step's passes say so: the train-phase passes of
         loss_on_batch / forward_train_phase stay what they are) - with set_augment on, the plan of THIS pass's rng_step is drawn and
         every stream goes through mgr_augment_apply, its noise included, in mgr_add_gaussian_noise's place."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         W = sp.concat_width
         save = train and not self.inference_only
-        self._fmt_train = bool(train)
-        saved_step, self.rng_step = self.rng_step, rng_step
         slot = 0
         cols = {}
         col = 0
@@ -830,26 +863,26 @@ class Engine:
         if aug is not None:
             # one plan per pass, from the pass's own step counter: a prefetched pass draws the plan of the step that consumes it, and
             # a stale pass that is redone draws the same plan again
-            augment_mod.enqueue_plan(dev, aug["cfg"], aug["table"], B, T, self._seed(augment_mod.PLAN_SLOT), aug["plan"])
+            augment_mod.enqueue_plan(dev, aug["cfg"], aug["table"], B, T, self._seed(augment_mod.PLAN_SLOT, rng_step), aug["plan"])
         # GaussianNoise (K1) per stream
         for si, s in enumerate(sp.streams):
             name = s["name"]
             X = self.Xin[name]
             if aug is not None:
                 # warp, masks, dropped stream and the stream's noise in one pass; the resident input stays pristine
-                augment_mod.enqueue_apply(dev, aug["cfg"], si, X, self.X[name], aug["plan"], B, T, float(s["noise"]), self._seed(900 + si))
+                augment_mod.enqueue_apply(dev, aug["cfg"], si, X, self.X[name], aug["plan"], B, T, float(s["noise"]), self._seed(900 + si, rng_step))
                 X = self.X[name]
             elif train and rand is None and s["noise"] > 0:
                 # on device; the resident input stays pristine for the next step
                 dev.call("mgr_add_gaussian_noise", X, self.X[name], X.size, float(s["noise"]),
-                         C.c_uint64(self._seed(900 + si)))
+                         C.c_uint64(self._seed(900 + si, rng_step)))
                 X = self.X[name]
             if name in self.fe:
                 X = self._frontend_fwd(name, X)     # (where the other networks apply GaussianNoise: the CNN front-end)
             self._xcur[name] = X
         depth = max(len(s["layers"]) for s in sp.streams)
         feat_by_scans = True     # every stream's last layer writes FEAT (and its transposed copy) from its scan
-        split_now = self._split_rows_wanted()   # the format of the transposed copies this pass's scans write
+        split_now = self._split_rows_wanted(train)   # the format of the transposed copies this pass's scans write
         feat_split = bool(split_now and self._ts_shape(W))
         # every reader of this pass's encoder output takes FEAT^T: the scans that write both leave the row-major copy out
         no_rows = self._feat_rows_unread(train, rand, feat_buf, feat_split)
@@ -874,11 +907,11 @@ class Engine:
                     L = self.dirs["%s/l%d/%s" % (name, k, dname)]
                     Ls_pair.append(L)
                     slot += 1   # (every projection GEMM fills the chip: one stream keeps their timings honest)
-                    mptr = self._prep_mask(L, train, rand, slot)
+                    mptr = self._prep_mask(L, train, rand, slot, rng_step)
                     self._masks[(L.prefix, L.d)] = mptr
                     zb = z_first[name] if (k == 0 and z_first is not None) else self.Zbuf[name]
                     pair += [mptr, L.Wp, L.bp, zb[di]]
-                self._project_pair(cur, ldcur, pair, Ls_pair, B, T, fin, H, XT=self.Y1T.get(name) if k == 1 else None,
+                self._project_pair(cur, ldcur, pair, Ls_pair, B, T, fin, H, train, XT=self.Y1T.get(name) if k == 1 else None,
                                    xt_ready=True)
                 for di, dname in enumerate(("fwd", "bwd")):
                     L = self.dirs["%s/l%d/%s" % (name, k, dname)]
@@ -913,19 +946,13 @@ class Engine:
             self._zero_tails(lens, [(j["Z"], 4 * j["H"], 4 * j["H"]) for j in jobs if j["reverse"]])
             if k == 0:
                 dev.record(self.EV_IN[self._xin_slot])   # the inputs have been read (noise kernel / depth-1 projections)
-            self.rng_step = saved_step
             yield ("projected", k)
-            saved_step, self.rng_step = self.rng_step, rng_step
-            self._fmt_train = bool(train)
             dev.stream(es)
             # all recurrences of this depth in ONE call (one persistent multi-CU launch when H is large)
-            self._scan_multi(jobs, "_ws_multi", form=self._enc_scan_form, seq_word=(seq_words or {}).get(k, 0))
+            self._scan_multi(jobs, "_ws_multi", form=scan_form, seq_word=(seq_words or {}).get(k, 0))
             # (... and its saved gates are zeroed there: the BPTT's dZ is exactly 0 in the tail)
             self._zero_tails(lens, [(j["gates"], 4 * j["H"], 4 * j["H"]) for j in jobs if j["reverse"] and j["gates"]])
-            self.rng_step = saved_step
             yield ("scanned", k)
-            saved_step, self.rng_step = self.rng_step, rng_step
-            self._fmt_train = bool(train)
             dev.stream(es)
         self._featT_ready[feat_buf.ptr] = feat_by_scans
         for si, s in enumerate(sp.streams):
@@ -934,16 +961,13 @@ class Engine:
                 H = s["layers"][-1]["H"]
                 dev.call("mgr_add2d", self.Y1[name], 2 * H, self.Y2[name], 2 * H, feat_buf.view(cols[name], (1,)), W,
                          B * T, 2 * H)
-        self.rng_step = saved_step
 
-    def _enqueue_fusion_head(self, train, rand, feat_buf, rng_step, dense=True):
+    def _enqueue_fusion_head(self, train, rand, feat_buf, rng_step, dense=True, lay=PLAIN):
         """Fusion BiLSTM (projection GEMMs + recurrences) and Dropout/Dense/softmax on stream 0 (dense=False: the caller runs
-        the Dense layer itself - the training step's mgr_head_fwd_bwd)."""
+        the Dense layer itself - the training step's mgr_head_fwd_bwd).  lay: the StepLayout of the training step this is part of."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         W = sp.concat_width
         save = train and not self.inference_only
-        self._fmt_train = bool(train)
-        saved_step, self.rng_step = self.rng_step, rng_step
         dev.stream(0)
         feat, ldf = feat_buf, W
         self._featin = feat_buf
@@ -955,27 +979,27 @@ class Engine:
             for di, dname in enumerate(("fwd", "bwd")):
                 L = self.dirs["fusion/%s" % dname]
                 Ls_pair.append(L)
-                mptr = self._prep_mask(L, train, rand, 500 + di)
+                mptr = self._prep_mask(L, train, rand, 500 + di, rng_step)
                 self._masks[(L.prefix, L.d)] = mptr
                 pair += [mptr, L.Wp, L.bp, self.ZF[di]]
             # (pipelined training: these GEMMs run while the next batch's deepest encoder scan holds the chip - the forms of the
             # pre-split products that fit on a CU beside a scan workgroup, not the 8-wave ones that wait for the scan to end)
-            with self._narrow_tiles(self._beside_scans and not self._wide_ok):
-                self._project_pair(feat_buf, W, pair, Ls_pair, B, T, W, Hf, XT=self._featT.get(feat_buf.ptr),
+            with self._narrow_tiles(lay.beside_scans and not lay.wide_ok):
+                self._project_pair(feat_buf, W, pair, Ls_pair, B, T, W, Hf, train, XT=self._featT.get(feat_buf.ptr),
                                    xt_ready=self._featT_ready.get(feat_buf.ptr, False), x_rows=self._feat_rows.get(feat_buf.ptr, True))
             self._zero_tails(lens, [(self.ZF[1], 4 * Hf, 4 * Hf)])
             dev.record(self.EV_FPROJ)   # (the next step's depth-1 scan is launched after these GEMMs, _enqueue_next_encoders)
-            if self._gate_words[0] is not None:
+            if lay.gate_fusion is not None:
                 # (Schedule.fused_encoder_scans: the fusion scan's 56 workgroups must land on the CUs the next batch's deepest encoder
                 #  scan - 208 whole CUs, released by the same event - leaves free, not on 56 CUs of their own.  That scan is enqueued
                 #  LATER in this call: it hands its launch number to the word this wait polls)
-                dev.call("mgr_stream_wait_resident_word", int(self._gate_words[0]), int(self.schedule.resident_wait_us))
+                dev.call("mgr_stream_wait_resident_word", int(lay.gate_fusion), int(self.schedule.resident_wait_us))
             for di, dname in enumerate(("fwd", "bwd")):
                 L = self.dirs["fusion/%s" % dname]
                 jobs.append(dict(Z=self.ZF[di], Up=L.Up, Y=self.YF.view(di * Hf, (1,)), ldy=2 * Hf, R=0, ldr=0,
                                  gates=L.gates if save else 0, cs=L.cs if save else 0, B=B, T=T, H=Hf,
                                  reverse=L.reverse))
-            self._scan_multi(jobs, "_ws_multi_f", form=self._fusion_scan_form)
+            self._scan_multi(jobs, "_ws_multi_f", form=lay.fusion_scan_form)
             self._zero_tails(lens, [(j["gates"], 4 * Hf, 4 * Hf) for j in jobs if j["reverse"] and j["gates"]])
             feat, ldf = self.YF, 2 * Hf
         # head
@@ -991,26 +1015,19 @@ class Engine:
                 self.head_mask.upload(np.asarray(rand["head/mask"], dtype=np.float32))
                 hm = self.head_mask.ptr
         elif train and p_head > 0:
-            self._head_seed = self._seed(999)
+            self._head_seed = self._seed(999, rng_step)
         self._head_args = (hm, p_head, self._head_seed)
-        self._head_step = self.rng_step      # (the counter this pass draws at: _sample_seed)
+        self._head_step = rng_step      # (the counter this pass draws at: _sample_seed)
         if dense:
             dev.call("mgr_dense_softmax_fwd", feat, ldf, hm, p_head, C.c_uint64(self._head_seed),
                      self._wview("dense/W"), self._wview("dense/b"), self.P, B, T, D, Cn)
             self._zero_tails(lens, [(self.P, Cn, Cn)])      # (what a caller gets does not depend on the padding anywhere)
         self._feat = (feat, ldf)
-        self.rng_step = saved_step
 
-    _wide_ok = False          # probe: with fused encoder scans no GEMM shares a CU with a scan workgroup - the library's own tile choice
-    _gate_words = (None, None)  # fused encoder scans: the host words through which the launches the fusion scan / the BPTT of the step
-                                # being enqueued wait for hand over their launch numbers
-    _enc_scan_form = _capi.SCAN_FORM_AUTO      # form of the encoder scan launches enqueued NOW (AUTO: the context's MGR_TUNE_SCAN_FORM)
-    _fusion_scan_form = _capi.SCAN_FORM_AUTO   # form of the fusion layer's scan launch
     _early_words = None      # seq_words dict of the generator in _early_gen
     _since_fresh = 0         # pipelined calls since the last one that started the next batch's pass itself (0 in such a call)
     _early_for = None        # the inputs the generator started last was announced for
     _early_gen = None        # _next_encoders_free generator of the batch after next, its first part already enqueued
-    _beside_scans = False    # the fusion layer's GEMMs of the step being enqueued run beside encoder scans of the next batch
 
     def _tuned(self, on, keys, keep_set=False):
         """Context manager: the library calls enqueued inside run with the tune keys `keys` ({key: value}, mgr.h); a caller's own
@@ -1628,14 +1645,13 @@ class Engine:
                            upload=True, prefetch_next=False, next_inputs=None, prefetch_after_next=False, after_next_inputs=None):
         """Enqueue one training step.  With prefetch_next (device-RNG training of a network whose encoders are frozen)
         the NEXT step's encoder pass is enqueued on a second stream into the other FEAT buffer right after this step's
-        fusion work, and this step consumes the encoder pass enqueued by the previous call (Schedule, DESIGN.md 5b).
+        fusion work, and this step consumes the encoder pass enqueued by the previous call (Schedule, DESIGN.md 6).
         prefetch_after_next (round 5; the caller promises that the call after the next one comes, with prefetch_next, for
         after_next_inputs): the encoder stream also gets the first part of THAT batch's pass - up to its deepest projections - at
         the end of this call instead of at the start of the next one.  The next call can only be made once the host has this step's
         loss (the CTC kernel, half-way through the step): the encoder stream used to sit idle from the end of its deepest scan
         until then (0.9 - 3.9 ms per step in the traces of round 5)."""
-        sp, dev, B, T = self.spec, self.dev, self.B, self.T
-        sch, ES = self.schedule, self.ES
+        dev, sch, ES, depth = self.dev, self.schedule, self.ES, self.depth
         if self._augment is not None and rand is not None:
             raise ValueError("a training step with set_augment on was given `rand`: host-supplied randomness has no augmentation plan "
                              "(set_augment(None) first)")
@@ -1644,9 +1660,8 @@ class Engine:
         for ahead_inputs in (next_inputs, after_next_inputs):
             self._check_lengths(ahead_inputs, augment=self._augment is not None)
         self._bind()
-        pipelined = prefetch_next and rand is None and self.can_pipeline and sch.pipeline
-        depth = max(len(s_["layers"]) for s_ in sp.streams)
-        # ---- 1. this step's encoder pass: the one the previous call prefetched, or in line on stream 0
+        pipelined = bool(prefetch_next and rand is None and self.frozen_fusion)
+        # ---- 1. this step's encoder pass: the one the previous call prefetched, or its own
         have = self._prefetched
         if have is not None:
             stale = rand is not None or not self.can_pipeline
@@ -1656,9 +1671,6 @@ class Engine:
                 dev.wait(0, ES)
                 have = None
         self._prefetched = None
-        defer = pipelined and sch.defer_param_grads and sp.fusion is not None and depth >= 2
-        any_tr_stream_ = any(s_["trainable"] for s_ in sp.streams)
-        host_blocking = bool(getattr(self.comm, "host_blocking", False))
         # What the encoder stream was handed a call early (the first part of the pass of the batch after this one) is settled BEFORE
         # this step's FEAT buffer is chosen: when the caller did not come back as announced - another batch, a predict /
         # loss_on_batch in between that discarded the prefetched pass - the early generator is dropped and its claim on the other FEAT
@@ -1666,52 +1678,76 @@ class Engine:
         # (A step without a prefetched pass always drops it: its own pass uses the encoder buffers the early part has written.)
         early, self._early_gen = self._early_gen, None
         early_words, self._early_words = self._early_words, None
-        keep_early = (have is not None and pipelined and defer and sch.encoders_run_ahead and sch.bptt_beside_deepest_scan and sp.fusion
-                      and not any_tr_stream_ and (not upload or next_inputs is self._early_for))
+        keep_early = have is not None and pipelined and self.can_run_free and (not upload or next_inputs is self._early_for)
         if early is not None and not keep_early:
             dev.wait(0, ES)
             self._feat_idx ^= 1        # (the generator toggled it when it was started; nothing of its pass has touched a FEAT buffer yet)
             early.close()
             early = None
+        # ---- the layout of this call: what _build resolved (can_*), narrowed by what only the call knows
+        # Round 6: a pipelined step WITHOUT a prefetched pass (the first step of a run, the step after a validation pass) runs its own
+        # encoder pass on the ENCODER stream, in the fused forms - nothing of this step can run beside it anyway, and from here on the
+        # call is a steady-state call: the next batch's pass follows on that stream at once, beside this step's trainable part, instead
+        # of behind a whole in-line pass in the plain forms and a stream-wide wait.  The step itself is what it was: same kernels'
+        # results, same order of randomness.
+        own_on_es = have is None and pipelined and self.can_fuse and sch.first_pass_on_encoder_stream
+        # (a call that runs its own encoder pass in line on stream 0 starts nothing ahead: that pass uses the encoder buffers)
+        has_pass = have is not None or own_on_es
+        defer = pipelined and self.can_defer
+        ahead = pipelined and self.can_run_ahead and has_pass
+        # Free-running encoder stream (Schedule.bptt_beside_deepest_scan): the next batch's encoder pass up to its deepest projections
+        # is handed to the encoder stream BEFORE this step's fusion work is enqueued - it depends on nothing of this step, and the
+        # host needs ~1-2 ms to enqueue the fusion layer and the head, during which that stream would sit idle
+        runs_free = pipelined and self.can_run_free and has_pass     # (a kept early generator implies it)
+        fresh = runs_free and early is None                          # ... and this call starts the next batch's pass itself
         # The fused forms of the encoder scans belong to every pass the encoder stream runs for a pipelined step (round 6: also the
         # passes of the first steps of a run, which round 5 ran in the plain form until a step had been announced two calls ahead)
-        fused_ok = bool(pipelined and defer and sch.fused_encoder_scans and sch.encoders_run_ahead and sch.bptt_beside_deepest_scan
-                        and sp.fusion and not any_tr_stream_ and not host_blocking)
-        own_on_es = False
-        if have is None:
-            if fused_ok and sch.first_pass_on_encoder_stream:
-                # Round 6: a pipelined step WITHOUT a prefetched pass (the first step of a run, the step after a validation pass) runs
-                # its own encoder pass on the ENCODER stream, in the fused forms - nothing of this step can run beside it anyway, and
-                # from here on the call is a steady-state call: the next batch's pass follows on that stream at once, beside this
-                # step's trainable part, instead of behind a whole in-line pass in the plain forms and a stream-wide wait.  The step
-                # itself is what it was: same kernels' results, same order of randomness.
-                dev.wait(ES, 0)        # (the encoder buffers / this FEAT buffer may still be read by what stream 0 has queued)
-                if upload:
-                    self._upload_inputs(inputs, None, True, stream=ES)
-                    self._xin_user[self._xin_slot] = self._step_id     # (this step reads them; frozen encoders: in this pass only)
-                cur = self._feat_ring[self._feat_idx]
-                self._enc_scan_form = _capi.SCAN_FORM_FUSED
-                try:
-                    self._enqueue_encoders(True, None, cur, ES, self.rng_step, augment=True)
-                finally:
-                    self._enc_scan_form = _capi.SCAN_FORM_AUTO
-                dev.wait(0, ES)
-                own_on_es = True
-            else:
-                if upload:
-                    self._upload_inputs(inputs, rand, True)
-                cur = self._feat_ring[self._feat_idx]
-                self._enqueue_encoders(True, rand, cur, 0, self.rng_step, augment=True)
-        else:
+        fused = pipelined and self.can_fuse and has_pass
+        two = bool(runs_free and prefetch_after_next and sch.encoders_two_ahead)
+        self._since_fresh = 0 if (fresh or not runs_free) else self._since_fresh + 1
+        free_words = early_words if early is not None else {}     # depth k -> the word the next pass's scan of depth k reports into
+        new_words = {}                                            # ... of the pass of the batch after next
+        lay = PLAIN._replace(beside_scans=pipelined)
+        if fused:
+            # Persistent launches of this call, in host order: fusion scan, BPTT, the next batch's deepest scan and - when the batch
+            # after next is announced - its depth-1 scan.  The encoder scans take the FUSED form (an argument of their launch), and
+            # each hands its launch number to the word the residency wait of the recurrence that runs BESIDE it polls (the waits are
+            # enqueued first).  Steady state: the fusion scan beside the next batch's deepest scan, the BPTT beside the depth-1 scan
+            # of the batch after next.  A call that starts the next batch's pass itself (fresh: the first steps of a run): the
+            # fusion scan beside that pass's depth-1 scan, the BPTT beside its deepest scan.
+            if fresh:
+                free_words[0] = self._new_seq_word()
+            wx = free_words[depth - 1] = self._new_seq_word()
+            wy = None
+            if two:
+                wy = new_words[0] = self._new_seq_word()
+            # (the call right after a fresh one: the encoder stream is still a phase behind - the deepest scan this call enqueues
+            #  starts milliseconds after the fusion scan is ready, and the wait for it ran into its bound, once per run: no wait)
+            late = (not fresh) and self._since_fresh == 1
+            gates = (free_words[0], wx) if fresh else ((None, wy) if late else (wx, wy))
+            lay = StepLayout(True, sch.fused_wide_tiles, _capi.SCAN_FORM_FUSED,
+                             _capi.SCAN_FORM_FUSED_ANY if sch.fusion_scan_fused else _capi.SCAN_FORM_AUTO, *gates)
+            self._gate_log.append((self._step_id, "fresh" if fresh else "steady", gates))
+        if have is not None:
             cur = have
             # this step's encoder pass (enqueued by the previous call) must be complete: the event behind its deepest scan - not
             # everything the encoder stream has been handed since (round 5 waited for the whole stream: in steady state the first part of
             # the NEXT batch's pass, queued behind it, is done by then anyway; in the first steps of a run it is not, and the second step
             # started 7 ms late)
             dev.wait_event(0, self.EV_ENC[self._feat_ring.index(cur)])
-        # (not in a call that ran its own encoder pass in line on stream 0: that pass uses the encoder buffers)
-        ahead = defer and sch.encoders_run_ahead and (have is not None or own_on_es)
-        free_ok = pipelined and ahead and sch.bptt_beside_deepest_scan and sp.fusion and not any_tr_stream_
+        elif own_on_es:
+            dev.wait(ES, 0)        # (the encoder buffers / this FEAT buffer may still be read by what stream 0 has queued)
+            if upload:
+                self._upload_inputs(inputs, None, True, stream=ES)
+                self._xin_user[self._xin_slot] = self._step_id     # (this step reads them; frozen encoders: in this pass only)
+            cur = self._feat_ring[self._feat_idx]
+            self._enqueue_encoders(True, None, cur, ES, self.rng_step, augment=True, scan_form=lay.enc_scan_form)
+            dev.wait(0, ES)
+        else:
+            if upload:
+                self._upload_inputs(inputs, rand, True)
+            cur = self._feat_ring[self._feat_idx]
+            self._enqueue_encoders(True, rand, cur, 0, self.rng_step, augment=True, scan_form=lay.enc_scan_form)
         if upload:
             self._upload_labels(labels, input_length, label_length)
         if pipelined:
@@ -1721,91 +1757,50 @@ class Engine:
                 dev.record(self.EV_PREV)   # only the launch that WRITES that buffer (the deepest scan) has to wait for it
             else:
                 dev.wait(ES, 0)
-        # Free-running encoder stream (Schedule.bptt_beside_deepest_scan): the next batch's encoder pass up to its deepest projections
-        # is handed to the encoder stream BEFORE this step's fusion work is enqueued - it depends on nothing of this step, and the
-        # host needs ~1-2 ms to enqueue the fusion layer and the head, during which that stream would sit idle
-        free_gen = None
-        free_words = None
-        fused = bool(fused_ok and free_ok)
-        fresh = False
-        self._gate_words = (None, None)
-        new_words = None
-        try:
-            if fused:
-                self._enc_scan_form = _capi.SCAN_FORM_FUSED     # every encoder scan launch enqueued from here to the end of this call
-            if early is not None:
-                free_gen, free_words = early, early_words   # (its first part was enqueued at the end of the previous call)
-            elif free_ok:
-                fresh = True
-                free_words = {}
-                if fused:
-                    free_words[0] = self._new_seq_word()
-                free_gen = self._next_encoders_free(next_inputs, depth, self.rng_step + 1, self._step_id + 1, seq_words=free_words)
-                next(free_gen)
-            # ---- 2., 3. fusion layer, head, CTC, loss read-back point, backward
-            # (fused: not with a host-blocking all-reduce - HostComm holds the host inside finish(), the depth-1 scan the BPTT's wait is
-            #  for would only be enqueued after it, the wait would always run into its bound; such runs share a GPU and use small per-rank
-            #  batches anyway)
-            two = bool(pipelined and free_gen is not None and prefetch_after_next and sch.encoders_two_ahead)
-            self._since_fresh = 0 if (fresh or free_gen is None) else self._since_fresh + 1
-            if fused:
-                # Persistent launches from here on, in host order: fusion scan, BPTT, the next batch's deepest scan and - when the batch
-                # after next is announced - its depth-1 scan.  The encoder scans take the FUSED form (an argument of their launch), and
-                # each hands its launch number to the word the residency wait of the recurrence that runs BESIDE it polls (the waits are
-                # enqueued first).  Steady state: the fusion scan beside the next batch's deepest scan, the BPTT beside the depth-1 scan
-                # of the batch after next.  A call that starts the next batch's pass itself (fresh: the first steps of a run): the
-                # fusion scan beside that pass's depth-1 scan (already enqueued: its word is filled), the BPTT beside its deepest scan.
-                wx = self._new_seq_word()
-                free_words[depth - 1] = wx
-                wy = None
-                if two and depth > 1:
-                    wy = self._new_seq_word()
-                    new_words = {0: wy}
-                # (the call right after a fresh one: the encoder stream is still a phase behind - the deepest scan this call enqueues
-                #  starts milliseconds after the fusion scan is ready, and the wait for it ran into its bound, once per run: no wait)
-                late = (not fresh) and self._since_fresh == 1
-                self._gate_words = (free_words.get(0), wx) if fresh else ((None, wy) if late else (wx, wy))
-                self._gate_log.append((self._step_id, "fresh" if fresh else "steady", self._gate_words))
-                self._wide_ok = bool(sch.fused_wide_tiles)
-                if sch.fusion_scan_fused:
-                    self._fusion_scan_form = _capi.SCAN_FORM_FUSED_ANY
-            finish = self._enqueue_trainable_part(cur, rand, pipelined, defer, sch.bptt_beside_deepest_scan, have is None and not own_on_es,
-                                                  apply_update)
+        free_gen = early      # (its first part was enqueued at the end of the previous call)
+        if fresh:
+            free_gen = self._next_encoders_free(next_inputs, self.rng_step + 1, self._step_id + 1, lay.enc_scan_form, seq_words=free_words)
+            next(free_gen)
+        # ---- 2., 3. fusion layer, head, CTC, loss read-back point, backward
+        finish = self._enqueue_trainable_part(cur, rand, lay, defer, pipelined and self.can_hold_bptt, not has_pass, apply_update)
 
-            # ---- 4. parameter gradients + optimizer, and (pipelined) the next step's encoder pass
-            if not pipelined:
-                finish()
-            elif free_gen is not None:
-                if new_words is None:
-                    new_words = {}
-                if two and sch.depth1_proj_ahead and self.Z1buf and depth > 1:
-                    # the batch AFTER the next one: its depth-1 projections in front of the next batch's deepest scan, the rest of its
-                    # first part at the end of this call (rng_step / _step_id were advanced above)
-                    def pre():
-                        self._early_gen = self._next_encoders_free(after_next_inputs, depth, self.rng_step + 1, self._step_id + 1,
-                                                                   split_first=True, seq_words=new_words)
-                        self._early_words = new_words
-                        next(self._early_gen)
-                    free_gen.send((finish, pre))
-                    next(self._early_gen)
-                else:
-                    free_gen.send(finish)
-                    if two:
-                        # the first part of the pass of the batch AFTER the next one (rng_step / _step_id were advanced above)
-                        self._early_gen = self._next_encoders_free(after_next_inputs, depth, self.rng_step + 1, self._step_id + 1,
-                                                                   seq_words=new_words)
-                        self._early_words = new_words
-                        next(self._early_gen)
+        # ---- 4. parameter gradients + optimizer, and (pipelined) the next step's encoder pass
+        if not pipelined:
+            finish()
+        elif free_gen is None:
+            self._enqueue_next_encoders(next_inputs, finish, defer, ahead, lay.enc_scan_form)
+        else:
+            def start_after_next(**kw):
+                # the first part of the pass of the batch AFTER the next one (rng_step / _step_id were advanced above)
+                self._early_gen = self._next_encoders_free(after_next_inputs, self.rng_step + 1, self._step_id + 1, lay.enc_scan_form,
+                                                           seq_words=new_words, **kw)
+                self._early_words = new_words
+                next(self._early_gen)
+            if two and self.Z1buf:
+                # (Schedule.depth1_proj_ahead, which Z1buf exists for) its depth-1 projections in front of the next batch's deepest
+                # scan, the rest of its first part at the end of this call
+                free_gen.send((finish, lambda: start_after_next(split_first=True)))
+                next(self._early_gen)
             else:
-                self._enqueue_next_encoders(next_inputs, finish, defer, ahead, depth,
-                                            free_running=bool(defer and sch.bptt_beside_deepest_scan and sp.fusion and not any_tr_stream_))
-        finally:
-            self._beside_scans = False
-            self._enc_scan_form = _capi.SCAN_FORM_AUTO
-            self._fusion_scan_form = _capi.SCAN_FORM_AUTO
-            self._wide_ok = False
-            self._gate_words = (None, None)
+                free_gen.send(finish)
+                if two:
+                    start_after_next()
         dev.stream(0)
+
+    def _mode_cfg(self, setter, cfg, what, what_parallel, kind=None, defaults=None):
+        """What set_risk / set_entropy / set_augment refuse alike, before anything of the mode set before is touched (a cfg that is
+        refused leaves the mode as it was): a communicator, an inference-only engine, keys that `defaults` does not have.  Returns
+        cfg over defaults."""
+        if self.comm is not None:
+            raise NotImplementedError("%s is single-GPU: data-parallel %s is not implemented" % (what, what_parallel))
+        if self.inference_only:
+            raise ValueError("%s on an inference-only engine" % setter)
+        if defaults is None:
+            return cfg
+        unknown = set(cfg) - set(defaults)
+        if unknown:
+            raise ValueError("unknown %s settings %s (known: %s)" % (kind, sorted(unknown), sorted(defaults)))
+        return dict(defaults, **cfg)
 
     RISK_DEFAULTS = dict(top_paths=8, beam_width=16, ctc_weight=0.1, costs=(1, 1, 1), post_scale=1.0, max_labels=None, source="beam",
                          sample_seed=None)
@@ -1835,14 +1830,7 @@ class Engine:
             return
         if self._entropy is not None:
             raise ValueError("set_risk with the entropy mode on: the two training modes are not combined (set_entropy(None) first)")
-        if self.comm is not None:
-            raise NotImplementedError("minimum-risk training is single-GPU: data-parallel risk training is not implemented")
-        if self.inference_only:
-            raise ValueError("set_risk on an inference-only engine")
-        unknown = set(cfg) - set(self.RISK_DEFAULTS)
-        if unknown:
-            raise ValueError("unknown risk settings %s (known: %s)" % (sorted(unknown), sorted(self.RISK_DEFAULTS)))
-        cfg = dict(self.RISK_DEFAULTS, **cfg)
+        cfg = self._mode_cfg("set_risk", cfg, "minimum-risk training", "risk training", "risk", self.RISK_DEFAULTS)
         sp, lib, B, T = self.spec, self.lib, self.B, self.T
         Cn, skip = sp.num_classes, int(sp.ctc["skip"])
         K, W = int(cfg["top_paths"]), int(cfg["beam_width"])
@@ -1886,15 +1874,30 @@ class Engine:
             self.mem.release(self._risk["bufs"])
             self._risk = None
 
-    def _enqueue_risk_head(self, feat, ldf, hm, p_head, hseed, dA, ldda):
-        """The head of a minimum-risk step on the current stream (set_risk): Dropout / Dense / softmax, the CTC gradient scaled
-        ctc_weight / B, the N-best list, its edit distances, the risk gradient ADDED with 1 / B, the two means, Dense backward."""
-        sp, dev, B, T, r = self.spec, self.dev, self.B, self.T, self._risk
-        cfg = r["cfg"]
-        Cn, D, skip, eps = sp.num_classes, sp.head_width, int(sp.ctc["skip"]), float(sp.ctc["eps"])
-        K, cw = cfg["top_paths"], float(cfg["ctc_weight"])
+    def _enqueue_mode_head(self, feat, ldf, hm, p_head, hseed, dA, ldda, losses):
+        """The head of a step of a training mode on the current stream, the separate calls mgr_head_fwd_bwd equals: Dropout / Dense /
+        softmax, then losses() - the mode's loss and gradient kernels from P into dLogits; it returns the per-sample arrays of the two
+        parts read_loss reports (the first None: not computed, reported as 0) -, their means, Dense backward."""
+        sp, dev, B, T = self.spec, self.dev, self.B, self.T
+        Cn, D = sp.num_classes, sp.head_width
         dev.call("mgr_dense_softmax_fwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self._wview("dense/W"), self._wview("dense/b"), self.P,
                  B, T, D, Cn)
+        first, second = losses()
+        if first is not None:
+            dev.call("mgr_mean", first, B, self.loss_mean)
+        else:
+            self.loss_mean.zero()
+        dev.call("mgr_mean", second, B, self.loss_mean.view(1, (1,)))
+        dev.call("mgr_dense_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self.dLogits, self._wview("dense/W"), self._gview("dense/W"),
+                 self._gview("dense/b"), dA, ldda, B, T, D, Cn, self.ws_dense, self.ws_dense.nbytes)
+
+    def _risk_losses(self):
+        """The middle of a minimum-risk step's head (set_risk): the CTC gradient scaled ctc_weight / B, the N-best list, its edit
+        distances, the risk gradient ADDED with 1 / B."""
+        sp, dev, B, T, r = self.spec, self.dev, self.B, self.T, self._risk
+        cfg = r["cfg"]
+        Cn, skip, eps = sp.num_classes, int(sp.ctc["skip"]), float(sp.ctc["eps"])
+        K, cw = cfg["top_paths"], float(cfg["ctc_weight"])
         if cw != 0.0:
             dev.call("mgr_ctc_loss_grad", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1, eps, cw / B,
                      self.loss_b, self.dLogits, self.ws_ctc, self.ws_ctc.nbytes)
@@ -1910,13 +1913,7 @@ class Engine:
         dev.call("mgr_ctc_risk_grad", self.P, self.ilen_d, B, T, Cn, skip, Cn - 1, eps, None, None, 0, r["out"], r["out_len"], K, T - skip,
                  cfg["max_labels"], r["dist"], 1.0, float(cfg["post_scale"]), 1.0 / B, 1 if cw != 0.0 else 0, r["logp"], r["weight"],
                  r["exp_risk"], self.dLogits, r["ws_risk"], r["ws_risk"].nbytes)
-        if cw != 0.0:
-            dev.call("mgr_mean", self.loss_b, B, self.loss_mean)
-        else:
-            self.loss_mean.zero()        # (the CTC loss was not computed: it is reported as 0)
-        dev.call("mgr_mean", r["exp_risk"], B, self.loss_mean.view(1, (1,)))
-        dev.call("mgr_dense_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self.dLogits, self._wview("dense/W"), self._gview("dense/W"),
-                 self._gview("dense/b"), dA, ldda, B, T, D, Cn, self.ws_dense, self.ws_dense.nbytes)
+        return (self.loss_b if cw != 0.0 else None), r["exp_risk"]
 
     ENTROPY_DEFAULTS = dict(weight=0.2)
     last_entropy = None
@@ -1932,16 +1929,9 @@ class Engine:
         if cfg is None:
             self._release_entropy()
             return
-        if self.comm is not None:
-            raise NotImplementedError("entropy-regularised training is single-GPU: data-parallel entropy training is not implemented")
-        if self.inference_only:
-            raise ValueError("set_entropy on an inference-only engine")
         if self._risk is not None:
             raise ValueError("set_entropy with the risk mode on: the two training modes are not combined (set_risk(None) first)")
-        unknown = set(cfg) - set(self.ENTROPY_DEFAULTS)
-        if unknown:
-            raise ValueError("unknown entropy settings %s (known: %s)" % (sorted(unknown), sorted(self.ENTROPY_DEFAULTS)))
-        cfg = dict(self.ENTROPY_DEFAULTS, **cfg)
+        cfg = self._mode_cfg("set_entropy", cfg, "entropy-regularised training", "entropy training", "entropy", self.ENTROPY_DEFAULTS)
         weight = float(cfg["weight"])
         if not weight >= 0.0 or not np.isfinite(weight):
             raise ValueError("weight >= 0, got %r" % (cfg["weight"],))
@@ -1958,19 +1948,14 @@ class Engine:
             self.mem.release(self._entropy["bufs"])
             self._entropy = None
 
-    def _enqueue_entropy_head(self, feat, ldf, hm, p_head, hseed, dA, ldda):
-        """The head of an entropy-regularised step on the current stream (set_entropy): Dropout / Dense / softmax, the CTC loss and the
-        alignment entropy with the gradient of (loss - weight H) / B, the two means, Dense backward."""
+    def _entropy_losses(self):
+        """The middle of an entropy-regularised step's head (set_entropy): the CTC loss and the alignment entropy with the gradient of
+        (loss - weight H) / B."""
         sp, dev, B, T, e = self.spec, self.dev, self.B, self.T, self._entropy
-        Cn, D, skip, eps = sp.num_classes, sp.head_width, int(sp.ctc["skip"]), float(sp.ctc["eps"])
-        dev.call("mgr_dense_softmax_fwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self._wview("dense/W"), self._wview("dense/b"), self.P,
-                 B, T, D, Cn)
+        Cn, skip, eps = sp.num_classes, int(sp.ctc["skip"]), float(sp.ctc["eps"])
         dev.call("mgr_ctc_entropy_grad", self.P, self.labels_d, self.ilen_d, self.llen_d, B, T, Cn, self.Lmax, skip, Cn - 1, eps, 1.0 / B,
                  e["cfg"]["weight"] / B, self.loss_b, e["H"], self.dLogits, e["ws"], e["ws"].nbytes)
-        dev.call("mgr_mean", self.loss_b, B, self.loss_mean)
-        dev.call("mgr_mean", e["H"], B, self.loss_mean.view(1, (1,)))
-        dev.call("mgr_dense_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self.dLogits, self._wview("dense/W"), self._gview("dense/W"),
-                 self._gview("dense/b"), dA, ldda, B, T, D, Cn, self.ws_dense, self.ws_dense.nbytes)
+        return self.loss_b, e["H"]
 
     def set_augment(self, cfg):
         """Train-time input augmentation (augment.py): with cfg - a dict over augment.DEFAULTS - the encoder pass of every
@@ -1985,10 +1970,7 @@ class Engine:
         if cfg is None:
             self._release_augment()
             return
-        if self.comm is not None:
-            raise NotImplementedError("input augmentation is single-GPU: data-parallel augmentation is not implemented")
-        if self.inference_only:
-            raise ValueError("set_augment on an inference-only engine")
+        self._mode_cfg("set_augment", cfg, "input augmentation", "augmentation")     # (its keys: normalize_config)
         norm = augment_mod.normalize_config(cfg, self.spec, self.T)
         n = augment_mod.plan_len(norm)
         self._release_augment()     # (the cfg is good: only now does the mode set before go)
@@ -2018,14 +2000,13 @@ class Engine:
             self.dev.wait(0, self.ES)
             self._prefetched = None
 
-    def _enqueue_trainable_part(self, cur, rand, beside_scans, defer, late_ok, own_inputs, apply_update):
-        """Steps 2 and 3 of a training step on stream 0 - fusion layer, head, CTC, the loss read-back point, the backward pass up to
-        what `defer` / `late_ok` hold back - and the closure `finish(gate=None)` that enqueues the rest (held-back BPTT, dW / dU / db
-        GEMMs, optimizer)."""
+    def _enqueue_trainable_part(self, cur, rand, lay, defer, hold_bptt, own_inputs, apply_update):
+        """Steps 2 and 3 of a training step of layout `lay` on stream 0 - fusion layer, head, CTC, the loss read-back point, the
+        backward pass up to what `defer` (the dW / dU / db GEMMs) / `hold_bptt` (the fusion layer's BPTT with them) hold back - and the
+        closure `finish(gate=None)` that enqueues the rest (held-back BPTT, dW / dU / db GEMMs, optimizer)."""
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         # ---- 2. fusion layer, head, CTC, loss read-back point
-        self._beside_scans = bool(beside_scans)
-        self._enqueue_fusion_head(True, rand, cur, self.rng_step, dense=False)
+        self._enqueue_fusion_head(True, rand, cur, self.rng_step, dense=False, lay=lay)
         self.rng_step += 1
         Cn, D = sp.num_classes, sp.head_width
         dev.stream(0)
@@ -2045,11 +2026,9 @@ class Engine:
         #  recurrence workgroups get one of the 48 other CUs each, and neither they nor the per-frame kernels share SIMDs with the scan,
         #  which is on the step's critical path)
         ctc_lds = {_capi.TUNE_CTC_CHAIN_LDS_KIB: 96, _capi.TUNE_CTC_FRAME_LDS_KIB: 64}
-        with self._tuned(self._gate_words[0] is not None or self._gate_words[1] is not None, ctc_lds, keep_set=True):
-            if self._risk is not None:
-                self._enqueue_risk_head(feat, ldf, hm, p_head, hseed, dA, ldda)
-            elif self._entropy is not None:
-                self._enqueue_entropy_head(feat, ldf, hm, p_head, hseed, dA, ldda)
+        with self._tuned(lay.fused, ctc_lds, keep_set=True):
+            if self._risk is not None or self._entropy is not None:
+                self._enqueue_mode_head(feat, ldf, hm, p_head, hseed, dA, ldda, self._risk_losses if self._risk is not None else self._entropy_losses)
             else:
                 dev.call("mgr_head_fwd_bwd", feat, ldf, hm, p_head, C.c_uint64(hseed), self._wview("dense/W"), self._wview("dense/b"),
                          self.labels_d, self.ilen_d, self.llen_d, B, T, D, Cn, self.Lmax, int(sp.ctc["skip"]), Cn - 1, float(sp.ctc["eps"]),
@@ -2079,9 +2058,9 @@ class Engine:
         late_bptt = None    # (Schedule.bptt_beside_deepest_scan) the fusion layer's BPTT itself is held back with its GEMMs
         if sp.fusion:
             Hf = sp.fusion["H"]
-            bargs = ("fusion", self.dYF, 2 * Hf, self._featin, W, W, self.YF, 2 * Hf, self.dFEAT if any_tr_stream else None, W)
+            bargs = ("fusion", self.dYF, 2 * Hf, self._featin, W, W, self.YF, 2 * Hf, self.dFEAT if any_tr_stream else None, W, lay)
             bkw = dict(defer_param_grads=defer, XinT=self._featT.get(self._featin.ptr), xin_rows=self._feat_rows.get(self._featin.ptr, True))
-            if defer and late_ok and not any_tr_stream:
+            if hold_bptt:
                 late_bptt = lambda: self._bilstm_backward(*bargs, **bkw)
             else:
                 deferred = self._bilstm_backward(*bargs, **bkw)
@@ -2089,12 +2068,10 @@ class Engine:
             col = 0
             for s in sp.streams:
                 if s["trainable"]:
-                    self._stream_backward(s, col)
+                    self._stream_backward(s, col, lay)
                 col += sp.stream_width(s)
             dev.stream(0)
             dev.record(self.EV_IN[self._xin_slot])   # trainable first layers read the inputs again in their dW GEMMs
-
-        gate_b = self._gate_words[1]
 
         def finish(gate=None):
             """This step's (held-back) BPTT, its dW / dU / db GEMMs and the optimizer on stream 0.  gate: enqueues the device-side
@@ -2103,9 +2080,9 @@ class Engine:
             launch" would be the BPTT queued behind the gate) and in FRONT of the chip-filling GEMMs, which are what
             must not be placed before the scan's workgroups: recurrence beside recurrence starts at once, GEMMs wait."""
             dev.stream(0)
-            if gate_b is not None and late_bptt is not None:
+            if lay.gate_bptt is not None and late_bptt is not None:
                 # (as for the fusion scan: the depth-1 scan of the batch after next, enqueued at the end of this call, fills the word)
-                dev.call("mgr_stream_wait_resident_word", int(gate_b), int(self.schedule.resident_wait_us))
+                dev.call("mgr_stream_wait_resident_word", int(lay.gate_bptt), int(self.schedule.resident_wait_us))
             d = late_bptt() if late_bptt is not None else deferred
             if gate is not None:
                 gate()
@@ -2115,7 +2092,7 @@ class Engine:
                 self.apply_gradients()
         return finish
 
-    def _next_encoders_free(self, next_inputs, depth, rng_step, consumer_step, split_first=False, seq_words=None):
+    def _next_encoders_free(self, next_inputs, rng_step, consumer_step, scan_form, split_first=False, seq_words=None):
         """Schedule.bptt_beside_deepest_scan, as a generator.  Part 1 (before this step's fusion work is enqueued): the next
         batch's encoder pass on stream ES up to and including its deepest projection GEMMs.  Part 2 (after the loss read-back point,
         resumed with send(finish) or send((finish, pre))): stream 0 waits for those GEMMs, then - once the deepest scan launched behind
@@ -2124,7 +2101,7 @@ class Engine:
         split_first (Schedule.depth1_proj_ahead): part 1 comes in two pieces - upload, noise and the depth-1 projections into the
         engine's second set of gate pre-activation buffers, then one more yield, then the rest - so that a caller can put the first
         piece in front of the PREVIOUS batch's deepest scan (its `pre`)."""
-        dev, ES = self.dev, self.ES
+        dev, ES, depth = self.dev, self.ES, self.depth
         self._feat_idx ^= 1
         nxt = self._feat_ring[self._feat_idx]
         self._early_for = next_inputs          # (becomes _prefetched_for when the pass is complete: two announcements may be in flight)
@@ -2134,7 +2111,7 @@ class Engine:
             self._xin_user[self._xin_slot] = consumer_step
         split_first = bool(split_first and self.Z1buf)
         phases = self._encoder_phases(True, None, nxt, ES, rng_step, z_first=self.Z1buf if split_first else None, seq_words=seq_words,
-                                      augment=True)
+                                      augment=True, scan_form=scan_form)
         for tag, k in phases:
             if tag == "projected" and k == 0 and split_first and depth > 1:
                 dev.stream(0)
@@ -2176,10 +2153,11 @@ class Engine:
             return None
         return lambda: self.dev.call("mgr_stream_wait_next_resident", self.schedule.resident_wait_us)
 
-    def _enqueue_next_encoders(self, next_inputs, finish, defer, ahead, depth, free_running=False):
+    def _enqueue_next_encoders(self, next_inputs, finish, defer, ahead, scan_form):
         """Encoder pass of the NEXT step on stream ES into the other FEAT buffer, concurrent with what enqueue_train_step
-        has put on stream 0; `finish` (this step's parameter-gradient GEMMs + optimizer) is placed according to the schedule."""
-        dev, ES = self.dev, self.ES
+        has put on stream 0; `finish` (this step's parameter-gradient GEMMs + optimizer) is placed according to the schedule.
+        (A step that may run the encoder stream free - `ahead` and the BPTT held back - goes through _next_encoders_free instead.)"""
+        dev, ES, depth = self.dev, self.ES, self.depth
         self._feat_idx ^= 1
         nxt = self._feat_ring[self._feat_idx]
         self._prefetched_for = next_inputs
@@ -2189,7 +2167,7 @@ class Engine:
             self._xin_user[self._xin_slot] = self._step_id   # (already advanced: the step that will consume it)
         if not defer:
             finish()
-            self._enqueue_encoders(True, None, nxt, ES, self.rng_step, hold_scans_for=0, augment=True)
+            self._enqueue_encoders(True, None, nxt, ES, self.rng_step, hold_scans_for=0, augment=True, scan_form=scan_form)
         else:
             # The dW/dU GEMMs of THIS step and the optimizer are held back until the next step's deepest projection GEMMs are
             # done and then run beside its deepest encoder scan: GEMM next to GEMM gains nothing, whereas a big scan leaves
@@ -2199,10 +2177,10 @@ class Engine:
             # depth-1 scan is launched after this step's fusion projections (a persistent launch placed among chip-filling
             # GEMMs gets a poor CU set), and only the deepest scan - the one that overwrites the FEAT buffer the previous
             # step's dW GEMMs read - waits for that step.
-            for tag, k in self._encoder_phases(True, None, nxt, ES, self.rng_step, augment=True):
+            for tag, k in self._encoder_phases(True, None, nxt, ES, self.rng_step, augment=True, scan_form=scan_form):
                 if tag != "projected":
                     continue
-                if ahead and k == 0 and not free_running:
+                if ahead and k == 0:
                     dev.stream(ES)
                     dev.wait_event(ES, self.EV_FPROJ)
                 if k == depth - 1:
@@ -2221,8 +2199,8 @@ class Engine:
         dev.record(self.EV_ENC[self._feat_ring.index(nxt)])
         self._prefetched = nxt
 
-    def _bilstm_backward(self, prefix, dY, lddy, Xin, ldx, fin, Hbuf, ldh, dX, lddx, defer_param_grads=False, XinT=None, xin_rows=True):
-        """BPTT + parameter grads of one Bidirectional layer (both directions in one persistent launch).
+    def _bilstm_backward(self, prefix, dY, lddy, Xin, ldx, fin, Hbuf, ldh, dX, lddx, lay, defer_param_grads=False, XinT=None, xin_rows=True):
+        """BPTT + parameter grads of one Bidirectional layer (both directions in one persistent launch) in a step of layout `lay`.
         defer_param_grads: return the dW/dU/db GEMM launches as a closure instead of enqueuing them now.
         XinT: the transposed copy of Xin the forward projection was fed (same step), if the engine keeps one - the
         dropout-aware dW then reads both of its operands along time.
@@ -2240,16 +2218,14 @@ class Engine:
         need = self.lib.mgr_lstm_scan_bwd_multi_ws_bytes(len(jobs), arr)
         if getattr(self, "_ws_bwd_multi", None) is None or self._ws_bwd_multi.nbytes < need:
             self._ws_bwd_multi = self.mem.bytes(need)
-        beside_scans = self._beside_scans     # (the deferred GEMMs run beside the next batch's encoder scans as well)
-        wide_ok = self._wide_ok
         # The form of the narrow-layer BPTT is an argument of the launch (mgr.h MGR_BPTT_FORM_*; AUTO = the context's MGR_TUNE_BPTT_FORM):
         # beside the next batch's encoder scans the form that yields to them - or, beside FUSED encoder scans (CUs of its own) and if the
         # schedule asks for it, the direct gather with one barrier per step; a launch that has the chip to itself takes the context's.
         form = _capi.BPTT_FORM_AUTO
-        if beside_scans and self.schedule.bptt_yields_beside_scans:
-            direct = (self._wide_ok or self._gate_words[1] is not None) and self.schedule.bptt_direct_when_alone
+        if lay.beside_scans and self.schedule.bptt_yields_beside_scans:
+            direct = (lay.wide_ok or lay.gate_bptt is not None) and self.schedule.bptt_direct_when_alone
             form = _capi.BPTT_FORM_DIRECT if direct else _capi.BPTT_FORM_YIELDING
-            if self._gate_words[0] is not None and self.schedule.bptt_fused:     # (a step of the fused schedule)
+            if lay.gate_fusion is not None and self.schedule.bptt_fused:     # (a step of the fused schedule)
                 form = _capi.BPTT_FORM_FUSED_DIRECT if direct else _capi.BPTT_FORM_FUSED
         if self.schedule.bptt_single_cu and jobs[0]["H"] in (32, 64, 100):
             form = _capi.BPTT_FORM_SINGLE_CU       # (whatever the schedule puts beside it: the choice must not depend on the layout)
@@ -2281,7 +2257,7 @@ class Engine:
                     if self.schedule.du_split and H >= 16:
                         self._prep_hst(L, Hbuf.view(di * H, (1,)), ldh)
                         hst, L.hst_ready = L.HsT, False
-                    with self._narrow_tiles(beside_scans and not wide_ok):
+                    with self._narrow_tiles(lay.beside_scans and not lay.wide_ok):     # (the deferred GEMMs run beside the encoder scans as well)
                         dev.call("mgr_lstm_param_grads_dropout_ts", XinT, self.ldt, mptr, float(L.p), Hbuf.view(di * H, (1,)), ldh, L.dZ,
                                  L.gWp, L.gUp, L.gbp, B, T, fin, H, L.reverse, L.ws_pg, L.ws_pg.nbytes, L.dzmax, L.dbsum, pws, hst)
                 elif kind == "t":
@@ -2318,7 +2294,7 @@ class Engine:
         self.dev.call("mgr_transpose_bt_split_shift", Hdir, ldh, L.HsT, self.ldt, self.B, self.T, L.H, 1 if L.reverse else -1)
         L.hst_ready = True
 
-    def _stream_backward(self, s, col):
+    def _stream_backward(self, s, col, lay):
         sp, dev, B, T = self.spec, self.dev, self.B, self.T
         W = sp.concat_width
         name = s["name"]
@@ -2332,15 +2308,15 @@ class Engine:
             else:
                 Hbuf, ldh = self.FEAT.view(col, (1,)), W
             self._bilstm_backward("%s/l1" % name, dout, W, self.Y1[name], 2 * H1, 2 * H1, Hbuf, ldh,
-                                  self.dY1[name], 2 * H1, XinT=self.Y1T.get(name))
+                                  self.dY1[name], 2 * H1, lay, XinT=self.Y1T.get(name))
             if s["residual"]:
                 dev.call("mgr_add2d", self.dY1[name], 2 * H1, dout, W, self.dY1[name], 2 * H1, B * T, 2 * H1)
             self._bilstm_backward("%s/l0" % name, self.dY1[name], 2 * H1, self._xcur[name], s["F"], s["F"],
-                                  self.Y1[name], 2 * H1, dF, s["F"] if dF is not None else 0)
+                                  self.Y1[name], 2 * H1, dF, s["F"] if dF is not None else 0, lay)
         else:
             H1 = s["layers"][0]["H"]
             self._bilstm_backward("%s/l0" % name, dout, W, self._xcur[name], s["F"], s["F"],
-                                  self.FEAT.view(col, (1,)), W, dF, s["F"] if dF is not None else 0)
+                                  self.FEAT.view(col, (1,)), W, dF, s["F"] if dF is not None else 0, lay)
         if dF is not None:
             self._frontend_bwd(name)
 
