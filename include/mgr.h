@@ -464,6 +464,43 @@ size_t mgr_lstm_scan_bwd_multi_ws_bytes(int njobs, const mgr_scan_bwd_job* jobs)
 int mgr_lstm_scan_bwd_multi(mgr_ctx* ctx, int njobs, const mgr_scan_bwd_job* jobs, void* ws, size_t ws_bytes);
 int mgr_lstm_scan_bwd_multi_ex(mgr_ctx* ctx, int njobs, const mgr_scan_bwd_job* jobs, void* ws, size_t ws_bytes,
                                const mgr_scan_launch_opts* opts);   /* opts->form: MGR_BPTT_FORM_* */
+/* What a multi-scan call launches, as a value: the decision the two *_multi_ex calls carry out (csrc/scan_choice.h), made by pure
+ * host functions of the CU count, the tune keys (tune[0 .. ntune), keys beyond ntune read as 0), the job list and opts->form.  The
+ * describe calls need no context and no GPU and enqueue nothing; they check the job list and the form like the calls themselves
+ * (same return code, same mgr_last_error) and fill *out, whose struct_size the caller has set to sizeof *out.  Pointers of the jobs
+ * are looked at (NULL or not, alignment), never followed.
+ *   kernel     forward MGR_SCAN_FWD_*, backward MGR_SCAN_BWD_*: the persistent cluster kernel of the call; NONE (0): no such launch
+ *   grid, block, lds_bytes   its launch; waves per workgroup, workgroups per_cu, live workgroups (forward: those that run a cluster)
+ *   ledger     the launch takes a place in the residency ledger (opts->seq_out gets its number; else MGR_SEQ_NONE)
+ *   need       workspace bytes of exactly this call; base_need: header + exchange images; zero_bytes: what is zeroed ahead of the launch
+ *   degraded   forward: ws_bytes < base_need kept the jobs off the cluster kernels
+ *   single_cu  backward: the call is ONE launch of the single-CU split-f16 kernel (fallback CU16 for every job)
+ *   job[i]     cluster: runs in the cluster kernel, as nbg clusters of G unit groups on `members` workgroups each, laid out by cls_*;
+ *              else fallback MGR_SCAN_FALLBACK_*.  yt_in_kernel: the kernel writes the transposed copy (else a transpose follows);
+ *              rows_in_scratch: the job gave no Y and its rows go to the workspace at rows_off; xbuf_off: its exchange images. */
+enum { MGR_SCAN_CHOICE_MAX_JOBS = 8 };
+enum { MGR_SCAN_FWD_NONE = 0, MGR_SCAN_FWD_IMAGE = 1, MGR_SCAN_FWD_KS = 2, MGR_SCAN_FWD_KS_S = 3, MGR_SCAN_FWD_K16 = 4, MGR_SCAN_FWD_K16_S = 5,
+       MGR_SCAN_FWD_K16_FUSED = 6 };
+enum { MGR_SCAN_BWD_NONE = 0, MGR_SCAN_BWD = 1, MGR_SCAN_BWD_S = 2, MGR_SCAN_BWD_SPLIT = 3, MGR_SCAN_BWD_16 = 4, MGR_SCAN_BWD_16_S = 5,
+       MGR_SCAN_BWD_16_SL = 6, MGR_SCAN_BWD_16_SD = 7, MGR_SCAN_BWD_16_SPLIT = 8, MGR_SCAN_BWD_16_F = 9, MGR_SCAN_BWD_16_FD = 10 };
+enum { MGR_SCAN_FALLBACK_NONE = 0, MGR_SCAN_FALLBACK_SIMPLE = 1, MGR_SCAN_FALLBACK_MFMA = 2, MGR_SCAN_FALLBACK_MFMA_JOINT = 3,
+       MGR_SCAN_FALLBACK_CU16 = 4 };
+typedef struct mgr_scan_choice_job {
+  int cluster, fallback, nw, tpw, G, nbg, members, cls_begin, cls_nclusters, cls_cluster0, cls_rot, yt_in_kernel, rows_in_scratch, reserved;
+  unsigned long long xbuf_off, rows_off;
+} mgr_scan_choice_job;
+typedef struct mgr_scan_choice {
+  unsigned struct_size;
+  int njobs, kernel, grid, block, lds_bytes, waves, per_cu, live, xcd_local, fused, exchange, ksplit, split16, split, single_cu, ledger, degraded;
+  unsigned long long base_need, need, zero_bytes;
+  mgr_scan_choice_job job[MGR_SCAN_CHOICE_MAX_JOBS];
+} mgr_scan_choice;
+/* ws_bytes: the workspace the call would be given ((size_t)-1: as much as it takes - then need is what
+ * mgr_lstm_scan_fwd_multi_ws_bytes says in a context with these tune keys) */
+int mgr_lstm_scan_fwd_describe(int cu_count, const int* tune, int ntune, int njobs, const mgr_scan_job* jobs,
+                               const mgr_scan_launch_opts* opts, size_t ws_bytes, mgr_scan_choice* out);
+int mgr_lstm_scan_bwd_describe(int cu_count, const int* tune, int ntune, int njobs, const mgr_scan_bwd_job* jobs,
+                               const mgr_scan_launch_opts* opts, mgr_scan_choice* out);
 /* Parameter gradients from dZ (all packed layouts, f32 MFMA split-K GEMMs, deterministic slab reduce):
  *   dWp[F,4H] = sum_rows (X (.) mask4)^T dZ ;  dUp[H,4H] = sum_rows hprev^T dZ ;  dbp[4H] = sum_rows dZ
  * Hs is the layer's own un-residualed output h (row stride ldh); hprev is its time-shifted view. */

@@ -96,6 +96,8 @@ SIGNATURES = {
     "mgr_lstm_scan_bwd_multi": (i32, [vp, i32, vp, vp, sz]),
     "mgr_lstm_scan_bwd_multi_ex": (i32, [vp, i32, vp, vp, sz, vp]),
     "mgr_lstm_scan_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz]),
+    "mgr_lstm_scan_fwd_describe": (i32, [i32, vp, i32, i32, vp, vp, sz, vp]),
+    "mgr_lstm_scan_bwd_describe": (i32, [i32, vp, i32, i32, vp, vp, vp]),
     "mgr_lstm_param_grads_ws_bytes": (sz, [i32, i32, i32, i32]),
     "mgr_lstm_param_grads": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz]),
     "mgr_lstm_param_grads_dropout_ws_bytes": (sz, [i32, i32, i32, i32]),
@@ -179,6 +181,57 @@ class ScanBwdJob(C.Structure):
 class ScanLaunchOpts(C.Structure):
     """struct mgr_scan_launch_opts"""
     _fields_ = [("struct_size", C.c_uint), ("form", i32), ("seq_out", vp)]
+
+
+class ScanChoiceJob(C.Structure):
+    """struct mgr_scan_choice_job"""
+    _fields_ = [(n, i32) for n in ("cluster", "fallback", "nw", "tpw", "G", "nbg", "members", "cls_begin", "cls_nclusters", "cls_cluster0",
+                                   "cls_rot", "yt_in_kernel", "rows_in_scratch", "reserved")] + [("xbuf_off", u64), ("rows_off", u64)]
+
+
+class ScanChoice(C.Structure):
+    """struct mgr_scan_choice: what a multi-scan call launches (csrc/scan_choice.h)"""
+    _fields_ = ([("struct_size", C.c_uint)] +
+                [(n, i32) for n in ("njobs", "kernel", "grid", "block", "lds_bytes", "waves", "per_cu", "live", "xcd_local", "fused", "exchange",
+                                    "ksplit", "split16", "split", "single_cu", "ledger", "degraded")] +
+                [("base_need", u64), ("need", u64), ("zero_bytes", u64), ("job", ScanChoiceJob * 8)])
+
+    def to_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "job")}
+        d["job"] = [{n: getattr(self.job[i], n) for n, _ in ScanChoiceJob._fields_ if n != "reserved"} for i in range(self.njobs)]
+        return d
+
+
+# mgr_scan_choice.kernel -> kernel name (MGR_SCAN_FWD_* / MGR_SCAN_BWD_* of include/mgr.h); job[i].fallback (MGR_SCAN_FALLBACK_*)
+SCAN_FWD_KERNELS = ["", "k_scan_cluster", "k_scan_cluster_ks", "k_scan_cluster_ks_s", "k_scan_cluster_k16", "k_scan_cluster_k16_s",
+                    "k_scan_cluster_k16fs"]
+SCAN_BWD_KERNELS = ["", "k_scan_cluster_bwd", "k_scan_cluster_bwd_s", "k_scan_cluster_bwd_split", "k_scan_cluster_bwd16", "k_scan_cluster_bwd16_s",
+                    "k_scan_cluster_bwd16_sl", "k_scan_cluster_bwd16_sd", "k_scan_cluster_bwd16_split", "k_scan_cluster_bwd16_f",
+                    "k_scan_cluster_bwd16_fd"]
+SCAN_FALLBACK_NONE, SCAN_FALLBACK_SIMPLE, SCAN_FALLBACK_MFMA, SCAN_FALLBACK_MFMA_JOINT, SCAN_FALLBACK_CU16 = range(5)
+
+
+def describe_scan(direction, cu_count, tune, jobs, form=0, ws_bytes=None):
+    """The decision of a multi-scan call as a ScanChoice - no context, no GPU.  direction "fwd" / "bwd"; tune: {key: value}; jobs: what
+    make_scan_jobs / make_scan_bwd_jobs take (pointers may be any aligned non-zero numbers: they are never followed); ws_bytes (forward):
+    the workspace the call would get, None = as much as it takes.  Raises MgrError with the call's own refusal text.
+        print(_capi.describe_scan("fwd", 256, {}, [dict(Z=4096, Up=4096, Y=4096, ldy=500, B=64, T=8, H=500)] * 2).to_dict())"""
+    lib = load_library()
+    t = (i32 * TUNE_COUNT)()
+    for k, v in tune.items():
+        t[int(k)] = int(v)
+    out = ScanChoice()
+    out.struct_size = C.sizeof(ScanChoice)
+    opts = make_launch_opts(form, 0)
+    if direction == "fwd":
+        arr = make_scan_jobs(jobs)
+        rc = lib.mgr_lstm_scan_fwd_describe(cu_count, t, TUNE_COUNT, len(jobs), arr, C.byref(opts), sz(-1).value if ws_bytes is None else ws_bytes,
+                                            C.byref(out))
+    else:
+        arr = make_scan_bwd_jobs(jobs)
+        rc = lib.mgr_lstm_scan_bwd_describe(cu_count, t, TUNE_COUNT, len(jobs), arr, C.byref(opts), C.byref(out))
+    check(rc, lib)
+    return out
 
 
 class SeqFillJob(C.Structure):

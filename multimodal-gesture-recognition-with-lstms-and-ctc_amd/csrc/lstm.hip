@@ -3,6 +3,8 @@
 //             weight-stationary MFMA kernel, one CU per batch group (H <= 128) or clusters of CUs exchanging h_t
 //   backward: H <= 128 -> lstm_mfma.hip (single-CU weight-stationary MFMA)
 //   anything else (H <= 1024) -> lstm_simple.hip (U streamed from L2; correctness fallback)
+// WHAT a call launches is decided once per call, by the pure host functions of scan_choice.h (mgr_scan_fwd_decide / mgr_scan_bwd_decide);
+// the entry points here validate, decide, and carry the choice out.
 #include <algorithm>
 #include <cstddef>
 
@@ -12,175 +14,13 @@
 int mgr_scan_fwd_simple(mgr_ctx*, const float*, const float*, float*, int, const float*, int, float*, float*, int, int, int, int);
 int mgr_scan_bwd_simple(mgr_ctx*, const float*, int, const float*, const float*, const float*, float*, int, int, int, int);
 int mgr_scan_bwd_mfma_multi(mgr_ctx*, int, const mgr_scan_bwd_job*);
-int mgr_scan_bwd_cu16_multi(mgr_ctx*, int, const mgr_scan_bwd_job*);   // lstm_cu_bwd.hip: one CU per (direction, 16-sample group), split-f16
+int mgr_scan_bwd_cu16_multi(mgr_ctx*, int, const mgr_scan_bwd_job*, const mgr_scan_choice&);   // lstm_cu_bwd.hip: one CU per (direction, 16-sample group), split-f16
 
 namespace {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-struct Cfg {
-  int nw, tpw;
-};
-// candidate (active waves, tiles per wave) configurations
-constexpr int NCFG = 4;
-const Cfg kCfgs[NCFG] = {{4, 1}, {8, 1}, {8, 2}, {8, 4}};
-
-struct Plan {
-  bool cluster[MGR_MAX_SCAN_JOBS];
-  Cfg cfg[MGR_MAX_SCAN_JOBS];
-  int G[MGR_MAX_SCAN_JOBS], nbg[MGR_MAX_SCAN_JOBS], wgs[MGR_MAX_SCAN_JOBS];
-  int total;
-  bool any, exchange;
-};
-
-size_t job_ws(const mgr_scan_job& j) {
-  int ks = j.H / 4;
-  size_t img = (size_t)((ks + 7) / 8) * 512;   // 1 KiB per 16 units, in whole K-blocks of 32 (the split-f16 step's image)
-  int nbg = (j.B + 15) / 16;
-  return mgr_align_up((size_t)nbg * 2 * img * sizeof(float), 256);
-}
-
-// Row-major output of a job that gave none (mgr.h: Y == NULL with a YT): a kernel family that does not write the transposed copy
-// itself is followed by a transpose FROM the rows, so its rows go to this scratch, packed [B][T][H].
-size_t job_rows_scratch(const mgr_scan_job& j) {
-  return (!j.Y && j.YT) ? mgr_align_up((size_t)j.B * j.T * j.H * sizeof(float), 256) : 0;
-}
-
-// header + exchange images: what the cluster kernels need whatever the jobs ask for
-size_t base_ws(int njobs, const mgr_scan_job* jobs) {
-  size_t s = kScanHdrBytes;
-  for (int i = 0; i < njobs; ++i) s += job_ws(jobs[i]);
-  return s;
-}
-
-// Choose per-job configurations: minimise the slowest job's per-step MFMA time subject to all workgroups
-// being co-resident (sum <= CUs).  Jobs that cannot run on the cluster kernel are left to the other families.
-void make_plan(const mgr_ctx* c, int njobs, const mgr_scan_job* jobs, Plan& P) {
-  int path = c->tune[MGR_TUNE_SCAN_PATH];
-  P.any = false;
-  P.exchange = false;
-  P.total = 0;
-  int idx[MGR_MAX_SCAN_JOBS], n = 0;
-  for (int i = 0; i < njobs; ++i) {
-    int H = jobs[i].H, ks = H / 4;
-    bool ok = (H % 4 == 0);
-    if (ok) {
-      ok = false;
-      for (int k = 0; k < NCFG; ++k) ok = ok || mgr_cluster_supported(ks, kCfgs[k].tpw);
-    }
-    if (path == 1) ok = false;
-    P.cluster[i] = ok;
-    if (ok) idx[n++] = i;
-  }
-  if (n == 0) return;
-  int best[MGR_MAX_SCAN_JOBS], cur[MGR_MAX_SCAN_JOBS];
-  long best_cost = -1;
-  int combos = 1;
-  for (int k = 0; k < n; ++k) combos *= NCFG;
-  for (int code = 0; code < combos; ++code) {
-    int x = code, total = 0;
-    long worst = 0, sum = 0;
-    bool feas = true, exch = false;
-    for (int k = 0; k < n; ++k) {
-      cur[k] = x % NCFG;
-      x /= NCFG;
-      const mgr_scan_job& j = jobs[idx[k]];
-      Cfg f = kCfgs[cur[k]];
-      int ks = j.H / 4;
-      if (!mgr_cluster_supported(ks, f.tpw)) feas = false;
-      if (path == 3 && cur[k] != 0) feas = false;
-      if (path == 4 && cur[k] != 1) feas = false;
-      if (path == 2 && (f.nw * f.tpw < ks)) feas = false;  // force single-CU (no exchange)
-      int tiles = f.nw * f.tpw;
-      int G = (ks + tiles - 1) / tiles;
-      if (G > 64) feas = false;
-      if (G > 1) exch = true;
-      int nbg = (j.B + 15) / 16;
-      // (classes of jobs are laid out on workgroup ranges rounded up to a multiple of 8 - the XCD count - at launch; count
-      // every job rounded up so that a plan accepted here always passes the launcher's co-residency check)
-      total += (G * nbg + 7) / 8 * 8;
-      // per-step estimate in cycles: MFMA chain per SIMD (+15% issue overhead) + cell update + exchange / barrier
-      int tiles_here = std::min(tiles, ks);
-      int per_simd = (tiles_here + 3) / 4;
-      long t = (long)per_simd * ks * 37 + 700 + (G > 1 ? 3300 : 400);
-      if (total > c->cu_count) t += (long)per_simd * ks * 12;  // a second workgroup on the CU competes for the MFMA pipe part of the time
-      worst = std::max(worst, t);
-      sum += t;
-    }
-    // capacity: one 8-wave workgroup per CU, or two 4-wave workgroups (<= 80 KiB LDS each) per CU
-    bool all4 = true;
-    int maxks = 0;
-    for (int k = 0; k < n; ++k) {
-      if (kCfgs[cur[k]].nw != 4) all4 = false;
-      maxks = std::max(maxks, jobs[idx[k]].H / 4);
-    }
-    size_t lds2 = (size_t)2 * ((maxks + 3) / 4) * 1024;
-    int capacity = (all4 && lds2 <= 80 * 1024) ? 2 * c->cu_count : c->cu_count;
-    if (!feas || (exch && total > capacity)) continue;
-    long cost = worst * 1000 + sum / n;
-    if (best_cost < 0 || cost < best_cost) {
-      best_cost = cost;
-      for (int k = 0; k < n; ++k) best[k] = cur[k];
-    }
-  }
-  if (best_cost < 0) {  // does not fit: leave these jobs to the fallback
-    for (int k = 0; k < n; ++k) P.cluster[idx[k]] = false;
-    return;
-  }
-  for (int k = 0; k < n; ++k) {
-    int i = idx[k];
-    P.cfg[i] = kCfgs[best[k]];
-    int tiles = P.cfg[i].nw * P.cfg[i].tpw;
-    P.G[i] = (jobs[i].H / 4 + tiles - 1) / tiles;
-    P.nbg[i] = (jobs[i].B + 15) / 16;
-    P.wgs[i] = P.G[i] * P.nbg[i];
-    P.total += P.wgs[i];
-    if (P.G[i] > 1) P.exchange = true;
-  }
-  P.any = true;
-}
-
 }  // namespace
-
-// Lay the cluster jobs of one launch out on workgroup ranges: jobs with identical geometry (the two directions of a layer)
-// form a class that shares one contiguous range, every class starts on a multiple of 8 (the XCD round-robin).
-template <class SameFn, class SizeFn>
-static int layout_classes(int njobs, const bool* use, SameFn same, SizeFn G_of, const int* nbg, int* cls_begin_of, int* cls_clusters_of,
-                          int* cls_cluster0_of, bool octets = false, int* cls_rot_of = nullptr) {
-  int cls_of[MGR_MAX_SCAN_JOBS], ncls = 0, cls_first[MGR_MAX_SCAN_JOBS], cls_clusters[MGR_MAX_SCAN_JOBS];
-  for (int i = 0; i < njobs; ++i) {
-    if (!use[i]) continue;
-    int found = -1;
-    for (int k = 0; k < ncls; ++k)
-      if (same(cls_first[k], i)) found = k;
-    if (found < 0) {
-      found = ncls++;
-      cls_first[found] = i;
-      cls_clusters[found] = 0;
-    }
-    cls_of[i] = found;
-    cls_clusters[found] += nbg[i];
-  }
-  int cls_begin[MGR_MAX_SCAN_JOBS], cls_next[MGR_MAX_SCAN_JOBS], cls_rot[MGR_MAX_SCAN_JOBS], begin = 0, lanes = 0;
-  for (int k = 0; k < ncls; ++k) {
-    begin = (begin + 7) / 8 * 8;
-    cls_begin[k] = begin;
-    cls_next[k] = 0;
-    cls_rot[k] = lanes & 7;   // (XCD-local layout) this class's first cluster takes the lane after the previous class's last
-    lanes += cls_clusters[k];
-    begin += G_of(cls_first[k]) * (octets ? (cls_clusters[k] + 7) / 8 * 8 : cls_clusters[k]);
-  }
-  for (int i = 0; i < njobs; ++i) {
-    if (!use[i]) continue;
-    const int k = cls_of[i];
-    cls_begin_of[i] = cls_begin[k];
-    cls_clusters_of[i] = cls_clusters[k];
-    cls_cluster0_of[i] = cls_next[k];
-    if (cls_rot_of) cls_rot_of[i] = octets ? cls_rot[k] : 0;
-    cls_next[k] += nbg[i];
-  }
-  return begin;   // grid size
-}
 
 static int check_launch_status(mgr_ctx* c, unsigned* status, const char* what) {
   unsigned st = 0;   // MGR_TUNE_SCAN_SYNC_CHECK: synchronous give-up check (tests)
@@ -206,18 +46,8 @@ int mgr_tune_get(mgr_ctx* c, int key, int* value) {
   return 0;
 }
 
-static size_t bwd_job_ws(const mgr_scan_bwd_job& j) {
-  int nbg = (j.B + 15) / 16;
-  size_t cluster = mgr_align_up((size_t)nbg * 2 * mgr_cluster_bwd_img_floats(j.H) * sizeof(float), 256);
-  size_t fallback = mgr_align_up((size_t)4 * j.H * j.H * sizeof(float), 256);
-  return std::max(cluster, fallback);
-}
-
-size_t mgr_lstm_scan_bwd_multi_ws_bytes(int njobs, const mgr_scan_bwd_job* jobs) {
-  size_t s = kScanHdrBytes;
-  for (int i = 0; i < njobs; ++i) s += bwd_job_ws(jobs[i]);
-  return s;
-}
+// the workspace queries that need no context: the layout functions of scan_choice.h, which yield offsets only
+size_t mgr_lstm_scan_bwd_multi_ws_bytes(int njobs, const mgr_scan_bwd_job* jobs) { return mgr_scan_bwd_ws_layout(njobs, jobs).bytes; }
 
 size_t mgr_lstm_scan_ws_bytes(int B, int T, int H) {
   (void)T;
@@ -225,21 +55,17 @@ size_t mgr_lstm_scan_ws_bytes(int B, int T, int H) {
   memset(&j, 0, sizeof(j));
   j.B = B;
   j.H = H;
-  size_t fallback = mgr_align_up((size_t)4 * H * H * sizeof(float), 256);  // U^T for the fallback backward kernel
   mgr_scan_bwd_job bj;
   memset(&bj, 0, sizeof(bj));
   bj.B = B;
   bj.H = H;
-  return std::max(std::max(fallback, job_ws(j) + kScanHdrBytes), mgr_lstm_scan_bwd_multi_ws_bytes(1, &bj));
+  // (the backward figure holds U^T for the fallback backward kernel)
+  return std::max(mgr_scan_fwd_ws_layout(1, &j, nullptr, nullptr).bytes, mgr_scan_bwd_ws_layout(1, &bj).bytes);
 }
 
-// (an upper bound that needs no context: row scratch for EVERY job without Y; mgr_lstm_scan_fwd_multi_ws_bytes leaves out the jobs
-// whose kernel writes the transposed copy itself)
-size_t mgr_lstm_scan_multi_ws_bytes(int njobs, const mgr_scan_job* jobs) {
-  size_t s = base_ws(njobs, jobs);
-  for (int i = 0; i < njobs; ++i) s += job_rows_scratch(jobs[i]);
-  return s;
-}
+// (an upper bound: row scratch for EVERY job without Y; mgr_lstm_scan_fwd_multi_ws_bytes leaves out the jobs whose kernel writes the
+// transposed copy itself)
+size_t mgr_lstm_scan_multi_ws_bytes(int njobs, const mgr_scan_job* jobs) { return mgr_scan_fwd_ws_layout(njobs, jobs, nullptr, nullptr).bytes; }
 
 // what a mgr_scan_launch_opts says, read through its own struct_size (members beyond it are zero)
 static void read_opts(const mgr_scan_launch_opts* o, int* form, unsigned** seq_out) {
@@ -263,13 +89,10 @@ int mgr_lstm_scan_fwd_multi(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, voi
   return mgr_lstm_scan_fwd_multi_ex(c, njobs, jobs, ws, ws_bytes, nullptr);
 }
 
-// The forward multi-scan call.  need_out != nullptr: enqueue NOTHING - plan the call as it would run in this context with a workspace
-// that is large enough and report the bytes that plan needs (mgr_lstm_scan_fwd_multi_ws_bytes; ws is not looked at).
-static int scan_fwd_multi(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, void* ws, size_t ws_bytes, const mgr_scan_launch_opts* opts,
-                          size_t* need_out) {
-  const bool query = need_out != nullptr;
-  // (the job list is checked before the context: these checks are what keeps a store through a NULL row pointer off the device, and
-  //  they are plain host code a box without a GPU can run - tests/test_cpu_scan_no_rows.py)
+// The checks of a forward call that are plain host code, shared by the call, its workspace query and mgr_lstm_scan_fwd_describe.
+// (The job list is checked before the context: these checks are what keeps a store through a NULL row pointer off the device, and a
+//  box without a GPU can run them - tests/test_cpu_scan_no_rows.py)
+static int check_fwd_jobs(int njobs, const mgr_scan_job* jobs) {
   MGR_REQUIRE(jobs && njobs > 0 && njobs <= MGR_MAX_SCAN_JOBS, "bad job list");
   for (int i = 0; i < njobs; ++i) {
     const mgr_scan_job& j = jobs[i];
@@ -281,210 +104,114 @@ static int scan_fwd_multi(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, void*
                 "job %d: transposed output needs a 16-byte aligned YT, ldt %% 4 == 0, ldt >= T rounded up to 32, ytb >= H * ldt", i);
     MGR_REQUIRE(!j.YT || !j.yt_split || j.ldt % 8 == 0, "job %d: split rows need ldt %% 8 == 0", i);
   }
+  return 0;
+}
+static int check_fwd_form(int form) {
+  MGR_REQUIRE(form >= MGR_SCAN_FORM_AUTO && form <= MGR_SCAN_FORM_FUSED_ANY, "unknown scan form %d", form);
+  MGR_REQUIRE(form != 2, "scan form 2 (the pair form) is retired");
+  return 0;
+}
+// Rows in scratch were decided, and the workspace is checked against them, BEFORE anything is enqueued: a kernel that stores through a
+// NULL row pointer faults the device.
+static int check_fwd_ws(const mgr_scan_choice& C, size_t ws_avail) {
+  MGR_REQUIRE(C.need == C.base_need || ws_avail >= C.need,
+              "jobs without Y whose kernel does not write YT itself need %zu bytes of workspace for their rows (mgr_lstm_scan_fwd_multi_ws_bytes)",
+              (size_t)C.need);
+  return 0;
+}
+
+// The forward multi-scan call: validate -> decide (scan_choice.h) -> carry the choice out.
+int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, void* ws, size_t ws_bytes,
+                               const mgr_scan_launch_opts* opts) {
+  int r = check_fwd_jobs(njobs, jobs);
+  if (r) return r;
   MGR_REQUIRE(c, "null context");
-  if (query) ws = nullptr;
-  if (!query) mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
+  mgr_planes_forget_range(c, ws, ws_bytes);   // (this call writes its workspace: kept weight planes in it are gone)
   int form;
   unsigned* seq_out;
   read_opts(opts, &form, &seq_out);
-  MGR_REQUIRE(form >= MGR_SCAN_FORM_AUTO && form <= MGR_SCAN_FORM_FUSED_ANY, "unknown scan form %d", form);
-  MGR_REQUIRE(form != 2, "scan form 2 (the pair form) is retired");
-  if (seq_out && !query) *seq_out = MGR_SEQ_NONE;   // (until a launch of this call enters the residency ledger)
-  // the form of the split-f16 K-split launches: the caller's, or MGR_TUNE_SCAN_FORM (3 fused, anything else plain)
-  const bool want_fused = form == MGR_SCAN_FORM_AUTO ? c->tune[MGR_TUNE_SCAN_FORM] == MGR_SCAN_FORM_FUSED : form >= MGR_SCAN_FORM_FUSED;
-  const bool fused_any = form == MGR_SCAN_FORM_FUSED_ANY;
+  r = check_fwd_form(form);
+  if (r) return r;
+  if (seq_out) *seq_out = MGR_SEQ_NONE;   // (until a launch of this call enters the residency ledger)
   int hmax = 0;
   for (int i = 0; i < njobs; ++i) hmax = jobs[i].H > hmax ? jobs[i].H : hmax;
   const int family = hmax > 128 ? MGR_K_SCAN_FWD : MGR_K_SCAN_FWD_NARROW;
-  int r = query ? 0 : mgr_prof_begin(c, family);
+  r = mgr_prof_begin(c, family);
   if (r) return r;
-  Plan P;
-  make_plan(c, njobs, jobs, P);
-  const size_t base_need = base_ws(njobs, jobs);
-  if (!query && P.any && (!ws || ws_bytes < base_need)) {
-    // no workspace for the exchange: degrade to the non-cluster families
-    for (int i = 0; i < njobs; ++i) P.cluster[i] = false;
-    P.any = false;
-  }
+  const size_t ws_avail = ws ? ws_bytes : 0;
+  const mgr_scan_choice C = mgr_scan_fwd_decide(c->cu_count, c->tune, njobs, jobs, form, ws_avail);
+  r = check_fwd_ws(C, ws_avail);
+  if (r) return r;
+  char* base = reinterpret_cast<char*>(ws);
   unsigned* status = nullptr;
-  bool yt_done[MGR_MAX_SCAN_JOBS] = {};
-  // Where each job's rows go: its Y - or, for a job that gave none and whose kernel does not write the transposed copy itself (the
-  // transpose behind the scans reads rows), scratch behind the exchange images, packed [B][T][H].  Decided, and the workspace checked
-  // against it, BEFORE anything is enqueued: a kernel that stores through a NULL row pointer faults the device.
-  float* rows[MGR_MAX_SCAN_JOBS];
+  float* rows[MGR_MAX_SCAN_JOBS];   // where each job's rows go: its Y, or scratch (a K-split job without Y keeps its NULL)
   int ldrows[MGR_MAX_SCAN_JOBS];
-  size_t need = base_need;
-  auto place_rows = [&]() -> int {
-    for (int i = 0; i < njobs; ++i) {
-      const mgr_scan_job& j = jobs[i];
-      rows[i] = j.Y;
-      ldrows[i] = j.ldy;
-      if (j.Y || yt_done[i]) continue;
-      rows[i] = ws ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + need) : nullptr;
-      ldrows[i] = j.H;
-      need += job_rows_scratch(j);
-    }
-    if (query) return 0;
-    MGR_REQUIRE(need == base_need || (ws && ws_bytes >= need),
-                "jobs without Y whose kernel does not write YT itself need %zu bytes of workspace for their rows (mgr_lstm_scan_fwd_multi_ws_bytes)",
-                need);
-    return 0;
-  };
-  if (P.any) {
+  for (int i = 0; i < njobs; ++i) {
+    const bool scratch = C.job[i].rows_in_scratch;
+    rows[i] = scratch ? reinterpret_cast<float*>(base + C.job[i].rows_off) : jobs[i].Y;
+    ldrows[i] = scratch ? jobs[i].H : jobs[i].ldy;
+  }
+  if (C.kernel != MGR_SCAN_FWD_NONE) {
     ClusterLaunch L;
     memset(&L, 0, sizeof(L));
-    char* base = reinterpret_cast<char*>(ws);
     status = reinterpret_cast<unsigned*>(base);
-    size_t off = kScanHdrBytes;
-    // K-split launches (every job a 4-wave, one-tile-per-wave cluster with an exchange) lay their clusters out XCD-locally
-    // (MGR_TUNE_SCAN_NO_XCD_LOCAL = 1 turns that off); the table of workgroup XCD ids lives in the launch header
-    // the K-split step addresses Z and the residual input with 32-bit byte offsets per lane (LDS-DMA prefetch): launches with a
-    // larger tensor take the LDS-image step
-    bool ks_ok = c->tune[MGR_TUNE_SCAN_LDS_IMAGE] == 0;
-    for (int i = 0; i < njobs && ks_ok; ++i) {
-      if (!P.cluster[i]) continue;
-      const mgr_scan_job& j = jobs[i];
-      const size_t zb = (size_t)j.B * j.T * 4 * j.H * sizeof(float), rb = j.R ? (size_t)j.B * j.T * j.ldr * sizeof(float) : 0;
-      ks_ok = zb < ((size_t)1 << 32) && rb < ((size_t)1 << 32);
-    }
-    // Fused form (lstm_cluster.hip, k_scan_cluster_k16fs): 8-wave workgroups that run TWO unit groups of their cluster, one workgroup
-    // per CU (config F's encoder depths: 208 workgroups on 208 CUs, 48 CUs left to the other stream).
-    bool fused = ks_ok && P.exchange && c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0 && want_fused && c->tune[MGR_TUNE_SCAN_NO_XCD_LOCAL] == 0;
-    for (int i = 0; i < njobs && fused; ++i) {
-      if (!P.cluster[i]) continue;
-      fused = P.cfg[i].nw == 4 && P.cfg[i].tpw == 1 && P.G[i] > 1 && mgr_cluster_ks_supported(jobs[i].H / 4);
-    }
-    {   // (only launches that do not fit one workgroup per CU as they are: the fusion layer's 56 workgroups stay what they are)
-      int unf = 0;
-      for (int i = 0; i < njobs; ++i)
-        if (P.cluster[i]) unf += P.G[i] * P.nbg[i];
-      fused = fused && (fused_any || unf > c->cu_count);
-    }
-    auto members = [&](int i) { return fused ? (P.G[i] + 1) / 2 : P.G[i]; };   // workgroups per cluster
-    bool xcd = c->tune[MGR_TUNE_SCAN_NO_XCD_LOCAL] == 0 && ks_ok && P.exchange;
-    {
-      int tot = 0, live_x = 0;
-      for (int i = 0; i < njobs && xcd; ++i) {
-        if (!P.cluster[i]) continue;
-        xcd = P.cfg[i].nw == 4 && P.cfg[i].tpw == 1 && P.G[i] > 1 && mgr_cluster_ks_supported(jobs[i].H / 4);
-      }
-      // (octets of clusters: the grid may grow; it must still fit the chip and the header's table)
-      if (xcd) {
-        int h[MGR_MAX_SCAN_JOBS], n = 0;
-        for (int i = 0; i < njobs; ++i) {
-          if (!P.cluster[i]) continue;
-          bool seen = false;
-          for (int k = 0; k < n; ++k) seen = seen || h[k] == jobs[i].H;
-          if (seen) continue;
-          h[n++] = jobs[i].H;
-          int clusters = 0;
-          for (int k = i; k < njobs; ++k)
-            if (P.cluster[k] && jobs[k].H == jobs[i].H) clusters += P.nbg[k];
-          tot += members(i) * ((clusters + 7) / 8 * 8);
-          live_x += members(i) * clusters;
-        }
-        xcd = live_x <= (fused ? 1 : 2) * c->cu_count && tot <= 2 * c->cu_count && (size_t)tot * sizeof(unsigned) <= kScanHdrBytes - 256;
-      }
-    }
-    int cb[MGR_MAX_SCAN_JOBS], cn[MGR_MAX_SCAN_JOBS], c0[MGR_MAX_SCAN_JOBS], cr[MGR_MAX_SCAN_JOBS];
-    // workgroups that really run (a class laid out in octets of clusters has empty ids when its cluster count is no multiple of 8:
-    // those workgroups count themselves in and return): what co-residency and the admission ledger are about
-    fused = fused && xcd;   // (the fused kernel understands the octet layout only)
-    int live = 0;
-    for (int i = 0; i < njobs; ++i)
-      if (P.cluster[i]) live += members(i) * P.nbg[i];
-    P.total = layout_classes(
-        njobs, P.cluster,
-        [&](int a, int b) { return jobs[a].H == jobs[b].H && P.cfg[a].nw == P.cfg[b].nw && P.cfg[a].tpw == P.cfg[b].tpw; },
-        [&](int a) { return members(a); }, P.nbg, cb, cn, c0, xcd, cr);
-    L.xcd_local = xcd;
+    const bool writes_yt = C.kernel != MGR_SCAN_FWD_IMAGE;   // (the K-split kernels honour ClusterJob::YT)
     for (int i = 0; i < njobs; ++i) {
-      if (!P.cluster[i]) continue;
+      const mgr_scan_choice_job& q = C.job[i];
+      if (!q.cluster) continue;
       const mgr_scan_job& j = jobs[i];
       ClusterJob& cj = L.job[L.njobs++];
-      int ks = j.H / 4;
-      size_t img = (size_t)((ks + 7) / 8) * 512;   // (job_ws)
-      cj.Z = j.Z; cj.Up = j.Up; cj.Y = j.Y; cj.R = j.R; cj.G = j.gates; cj.Cs = j.cs;
-      cj.ldy = j.ldy; cj.ldr = j.ldr; cj.B = j.B; cj.T = j.T; cj.H = j.H; cj.reverse = j.reverse;
-      cj.ks = ks; cj.tpw = P.cfg[i].tpw; cj.nw = P.cfg[i].nw;
-      cj.G_ = P.G[i]; cj.nbg = P.nbg[i];
-      cj.cls_begin = cb[i]; cj.cls_nclusters = cn[i]; cj.cls_cluster0 = c0[i]; cj.cls_rot = cr[i];
-      cj.xbuf = base ? reinterpret_cast<float*>(base + off) : nullptr;
-      off += mgr_align_up((size_t)P.nbg[i] * 2 * img * sizeof(float), 256);
-    }
-    L.fused = fused ? 1 : 0;
-    L.live_wgs = live;
-    L.ksplit = ks_ok ? 1 : 0;
-    L.split16 = c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0;
-    // transposed outputs: the K-split kernel writes them itself; everything else gets a transpose behind the scans (below)
-    if (mgr_cluster_uses_ks(L, P.exchange)) {
-      int k = 0;
-      for (int i = 0; i < njobs; ++i) {
-        if (!P.cluster[i]) continue;
-        ClusterJob& cj = L.job[k++];
-        cj.YT = jobs[i].YT; cj.ytb = jobs[i].ytb; cj.ldt = jobs[i].ldt; cj.yt_split = jobs[i].yt_split;
-        yt_done[i] = jobs[i].YT != nullptr;
+      cj.Z = j.Z; cj.Up = j.Up; cj.Y = rows[i]; cj.R = j.R; cj.G = j.gates; cj.Cs = j.cs;
+      cj.ldy = ldrows[i]; cj.ldr = j.ldr; cj.B = j.B; cj.T = j.T; cj.H = j.H; cj.reverse = j.reverse;
+      cj.ks = j.H / 4; cj.tpw = q.tpw; cj.nw = q.nw;
+      cj.G_ = q.G; cj.nbg = q.nbg;
+      cj.cls_begin = q.cls_begin; cj.cls_nclusters = q.cls_nclusters; cj.cls_cluster0 = q.cls_cluster0; cj.cls_rot = q.cls_rot;
+      cj.xbuf = reinterpret_cast<float*>(base + q.xbuf_off);
+      if (writes_yt) {
+        cj.YT = j.YT; cj.ytb = j.ytb; cj.ldt = j.ldt; cj.yt_split = j.yt_split;
       }
+      MGR_REQUIRE(cj.Y || (q.yt_in_kernel && cj.YT), "job %d: no rows to write to", i);
     }
-    r = place_rows();
-    if (r) return r;
-    if (query) {
-      *need_out = need;
-      return 0;
-    }
-    {   // (a K-split job without Y keeps its NULL: the kernel skips the row store; every other kernel stores through the pointer)
-      int k = 0;
-      for (int i = 0; i < njobs; ++i) {
-        if (!P.cluster[i]) continue;
-        ClusterJob& cj = L.job[k++];
-        cj.Y = rows[i];
-        cj.ldy = ldrows[i];
-        MGR_REQUIRE(cj.Y || (yt_done[i] && cj.YT), "job %d: no rows to write to", i);
-      }
-    }
+    L.xcd_local = C.xcd_local;
+    L.fused = C.fused;
+    L.live_wgs = C.live;
+    L.ksplit = C.ksplit;
+    L.split16 = C.split16;
     if (c->tune[MGR_TUNE_SCAN_PRINT_PLAN]) {
       for (int i = 0; i < L.njobs; ++i)
         fprintf(stderr, "[mgr scan plan] job %d: H=%d ks=%d nw=%d tpw=%d G=%d nbg=%d wg_begin=%d\n", i, L.job[i].H,
                 L.job[i].ks, L.job[i].nw, L.job[i].tpw, L.job[i].G_, L.job[i].nbg, L.job[i].cls_begin);
-      fprintf(stderr, "[mgr scan plan] total %d workgroups, exchange=%d\n", P.total, (int)P.exchange);
+      fprintf(stderr, "[mgr scan plan] total %d workgroups, exchange=%d\n", C.grid, C.exchange);
     }
-    int waves, per_cu;
-    mgr_cluster_geometry(L, P.exchange, &waves, &per_cu);
     L.cm.status = status;
     L.cm.sticky = mgr_status_block(c);
     L.cm.resident = c->sticky_status + 1;
-    L.cm.total_wgs = P.total;
-    // (a launch without an exchange spins on nobody: it needs no place in the ledger and is never ordered behind one)
-    if (P.exchange) {
-      r = mgr_persist_admit(c, live, waves, per_cu, L.fused, &L.cm.seq);
+    L.cm.total_wgs = C.grid;
+    // The ledger counts the forward launch by its LIVE workgroups (the octet layout leaves empty ids that count themselves in and
+    // return), the BPTT launch by its grid (mgr_lstm_scan_bwd_multi_ex): an asymmetry as old as the two layouts, kept as it is.
+    if (C.ledger) {
+      r = mgr_persist_admit(c, C.live, C.waves, C.per_cu, C.fused, &L.cm.seq);
       if (r) return r;
       if (seq_out) *seq_out = L.cm.seq;
     }
     // exchange slots + status must be zero at every launch (epochs count from 1 within the call)
-    MGR_HIP(hipMemsetAsync(base, 0, off, mgr_stream(c)));
-    r = mgr_cluster_launch(c, L, P.total, P.exchange);
+    MGR_HIP(hipMemsetAsync(base, 0, C.zero_bytes, mgr_stream(c)));
+    r = mgr_cluster_launch(c, L, C);
     if (r) return r;
-    if (P.exchange) {
-      r = mgr_persist_commit(c, live, waves, per_cu, L.fused);
+    if (C.ledger) {
+      r = mgr_persist_commit(c, C.live, C.waves, C.per_cu, C.fused);
       if (r) return r;
-    }
-  } else {
-    r = place_rows();
-    if (r) return r;
-    if (query) {
-      *need_out = need;
-      return 0;
     }
   }
   for (int i = 0; i < njobs; ++i) {
-    if (P.cluster[i]) continue;
+    if (C.job[i].cluster) continue;
     const mgr_scan_job& j = jobs[i];
     r = mgr_scan_fwd_simple(c, j.Z, j.Up, rows[i], ldrows[i], j.R, j.ldr, j.gates, j.cs, j.B, j.T, j.H, j.reverse);
     if (r < 0) return r;
   }
   for (int i = 0; i < njobs; ++i) {   // transposed outputs the scan kernel did not write itself
     const mgr_scan_job& j = jobs[i];
-    if (!j.YT || yt_done[i]) continue;
+    if (!j.YT || C.job[i].yt_in_kernel) continue;
     r = j.yt_split ? mgr_transpose_bt_split_strided(c, rows[i], ldrows[i], j.YT, j.ldt, j.ytb, j.ldt, j.B, j.T, j.H)
                    : mgr_transpose_bt_strided(c, rows[i], ldrows[i], j.YT, j.ldt, j.ytb, j.ldt, j.B, j.T, j.H);
     if (r) return r;
@@ -495,14 +222,36 @@ static int scan_fwd_multi(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, void*
   return 0;
 }
 
-int mgr_lstm_scan_fwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, void* ws, size_t ws_bytes,
-                               const mgr_scan_launch_opts* opts) {
-  return scan_fwd_multi(c, njobs, jobs, ws, ws_bytes, opts, nullptr);
+// (0: a bad job list, no context or an unknown form - mgr_last_error)
+size_t mgr_lstm_scan_fwd_multi_ws_bytes(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, const mgr_scan_launch_opts* opts) {
+  if (check_fwd_jobs(njobs, jobs) != 0) return 0;
+  if (!c) {
+    mgr_fail(-1, "null context");
+    return 0;
+  }
+  mgr_scan_choice C;
+  C.struct_size = (unsigned)sizeof(C);
+  return mgr_lstm_scan_fwd_describe(c->cu_count, c->tune, MGR_TUNE_COUNT, njobs, jobs, opts, (size_t)-1, &C) == 0 ? (size_t)C.need : 0;
 }
 
-size_t mgr_lstm_scan_fwd_multi_ws_bytes(mgr_ctx* c, int njobs, const mgr_scan_job* jobs, const mgr_scan_launch_opts* opts) {
-  size_t need = 0;
-  return scan_fwd_multi(c, njobs, jobs, nullptr, 0, opts, &need) == 0 ? need : 0;
+// tune keys of a describe call: tune[0 .. ntune), the rest 0
+static void read_tune(const int* tune, int ntune, int* out) {
+  for (int k = 0; k < MGR_TUNE_COUNT; ++k) out[k] = tune && k < ntune ? tune[k] : 0;
+}
+
+int mgr_lstm_scan_fwd_describe(int cu_count, const int* tune, int ntune, int njobs, const mgr_scan_job* jobs, const mgr_scan_launch_opts* opts,
+                               size_t ws_bytes, mgr_scan_choice* out) {
+  int r = check_fwd_jobs(njobs, jobs);
+  if (r) return r;
+  MGR_REQUIRE(out && out->struct_size == sizeof(*out) && cu_count > 0, "describe: out->struct_size must be sizeof(mgr_scan_choice), cu_count > 0");
+  int form, t[MGR_TUNE_COUNT];
+  unsigned* seq_out;
+  read_opts(opts, &form, &seq_out);
+  r = check_fwd_form(form);
+  if (r) return r;
+  read_tune(tune, ntune, t);
+  *out = mgr_scan_fwd_decide(cu_count, t, njobs, jobs, form, ws_bytes);
+  return check_fwd_ws(*out, ws_bytes);
 }
 
 int mgr_lstm_scan_fwd(mgr_ctx* c, const float* Z, const float* Up, float* Y, int ldy, const float* R, int ldr,
@@ -518,6 +267,21 @@ int mgr_lstm_scan_bwd_multi(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jobs,
   return mgr_lstm_scan_bwd_multi_ex(c, njobs, jobs, ws, ws_bytes, nullptr);
 }
 
+static int check_bwd_form(int form) {
+  MGR_REQUIRE(form >= MGR_BPTT_FORM_AUTO && form <= MGR_BPTT_FORM_SINGLE_CU, "unknown BPTT form %d", form);
+  return 0;
+}
+static int check_bwd_jobs(int njobs, const mgr_scan_bwd_job* jobs) {
+  for (int i = 0; i < njobs; ++i) {
+    const mgr_scan_bwd_job& j = jobs[i];
+    MGR_REQUIRE(j.dY && j.gates && j.cs && j.Up && j.dZ, "job %d: null argument", i);
+    MGR_REQUIRE(j.B > 0 && j.T > 0 && j.H > 0 && j.lddy >= j.H, "job %d: bad shape", i);
+    MGR_REQUIRE(aligned16(j.gates) && aligned16(j.Up) && aligned16(j.dZ), "job %d: gates/Up/dZ must be 16-byte aligned", i);
+  }
+  return 0;
+}
+
+// The BPTT multi-scan call: validate -> decide (scan_choice.h) -> carry the choice out.
 int mgr_lstm_scan_bwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jobs, void* ws, size_t ws_bytes,
                                const mgr_scan_launch_opts* opts) {
   MGR_REQUIRE(c && jobs && njobs > 0 && njobs <= MGR_MAX_SCAN_JOBS, "bad job list");
@@ -525,142 +289,67 @@ int mgr_lstm_scan_bwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jo
   int form;
   unsigned* seq_out;
   read_opts(opts, &form, &seq_out);
-  MGR_REQUIRE(form >= MGR_BPTT_FORM_AUTO && form <= MGR_BPTT_FORM_SINGLE_CU, "unknown BPTT form %d", form);
-  if (seq_out) *seq_out = MGR_SEQ_NONE;
-  const bool want_fused = form == MGR_BPTT_FORM_FUSED || form == MGR_BPTT_FORM_FUSED_DIRECT;
-  // 0 trimmed, 1 yielding, 2 direct gather (the fused forms: the trimmed step / the direct gather)
-  const int key16 = form == MGR_BPTT_FORM_AUTO ? c->tune[MGR_TUNE_BPTT_FORM]
-                    : (form == MGR_BPTT_FORM_FUSED || form == MGR_BPTT_FORM_SINGLE_CU) ? 0 : form == MGR_BPTT_FORM_FUSED_DIRECT ? 2 : form - 1;
-  MGR_REQUIRE(ws && ws_bytes >= mgr_lstm_scan_bwd_multi_ws_bytes(njobs, jobs), "workspace too small");
-  for (int i = 0; i < njobs; ++i) {
-    const mgr_scan_bwd_job& j = jobs[i];
-    MGR_REQUIRE(j.dY && j.gates && j.cs && j.Up && j.dZ, "job %d: null argument", i);
-    MGR_REQUIRE(j.B > 0 && j.T > 0 && j.H > 0 && j.lddy >= j.H, "job %d: bad shape", i);
-    MGR_REQUIRE(aligned16(j.gates) && aligned16(j.Up) && aligned16(j.dZ), "job %d: gates/Up/dZ must be 16-byte aligned", i);
-  }
-  int r = mgr_prof_begin(c, MGR_K_SCAN_BWD);
+  int r = check_bwd_form(form);
   if (r) return r;
-  const int path = c->tune[MGR_TUNE_SCAN_PATH];
-  // The single-CU split-f16 form (lstm_cu_bwd.hip): asked for by the caller (or MGR_TUNE_BPTT_SINGLE_CU = 1), taken when the jobs are
-  // the directions of ONE narrow layer (same shape, 16 < H <= 128) and the f16 matrix pipe is in use; no inter-CU exchange, no ledger
-  // entry
-  if ((form == MGR_BPTT_FORM_SINGLE_CU || (form == MGR_BPTT_FORM_AUTO && c->tune[MGR_TUNE_BPTT_SINGLE_CU] == 1)) &&
-      c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0 && (path == 0 || path == 3)) {
-    r = mgr_scan_bwd_cu16_multi(c, njobs, jobs);
-    if (r < 0) return r;
-    if (r == 1) {
-      for (int i = 0; i < njobs; ++i) {   // (the row maxima of dZ: a reduction pass, as behind every kernel that does not keep them itself)
-        const mgr_scan_bwd_job& j = jobs[i];
-        if (!j.dzmax && !j.dbsum) continue;
-        r = mgr_rowmax_bt(c, j.dZ, 4 * j.H, j.T, j.B, j.dzmax, j.dbsum);
-        if (r) return r;
-      }
-      return mgr_prof_end(c, MGR_K_SCAN_BWD);
+  if (seq_out) *seq_out = MGR_SEQ_NONE;
+  MGR_REQUIRE(ws && ws_bytes >= mgr_lstm_scan_bwd_multi_ws_bytes(njobs, jobs), "workspace too small");
+  r = check_bwd_jobs(njobs, jobs);
+  if (r) return r;
+  r = mgr_prof_begin(c, MGR_K_SCAN_BWD);
+  if (r) return r;
+  const mgr_scan_choice C = mgr_scan_bwd_decide(c->cu_count, c->tune, njobs, jobs, form);
+  char* base = reinterpret_cast<char*>(ws);
+  unsigned* status = reinterpret_cast<unsigned*>(base);
+  if (C.single_cu) {
+    r = mgr_scan_bwd_cu16_multi(c, njobs, jobs, C);
+    if (r) return r;
+  }
+  if (C.kernel != MGR_SCAN_BWD_NONE) {
+    ClusterBwdLaunch L;
+    memset(&L, 0, sizeof(L));
+    L.xcd_local = C.xcd_local;
+    L.fused = C.fused;
+    for (int i = 0; i < njobs; ++i) {
+      const mgr_scan_choice_job& q = C.job[i];
+      if (!q.cluster) continue;
+      const mgr_scan_bwd_job& j = jobs[i];
+      ClusterBwdJob& cj = L.job[L.njobs++];
+      cj.dY = j.dY; cj.gates = j.gates; cj.cs = j.cs; cj.Up = j.Up; cj.dZ = j.dZ; cj.dzmax = j.dzmax; cj.dbsum = j.dbsum;
+      cj.lddy = j.lddy; cj.B = j.B; cj.T = j.T; cj.H = j.H; cj.reverse = j.reverse;
+      cj.G_ = q.G; cj.nbg = q.nbg;
+      cj.cls_begin = q.cls_begin; cj.cls_nclusters = q.cls_nclusters; cj.cls_cluster0 = q.cls_cluster0; cj.cls_rot = q.cls_rot;
+      cj.xbuf = reinterpret_cast<float*>(base + q.xbuf_off);
     }
-  }
-  char* w = reinterpret_cast<char*>(ws);
-  char* base = w;
-  unsigned* status = reinterpret_cast<unsigned*>(w);
-  w += kScanHdrBytes;
-  ClusterBwdLaunch L;
-  memset(&L, 0, sizeof(L));
-  int total = 0, nbg[MGR_MAX_SCAN_JOBS];
-  bool use_cluster[MGR_MAX_SCAN_JOBS];
-  // cluster kernel when instantiated and the whole launch is co-resident (two 4-wave workgroups per CU)
-  for (int i = 0; i < njobs; ++i) {
-    const mgr_scan_bwd_job& j = jobs[i];
-    nbg[i] = (j.B + 15) / 16;
-    // (the cluster kernel addresses the saved state with 32-bit byte offsets per lane: LDS-DMA prefetch)
-    const bool small = (size_t)j.B * j.T * j.H * 16 < ((size_t)1 << 32) && (size_t)j.B * j.T * j.lddy * 4 < ((size_t)1 << 32);
-    use_cluster[i] = (path == 0 || path == 3) && mgr_cluster_bwd_supported(j.H) && small;
-    if (use_cluster[i]) total += ((j.H + 15) / 16) * nbg[i];
-  }
-  if (total + 8 * njobs > 2 * c->cu_count)
-    for (int i = 0; i < njobs; ++i) use_cluster[i] = false;
-  char* wj[MGR_MAX_SCAN_JOBS];
-  for (int i = 0; i < njobs; ++i) {
-    wj[i] = w;
-    w += bwd_job_ws(jobs[i]);
-  }
-  int cb[MGR_MAX_SCAN_JOBS], cn[MGR_MAX_SCAN_JOBS], c0[MGR_MAX_SCAN_JOBS], cr[MGR_MAX_SCAN_JOBS];
-  auto same_h = [&](int a, int b) { return jobs[a].H == jobs[b].H; };
-  auto g_of = [&](int a) { return (jobs[a].H + 15) / 16; };
-  // XCD-local layout (octets of clusters) where the padded grid still fits the chip and the header's table
-  // (MGR_TUNE_SCAN_NO_XCD_LOCAL = 1: off)
-  bool xcd = c->tune[MGR_TUNE_SCAN_NO_XCD_LOCAL] == 0;
-  int grid = layout_classes(njobs, use_cluster, same_h, g_of, nbg, cb, cn, c0, xcd, cr);
-  if (xcd && (grid > 2 * c->cu_count || (size_t)grid * sizeof(unsigned) > kScanHdrBytes - 256)) {
-    xcd = false;
-    grid = layout_classes(njobs, use_cluster, same_h, g_of, nbg, cb, cn, c0, false, cr);
-  }
-  // Fused form (lstm_cluster_bwd.hip, k_scan_cluster_bwd16_f): asked for by the caller, taken when every job of the launch qualifies -
-  // the same clusters with ceil(G / 2) eight-wave members, a CU each
-  bool fused = want_fused && xcd;
-  for (int i = 0; i < njobs && fused; ++i)
-    fused = use_cluster[i] && jobs[i].H > 16 && jobs[i].H <= 128 && c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0;
-  if (fused) {
-    auto gr_of = [&](int a) { return (g_of(a) + 1) / 2; };
-    const int gridf = layout_classes(njobs, use_cluster, same_h, gr_of, nbg, cb, cn, c0, true, cr);
-    if (gridf <= c->cu_count && (size_t)gridf * sizeof(unsigned) <= kScanHdrBytes - 256)
-      grid = gridf;
-    else {
-      fused = false;
-      grid = layout_classes(njobs, use_cluster, same_h, g_of, nbg, cb, cn, c0, true, cr);
-    }
-  }
-  L.xcd_local = xcd;
-  L.fused = fused ? 1 : 0;
-  for (int i = 0; i < njobs; ++i) {
-    if (!use_cluster[i]) continue;
-    const mgr_scan_bwd_job& j = jobs[i];
-    ClusterBwdJob& cj = L.job[L.njobs++];
-    cj.dY = j.dY; cj.gates = j.gates; cj.cs = j.cs; cj.Up = j.Up; cj.dZ = j.dZ; cj.dzmax = j.dzmax; cj.dbsum = j.dbsum;
-    cj.lddy = j.lddy; cj.B = j.B; cj.T = j.T; cj.H = j.H; cj.reverse = j.reverse;
-    cj.G_ = (j.H + 15) / 16; cj.nbg = nbg[i];
-    cj.cls_begin = cb[i]; cj.cls_nclusters = cn[i]; cj.cls_cluster0 = c0[i]; cj.cls_rot = cr[i];
-    cj.xbuf = reinterpret_cast<float*>(wj[i]);
-  }
-  if (L.njobs > 0) {
-    int waves, per_cu;
-    mgr_cluster_bwd_geometry(c, L, grid, &waves, &per_cu);
     L.cm.status = status;
     L.cm.sticky = mgr_status_block(c);
     L.cm.resident = c->sticky_status + 1;
-    L.cm.total_wgs = grid;
-    r = mgr_persist_admit(c, grid, waves, per_cu, L.fused, &L.cm.seq);
+    L.cm.total_wgs = C.grid;
+    // (the ledger counts this launch by its GRID, the forward launch by its live workgroups: mgr_lstm_scan_fwd_multi_ex)
+    r = mgr_persist_admit(c, C.grid, C.waves, C.per_cu, C.fused, &L.cm.seq);
     if (r) return r;
     if (seq_out) *seq_out = L.cm.seq;
-    MGR_HIP(hipMemsetAsync(base, 0, (size_t)(w - base), mgr_stream(c)));
-    r = mgr_cluster_bwd_launch(c, L, grid, key16);
+    MGR_HIP(hipMemsetAsync(base, 0, C.zero_bytes, mgr_stream(c)));
+    r = mgr_cluster_bwd_launch(c, L, C);
     if (r) return r;
-    r = mgr_persist_commit(c, grid, waves, per_cu, L.fused);
+    r = mgr_persist_commit(c, C.grid, C.waves, C.per_cu, C.fused);
     if (r) return r;
   }
-  // the single-CU kernel takes every job that is left in ONE launch when they share a shape (the two directions of a layer)
-  bool mfma_done = false;
-  {
-    int rest = 0;
-    bool same = true;
-    mgr_scan_bwd_job left[MGR_MAX_SCAN_JOBS];
-    for (int i = 0; i < njobs; ++i) {
-      if (use_cluster[i]) continue;
-      left[rest] = jobs[i];
-      same = same && jobs[i].B == left[0].B && jobs[i].T == left[0].T && jobs[i].H == left[0].H && jobs[i].lddy == left[0].lddy;
-      ++rest;
-    }
-    if (rest > 0 && same && path != 1) {
-      r = mgr_scan_bwd_mfma_multi(c, rest, left);
-      if (r < 0) return r;
-      mfma_done = r == 1;
-    }
+  // the jobs that are left: the single-CU MFMA kernel - ONE launch for all of them when they share a shape - or the simple kernel
+  mgr_scan_bwd_job joint[MGR_MAX_SCAN_JOBS];
+  int njoint = 0;
+  for (int i = 0; i < njobs; ++i)
+    if (C.job[i].fallback == MGR_SCAN_FALLBACK_MFMA_JOINT) joint[njoint++] = jobs[i];
+  if (njoint > 0) {
+    r = mgr_scan_bwd_mfma_multi(c, njoint, joint);
+    if (r < 0) return r;
   }
   for (int i = 0; i < njobs; ++i) {
-    if (use_cluster[i] || mfma_done) continue;
     const mgr_scan_bwd_job& j = jobs[i];
     r = 0;
-    if (path != 1) r = mgr_scan_bwd_mfma_multi(c, 1, &j);
-    if (r == 0) {
-      float* UpT = reinterpret_cast<float*>(wj[i]);
+    if (C.job[i].fallback == MGR_SCAN_FALLBACK_MFMA) {
+      r = mgr_scan_bwd_mfma_multi(c, 1, &j);
+    } else if (C.job[i].fallback == MGR_SCAN_FALLBACK_SIMPLE) {
+      float* UpT = reinterpret_cast<float*>(base + C.job[i].xbuf_off);
       r = mgr_transpose(c, j.Up, UpT, j.H, 4 * j.H);
       if (r) return r;
       r = mgr_scan_bwd_simple(c, j.dY, j.lddy, j.gates, j.cs, UpT, j.dZ, j.B, j.T, j.H, j.reverse);
@@ -669,13 +358,29 @@ int mgr_lstm_scan_bwd_multi_ex(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jo
   }
   for (int i = 0; i < njobs; ++i) {   // the row maxima / sums of dZ where the kernel that ran did not leave them itself
     const mgr_scan_bwd_job& j = jobs[i];
-    if ((!j.dzmax && !j.dbsum) || use_cluster[i]) continue;
+    if ((!j.dzmax && !j.dbsum) || C.job[i].cluster) continue;
     r = mgr_rowmax_bt(c, j.dZ, 4 * j.H, j.T, j.B, j.dzmax, j.dbsum);
     if (r) return r;
   }
   r = mgr_prof_end(c, MGR_K_SCAN_BWD);
   if (r) return r;
-  if (L.njobs > 0 && c->tune[MGR_TUNE_SCAN_SYNC_CHECK]) return check_launch_status(c, status, "cluster BPTT");
+  if (C.kernel != MGR_SCAN_BWD_NONE && c->tune[MGR_TUNE_SCAN_SYNC_CHECK]) return check_launch_status(c, status, "cluster BPTT");
+  return 0;
+}
+
+int mgr_lstm_scan_bwd_describe(int cu_count, const int* tune, int ntune, int njobs, const mgr_scan_bwd_job* jobs, const mgr_scan_launch_opts* opts,
+                               mgr_scan_choice* out) {
+  MGR_REQUIRE(jobs && njobs > 0 && njobs <= MGR_MAX_SCAN_JOBS, "bad job list");
+  MGR_REQUIRE(out && out->struct_size == sizeof(*out) && cu_count > 0, "describe: out->struct_size must be sizeof(mgr_scan_choice), cu_count > 0");
+  int form, t[MGR_TUNE_COUNT];
+  unsigned* seq_out;
+  read_opts(opts, &form, &seq_out);
+  int r = check_bwd_form(form);
+  if (r) return r;
+  r = check_bwd_jobs(njobs, jobs);
+  if (r) return r;
+  read_tune(tune, ntune, t);
+  *out = mgr_scan_bwd_decide(cu_count, t, njobs, jobs, form);
   return 0;
 }
 

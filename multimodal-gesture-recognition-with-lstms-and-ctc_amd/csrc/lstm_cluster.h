@@ -3,12 +3,11 @@
 // arrival / exit, the octet decode, the give-up protocol of the bounded spins, the LDS-DMA helpers.
 #pragma once
 #include "common.h"
-
-constexpr int MGR_MAX_SCAN_JOBS = 8;
+#include "scan_choice.h"   // MGR_MAX_SCAN_JOBS, kScanHdrBytes, the instantiation lists, mgr_scan_*_decide
 
 // Header of every persistent launch's workspace (zeroed by a memset node ahead of the launch).
 //   [0] give-up code of THIS launch (a bounded spin expired)          [1] arrival counter (workgroups that have started)
-constexpr size_t kScanHdrBytes = 4096;   //   [64, 1024) XCC (XCD) id + 1 of every workgroup of the launch (XCD-local exchange)
+//   (kScanHdrBytes = 4096, scan_choice.h)                            [64, 1024) XCC (XCD) id + 1 of every workgroup of the launch (XCD-local exchange)
 
 // Status block (mgr_ctx::sticky_status, or the block bound with mgr_scan_status_bind; never cleared by a launch):
 //   [0] OR of every launch's status bits since the last mgr_scan_status_clear
@@ -66,13 +65,8 @@ struct ClusterLaunch {
   ClusterJob job[MGR_MAX_SCAN_JOBS];
 };
 
-// true if (ks, tpw) has an instantiation / if ks has a K-split instantiation
-bool mgr_cluster_supported(int ks, int tpw);
-bool mgr_cluster_ks_supported(int ks);
-// geometry of the launch that mgr_cluster_launch would issue: waves per workgroup, workgroups per CU
-void mgr_cluster_geometry(const ClusterLaunch& L, bool any_exchange, int* waves, int* per_cu);
-bool mgr_cluster_uses_ks(const ClusterLaunch& L, bool any_exchange);   // the launch will run the K-split kernel (which honours ClusterJob::YT)
-int mgr_cluster_launch(mgr_ctx* c, const ClusterLaunch& L, int total_wgs, bool any_exchange);
+// issues the launch that C (mgr_scan_fwd_decide) describes: kernel, grid, block, LDS
+int mgr_cluster_launch(mgr_ctx* c, const ClusterLaunch& L, const mgr_scan_choice& C);
 
 // ---- backward (lstm_cluster_bwd.hip)
 struct ClusterBwdJob {
@@ -96,12 +90,8 @@ struct ClusterBwdLaunch {
                    // cls_* fields then count ceil(G_ / 2) members per cluster (k_scan_cluster_bwd16_f / _fd)
   ClusterBwdJob job[MGR_MAX_SCAN_JOBS];
 };
-bool mgr_cluster_bwd_supported(int H);
-bool mgr_cluster_bwd_fusable(const mgr_ctx* c, const ClusterBwdLaunch& L);   // L.xcd_local, the jobs' H / G_ filled in
-size_t mgr_cluster_bwd_img_floats(int H);
-void mgr_cluster_bwd_geometry(const mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs, int* waves, int* per_cu);
-// form16: 0 trimmed, 1 yielding, 2 direct (mgr.h, MGR_TUNE_BPTT_FORM)
-int mgr_cluster_bwd_launch(mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs, int form16);
+// issues the launch that C (mgr_scan_bwd_decide) describes
+int mgr_cluster_bwd_launch(mgr_ctx* c, const ClusterBwdLaunch& L, const mgr_scan_choice& C);
 
 // ---- admission of persistent launches (lstm.hip): co-residency by construction across the streams of a context
 int mgr_persist_admit(mgr_ctx* c, int wgs, int waves_per_wg, int per_cu, int fused, unsigned* seq_out);

@@ -906,12 +906,7 @@ __device__ __forceinline__ void cluster_run_k16(const ClusterJob& jb, const Clus
   if (ytrow) ks_zero_tail(ytrow, T, jb.ldt, yt_split);
 }
 
-#define CLKS_FOREACH(X) X(125) X(75) X(32) X(25)
-
-#define CL_FOREACH(X) \
-  X(125, 1) X(75, 1) X(75, 2) X(32, 1) X(32, 2) X(32, 4) X(25, 1) X(25, 2) X(25, 4) X(16, 1) X(16, 2) X(8, 1) X(8, 2) \
-  X(4, 1) X(3, 1) X(2, 1) X(1, 1)
-
+// (CL_FOREACH, CLKS_LARGE / CLKS_SMALL: the instantiation lists of scan_choice.h)
 // A workgroup locates its (job, batch group, unit group) by walking the launch's job table IN the kernel body (taking the
 // address of the kernel argument in a helper would make hipcc copy the whole struct to scratch memory).  Members of a cluster
 // are CONTIGUOUS workgroup ids: the round-robin dispatcher then spreads them over all XCDs, which measured best for the
@@ -939,8 +934,6 @@ __global__ __launch_bounds__(CL_WAVES * 64) void k_scan_cluster(ClusterLaunch L)
 // Two kernels, by layer width: a kernel's register allocation is that of its largest instantiation (209 VGPRs for H = 500), and
 // a narrow layer's scan (the fusion layer, H = 100: 56 workgroups that run BESIDE the 408 of the encoder scans) should not
 // ask a CU for registers it never touches - with ~100 it fits on any CU that has a wave slot left.
-#define CLKS_LARGE(X) X(125) X(75)
-#define CLKS_SMALL(X) X(32) X(25)
 template <bool SMALL>
 __device__ __forceinline__ void scan_cluster_ks_body(const ClusterLaunch& L, float* smem) {
   mgr_cluster_enter(L.cm);
@@ -1068,76 +1061,15 @@ constexpr size_t K16FS_LDS_BYTES = (2 * (size_t)K16_LDS_FLOATS + 4 * 4 * 2 * 256
 
 }  // namespace
 
-bool mgr_cluster_supported(int ks, int tpw) {
-#define CL_CASE(KS, TPW) \
-  if (ks == KS && tpw == TPW) return true;
-  CL_FOREACH(CL_CASE)
-#undef CL_CASE
-  return false;
-}
+// (scan_choice.h states the dynamic LDS of these kernels for its decision: the layouts above are what it must say)
+static_assert(kScanLdsKs == KS_LDS_FLOATS * sizeof(float) && kScanLdsK16 == K16_LDS_FLOATS * sizeof(float) && kScanLdsK16Fused == K16FS_LDS_BYTES &&
+                  CL_WAVES == 8,
+              "scan_choice.h: LDS bytes / waves of the forward cluster kernels");
 
-bool mgr_cluster_ks_supported(int ks) {
-#define CLKS_CASE(KS) \
-  if (ks == KS) return true;
-  CLKS_FOREACH(CLKS_CASE)
-#undef CLKS_CASE
-  return false;
-}
-
-static bool ks_eligible(const ClusterLaunch& L, bool any_exchange, int waves) {
-  bool ks_all = L.ksplit && any_exchange && waves == 4;
-  for (int i = 0; i < L.njobs && ks_all; ++i) {
-    const ClusterJob& j = L.job[i];
-    bool inst = false;
-#define CLKS_CASE(KS) \
-  if (j.ks == KS) inst = true;
-    CLKS_FOREACH(CLKS_CASE)
-#undef CLKS_CASE
-    ks_all = inst && j.G_ > 1 && j.tpw == 1 && j.nw == 4;
-  }
-  return ks_all;
-}
-
-static size_t image_lds(const ClusterLaunch& L) {
-  size_t lds = 0;
-  for (int i = 0; i < L.njobs; ++i) {
-    size_t need = 2 * (size_t)((L.job[i].ks + 3) / 4) * 256 * sizeof(float);
-    lds = need > lds ? need : lds;
-  }
-  return lds;
-}
-
-void mgr_cluster_geometry(const ClusterLaunch& L, bool any_exchange, int* waves, int* per_cu) {
-  int maxnw = 0;
-  for (int i = 0; i < L.njobs; ++i) maxnw = L.job[i].nw > maxnw ? L.job[i].nw : maxnw;
-  *waves = maxnw <= 4 ? 4 : CL_WAVES;
-  // 4-wave workgroups with <= 80 KiB of LDS fit two per CU (8 waves, <= 256 VGPRs each); anything else sits alone on its CU
-  *per_cu = (*waves == 4 && (ks_eligible(L, any_exchange, *waves) || image_lds(L) <= 80 * 1024)) ? 2 : 1;
-  if (L.fused && L.split16 && ks_eligible(L, any_exchange, *waves)) {              // (the fused form: 8 waves, 104 KiB, a CU of its own)
-    *waves = 8;
-    *per_cu = 1;
-  }
-}
-
-bool mgr_cluster_uses_ks(const ClusterLaunch& L, bool any_exchange) {
-  if (L.fused && L.split16 && ks_eligible(L, any_exchange, 4)) return true;
-  int waves, per_cu;
-  mgr_cluster_geometry(L, any_exchange, &waves, &per_cu);
-  return ks_eligible(L, any_exchange, waves);
-}
-
-int mgr_cluster_launch(mgr_ctx* c, const ClusterLaunch& L, int total_wgs, bool any_exchange) {
-  int waves, per_cu;
-  mgr_cluster_geometry(L, any_exchange, &waves, &per_cu);
-  size_t lds = image_lds(L);
-  if (any_exchange) {
-    // co-residency of every spinning workgroup is what makes the in-launch hand-off deadlock-free; a workgroup that must sit
-    // alone on its CU says so through its LDS request
-    if (per_cu == 1 && lds < 84 * 1024) lds = 84 * 1024;
-    const int live = L.live_wgs > 0 ? L.live_wgs : total_wgs;
-    MGR_REQUIRE(live <= per_cu * c->cu_count, "cluster scan needs %d co-resident workgroups but the device holds %d", live,
-                per_cu * c->cu_count);
-  }
+int mgr_cluster_launch(mgr_ctx* c, const ClusterLaunch& L, const mgr_scan_choice& C) {
+  // co-residency of every spinning workgroup is what makes the in-launch hand-off deadlock-free
+  MGR_REQUIRE(!C.exchange || C.live <= C.per_cu * c->cu_count, "cluster scan needs %d co-resident workgroups but the device holds %d", C.live,
+              C.per_cu * c->cu_count);
   if (!(c->attr_done & MGR_ATTR_SCAN_CLUSTER)) {   // (function attributes are per device, hence per context)
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_ks), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1146,30 +1078,20 @@ int mgr_cluster_launch(mgr_ctx* c, const ClusterLaunch& L, int total_wgs, bool a
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_k16_s), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     c->attr_done |= MGR_ATTR_SCAN_CLUSTER;
   }
-  const bool fused = L.fused && L.split16 && ks_eligible(L, any_exchange, 4);
-  MGR_REQUIRE(!L.xcd_local || fused || ks_eligible(L, any_exchange, waves), "XCD-local layout is only understood by the K-split kernel");
-  if (fused) {
-    MGR_REQUIRE(L.xcd_local, "the fused form is laid out in octets");
-    if (!(c->attr_done & MGR_ATTR_SCAN_CLUSTER_FUSED)) {   // (per device, hence per context - like the block above)
-      MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_k16fs), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      c->attr_done |= MGR_ATTR_SCAN_CLUSTER_FUSED;
-    }
-    hipLaunchKernelGGL(k_scan_cluster_k16fs, dim3(total_wgs), dim3(512), K16FS_LDS_BYTES, mgr_stream(c), L);
-  } else if (ks_eligible(L, any_exchange, waves)) {
-    // partial-sum exchange, staging tiles of the transposed output, Z / R rings (no h image): 50 KiB, two workgroups per CU
-    bool small = true;
-    for (int i = 0; i < L.njobs; ++i) small = small && L.job[i].ks <= 32;
-    if (L.split16) {
-      if (small)
-        hipLaunchKernelGGL(k_scan_cluster_k16_s, dim3(total_wgs), dim3(256), K16_LDS_FLOATS * sizeof(float), mgr_stream(c), L);
-      else
-        hipLaunchKernelGGL(k_scan_cluster_k16, dim3(total_wgs), dim3(256), K16_LDS_FLOATS * sizeof(float), mgr_stream(c), L);
-    } else if (small)
-      hipLaunchKernelGGL(k_scan_cluster_ks_s, dim3(total_wgs), dim3(256), KS_LDS_FLOATS * sizeof(float), mgr_stream(c), L);
-    else
-      hipLaunchKernelGGL(k_scan_cluster_ks, dim3(total_wgs), dim3(256), KS_LDS_FLOATS * sizeof(float), mgr_stream(c), L);
-  } else {
-    hipLaunchKernelGGL(k_scan_cluster, dim3(total_wgs), dim3(waves * 64), lds, mgr_stream(c), L);
+  if (C.kernel == MGR_SCAN_FWD_K16_FUSED && !(c->attr_done & MGR_ATTR_SCAN_CLUSTER_FUSED)) {   // (per device, hence per context - like the block above)
+    MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_k16fs), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    c->attr_done |= MGR_ATTR_SCAN_CLUSTER_FUSED;
+  }
+  const dim3 grid(C.grid), block(C.block);
+  const size_t lds = (size_t)C.lds_bytes;
+  switch (C.kernel) {
+    case MGR_SCAN_FWD_IMAGE: hipLaunchKernelGGL(k_scan_cluster, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_FWD_KS: hipLaunchKernelGGL(k_scan_cluster_ks, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_FWD_KS_S: hipLaunchKernelGGL(k_scan_cluster_ks_s, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_FWD_K16: hipLaunchKernelGGL(k_scan_cluster_k16, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_FWD_K16_S: hipLaunchKernelGGL(k_scan_cluster_k16_s, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_FWD_K16_FUSED: hipLaunchKernelGGL(k_scan_cluster_k16fs, grid, block, lds, mgr_stream(c), L); break;
+    default: MGR_REQUIRE(false, "cluster scan: no kernel %d", C.kernel);
   }
   MGR_LAUNCH_CHECK();
   return 0;

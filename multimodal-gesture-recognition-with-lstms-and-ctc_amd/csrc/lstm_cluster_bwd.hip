@@ -756,10 +756,7 @@ __device__ __forceinline__ void cluster_bwd_run16(const ClusterBwdJob& jb, int b
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may be in flight when the wave ends
 }
 
-#define BW_SMALL(X) X(8) X(16) X(32) X(64) X(100) X(128)
-#define BW_LARGE(X) X(300) X(500)
-#define BW_FOREACH(X) BW_SMALL(X) BW_LARGE(X)
-
+// (BW_SMALL / BW_LARGE / BW_FOREACH: the instantiation lists of scan_choice.h)
 // SMALL: every job of the launch is narrow (H <= 128) - its own kernel, so that the fusion layer's BPTT (56 workgroups beside
 // the projection GEMMs of the other stream) is allocated ~100 VGPRs instead of the 256 the H = 500 instantiation needs
 template <bool SPLIT, bool SMALL = false, bool F16 = false, int LEAN = 0>
@@ -889,56 +886,12 @@ __global__ __launch_bounds__(2 * BW_WAVES * 64) void k_scan_cluster_bwd16_split(
 
 }  // namespace
 
-// floats of exchange memory per batch group and slot: [dest G][src G][256]
-size_t mgr_cluster_bwd_img_floats(int H) {
-  size_t g = (size_t)(H + 15) / 16;
-  return g * g * 256;
-}
+// (scan_choice.h states the dynamic LDS of these kernels for its decision: the layouts above are what it must say)
+static_assert(kScanLdsBwdA == BW_LDS_FLOATS_A * sizeof(float) && kScanLdsBwdB == BW_LDS_FLOATS_B * sizeof(float) && BW_WAVES == 4,
+              "scan_choice.h: LDS bytes / waves of the BPTT cluster kernels");
 
-bool mgr_cluster_bwd_supported(int H) {
-#define BW_CASE(HH) \
-  if (H == HH) return true;
-  BW_FOREACH(BW_CASE)
-#undef BW_CASE
-  return false;
-}
-
-// split roles (8 waves, > 80 KiB of LDS requested so that exactly one workgroup sits on a CU) whenever the launch fits one
-// workgroup per CU, has an exchange at all and the layers are wide: at H = 100 (7 workgroups per cluster, two 16-byte stores
-// per lane and step) the store acknowledgement is 0.35 of 2.2 us and the 8-wave workgroups cost config F 0.7 % end to end,
-// at H = 300 / 500 they save a third of the step (E: 60 -> 48 ms/step, S_ref 24 -> 21).  MGR_TUNE_BPTT_SPLIT_ROLE: 1 = never, 2 = always.
-static bool bwd_split(const mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs) {
-  int maxH = 0;
-  bool exchange = false;
-  for (int i = 0; i < L.njobs; ++i) {
-    maxH = L.job[i].H > maxH ? L.job[i].H : maxH;
-    exchange = exchange || L.job[i].G_ > 1;
-  }
-  const int key = c->tune[MGR_TUNE_BPTT_SPLIT_ROLE];
-  return exchange && (maxH >= 200 || key == 2) && total_wgs <= c->cu_count && key != 1;
-}
-
-// the fused form runs narrow layers (16 < H <= 128) on the split-f16 path, laid out in XCD-local octets
-bool mgr_cluster_bwd_fusable(const mgr_ctx* c, const ClusterBwdLaunch& L) {
-  bool ok = c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0 && L.xcd_local && L.njobs > 0;
-  for (int i = 0; i < L.njobs; ++i) ok = ok && L.job[i].H > 16 && L.job[i].H <= 128 && L.job[i].G_ >= 2;
-  return ok;
-}
-
-void mgr_cluster_bwd_geometry(const mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs, int* waves, int* per_cu) {
-  if (L.fused) {
-    *waves = 2 * BW_WAVES;
-    *per_cu = 1;
-    return;
-  }
-  const bool split = bwd_split(c, L, total_wgs);
-  *waves = split ? 2 * BW_WAVES : BW_WAVES;
-  *per_cu = split ? 1 : 2;
-}
-
-int mgr_cluster_bwd_launch(mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs, int form16) {
-  const bool alone = form16 == 0;
-  MGR_REQUIRE(total_wgs <= 2 * c->cu_count, "cluster BPTT needs %d co-resident workgroups", total_wgs);
+int mgr_cluster_bwd_launch(mgr_ctx* c, const ClusterBwdLaunch& L, const mgr_scan_choice& C) {
+  MGR_REQUIRE(C.grid <= 2 * c->cu_count, "cluster BPTT needs %d co-resident workgroups", C.grid);
   if (!(c->attr_done & MGR_ATTR_SCAN_CLUSTER_BWD)) {
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_bwd_split), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -952,38 +905,20 @@ int mgr_cluster_bwd_launch(mgr_ctx* c, const ClusterBwdLaunch& L, int total_wgs,
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_cluster_bwd16_fd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     c->attr_done |= MGR_ATTR_SCAN_CLUSTER_BWD;
   }
-  const bool f16 = c->tune[MGR_TUNE_SCAN_F32_MFMA] == 0;   // split-f16 operands (MGR_TUNE_SCAN_F32_MFMA = 1: f32 MFMA)
-  if (L.fused) {
-    MGR_REQUIRE(mgr_cluster_bwd_fusable(c, L) && total_wgs <= c->cu_count, "the fused BPTT form needs narrow split-f16 layers in octets, one workgroup per CU");
-    // (>= 84 KiB requested: the workgroup sits alone on its CU whatever its registers would allow)
-    size_t lds = 2 * (size_t)BW_LDS_FLOATS_B * sizeof(float);
-    lds = lds < 84 * 1024 ? 84 * 1024 : lds;
-    if (form16 == 2)
-      hipLaunchKernelGGL(k_scan_cluster_bwd16_fd, dim3(total_wgs), dim3(2 * BW_WAVES * 64), lds, mgr_stream(c), L);
-    else
-      hipLaunchKernelGGL(k_scan_cluster_bwd16_f, dim3(total_wgs), dim3(2 * BW_WAVES * 64), lds, mgr_stream(c), L);
-  } else if (bwd_split(c, L, total_wgs)) {
-    size_t lds = 84 * 1024;
-    if (f16)
-      hipLaunchKernelGGL(k_scan_cluster_bwd16_split, dim3(total_wgs), dim3(2 * BW_WAVES * 64), lds, mgr_stream(c), L);
-    else
-      hipLaunchKernelGGL(k_scan_cluster_bwd_split, dim3(total_wgs), dim3(2 * BW_WAVES * 64), lds, mgr_stream(c), L);
-  } else {
-    size_t lds = (size_t)BW_LDS_FLOATS_A * sizeof(float);
-    bool small = true;
-    for (int i = 0; i < L.njobs; ++i) small = small && L.job[i].H <= 128;
-    if (small && f16 && form16 == 2)
-      hipLaunchKernelGGL(k_scan_cluster_bwd16_sd, dim3(total_wgs), dim3(BW_WAVES * 64), (size_t)BW_LDS_FLOATS_B * sizeof(float), mgr_stream(c), L);
-    else if (small && f16 && alone)
-      hipLaunchKernelGGL(k_scan_cluster_bwd16_sl, dim3(total_wgs), dim3(BW_WAVES * 64), (size_t)BW_LDS_FLOATS_B * sizeof(float), mgr_stream(c), L);
-    else if (small && f16)
-      hipLaunchKernelGGL(k_scan_cluster_bwd16_s, dim3(total_wgs), dim3(BW_WAVES * 64), lds, mgr_stream(c), L);
-    else if (small)
-      hipLaunchKernelGGL(k_scan_cluster_bwd_s, dim3(total_wgs), dim3(BW_WAVES * 64), lds, mgr_stream(c), L);
-    else if (f16)
-      hipLaunchKernelGGL(k_scan_cluster_bwd16, dim3(total_wgs), dim3(BW_WAVES * 64), lds, mgr_stream(c), L);
-    else
-      hipLaunchKernelGGL(k_scan_cluster_bwd, dim3(total_wgs), dim3(BW_WAVES * 64), lds, mgr_stream(c), L);
+  const dim3 grid(C.grid), block(C.block);
+  const size_t lds = (size_t)C.lds_bytes;
+  switch (C.kernel) {
+    case MGR_SCAN_BWD: hipLaunchKernelGGL(k_scan_cluster_bwd, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_BWD_S: hipLaunchKernelGGL(k_scan_cluster_bwd_s, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_BWD_SPLIT: hipLaunchKernelGGL(k_scan_cluster_bwd_split, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_BWD_16: hipLaunchKernelGGL(k_scan_cluster_bwd16, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_BWD_16_S: hipLaunchKernelGGL(k_scan_cluster_bwd16_s, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_BWD_16_SL: hipLaunchKernelGGL(k_scan_cluster_bwd16_sl, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_BWD_16_SD: hipLaunchKernelGGL(k_scan_cluster_bwd16_sd, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_BWD_16_SPLIT: hipLaunchKernelGGL(k_scan_cluster_bwd16_split, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_BWD_16_F: hipLaunchKernelGGL(k_scan_cluster_bwd16_f, grid, block, lds, mgr_stream(c), L); break;
+    case MGR_SCAN_BWD_16_FD: hipLaunchKernelGGL(k_scan_cluster_bwd16_fd, grid, block, lds, mgr_stream(c), L); break;
+    default: MGR_REQUIRE(false, "cluster BPTT: no kernel %d", C.kernel);
   }
   MGR_LAUNCH_CHECK();
   return 0;

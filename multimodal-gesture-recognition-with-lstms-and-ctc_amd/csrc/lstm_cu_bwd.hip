@@ -276,30 +276,17 @@ __global__ __launch_bounds__(CB_WAVES * 64, 1) void k_scan_bwd_cu16(CuBwdJobs J,
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may be in flight when the wave ends
 }
 
-#define CB_FOREACH(X) X(32) X(64) X(100)   // (H = 128: eight tiles - image + rings would need 160.1 KiB of LDS; it keeps the multi-CU forms)
-
 }  // namespace
 
-bool mgr_scan_bwd_cu16_supported(int H) {
-#define CB_CASE(HH) \
-  if (H == HH) return true;
-  CB_FOREACH(CB_CASE)
-#undef CB_CASE
-  return false;
-}
-
 // All jobs (same H, B, T, lddy: the two directions of a layer) as ONE launch, blockIdx.y = job: (B + 15) / 16 x njobs workgroups, a CU
-// each.  No exchange between workgroups: the launch needs no entry in the residency ledger.  Returns 1 if launched, 0 if the shape has
-// no instantiation or an operand is not laid out for the 16-byte LDS-DMA rows, < 0 on error.
-int mgr_scan_bwd_cu16_multi(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jobs) {
+// each.  No exchange between workgroups: the launch needs no entry in the residency ledger.  Whether the call takes this form - an
+// instantiation (CB_FOREACH, scan_choice.h), operands laid out for the 16-byte LDS-DMA rows - is decided by mgr_scan_bwd_decide
+// (C.single_cu); C carries the LDS bytes.
+int mgr_scan_bwd_cu16_multi(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jobs, const mgr_scan_choice& C) {
   const int B = jobs[0].B, T = jobs[0].T, H = jobs[0].H, lddy = jobs[0].lddy;
-  if (!mgr_scan_bwd_cu16_supported(H) || lddy % 4 != 0) return 0;
-  if ((size_t)B * T * H * 16 >= ((size_t)1 << 32) || (size_t)B * T * lddy * 4 >= ((size_t)1 << 32)) return 0;   // (32-bit lane offsets)
   CuBwdJobs J;
   memset(&J, 0, sizeof(J));
   for (int i = 0; i < njobs; ++i) {
-    if (jobs[i].B != B || jobs[i].T != T || jobs[i].H != H || jobs[i].lddy != lddy) return 0;
-    if ((reinterpret_cast<uintptr_t>(jobs[i].dY) & 15) || (reinterpret_cast<uintptr_t>(jobs[i].cs) & 15)) return 0;
     J.dY[i] = jobs[i].dY; J.G[i] = jobs[i].gates; J.Cs[i] = jobs[i].cs; J.Up[i] = jobs[i].Up; J.dZ[i] = jobs[i].dZ;
     J.reverse[i] = jobs[i].reverse;
   }
@@ -307,12 +294,12 @@ int mgr_scan_bwd_cu16_multi(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jobs)
   hipStream_t s = mgr_stream(c);
 #define CB_CASE(HH)                                                                                                              \
   if (H == HH) {                                                                                                                 \
-    const size_t lds = (size_t)CbCfg<HH>::LDS_FLOATS * sizeof(float);                                                            \
+    static_assert(mgr_scan_bwd_cu16_lds(HH) == (size_t)CbCfg<HH>::LDS_FLOATS * sizeof(float) && CB_WAVES == 8, "scan_choice.h: LDS bytes"); \
     MGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_bwd_cu16<HH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-    hipLaunchKernelGGL((k_scan_bwd_cu16<HH>), grid, dim3(CB_WAVES * 64), lds, s, J, lddy, B, T);                                  \
+    hipLaunchKernelGGL((k_scan_bwd_cu16<HH>), grid, dim3(C.block), (size_t)C.lds_bytes, s, J, lddy, B, T);                         \
   }
   CB_FOREACH(CB_CASE)
 #undef CB_CASE
   MGR_LAUNCH_CHECK();
-  return 1;
+  return 0;
 }

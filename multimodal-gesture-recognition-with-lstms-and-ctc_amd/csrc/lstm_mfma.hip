@@ -164,13 +164,7 @@ int mgr_scan_bwd_mfma_multi(mgr_ctx* c, int njobs, const mgr_scan_bwd_job* jobs)
     hipLaunchKernelGGL((k_scan_bwd_mfma<HH>), grid, dim3(NW * 64), 0, s, J, lddy, B, T); \
     break;
   switch (H) {
-    BWD_CASE(4)
-    BWD_CASE(8)
-    BWD_CASE(16)
-    BWD_CASE(32)
-    BWD_CASE(64)
-    BWD_CASE(100)
-    BWD_CASE(128)
+    BWD_MFMA_FOREACH(BWD_CASE)   // (the instantiation list of scan_choice.h)
     default:
       return 0;
   }
