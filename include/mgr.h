@@ -1010,6 +1010,52 @@ int mgr_mfcc(mgr_ctx* ctx, const int16_t* samples, const int64_t* sample_offsets
  * deterministic (no atomics). */
 int mgr_roi_crop(mgr_ctx* ctx, const uint8_t* frames, int n, int H, int W, const int32_t* boxes, int img_dim, uint8_t* out);
 
+/* ---- K20 / K21: live recognition - chunked BiLSTM inference with carried state.  Inference only. ----
+ * A session is a stream of frames that is still being produced; the network sees it in WINDOWS of Tw frames.  Per window and
+ * session s, n_valid[s] <= Tw frames are present and the first n_keep[s] <= n_valid[s] of them are answered by this window (the
+ * rest is lookahead, seen again by the next window).  One job of the call below is ONE direction of ONE layer for S sessions:
+ *   Z [S,Tw,4H] and Up [H,4H] packed, Y with row stride ldy, R (or NULL) with row stride ldr: as in the scan jobs above.
+ *   reverse == 0: the recurrence starts from state [S,2,H] = (h, c) of each session, walks t = 0 .. n_valid[s] - 1 and overwrites
+ *                 the state with (h, c) after frame n_keep[s] - 1; with n_keep[s] == 0 the state is left as it was.
+ *   reverse != 0: starts from zero at t = n_valid[s] - 1 and walks down to 0; state must be NULL.
+ * n_valid, n_keep: device int32 [S], shared by the jobs of the call.  n_valid[s] == 0: the session is idle - nothing of it is read
+ * and no byte of its Y rows or its state is written.  Otherwise rows n_valid[s] <= t < Tw of Y (columns 0:H) are written as zero,
+ * and rows t >= n_valid[s] of Z are never read (they may hold NaN).  The device clips n_valid into [0, Tw] and n_keep into
+ * [0, n_valid].  h_n_valid / h_n_keep: the same values on the HOST, or both NULL; when given they are checked (0 <= n_keep <=
+ * n_valid <= Tw) before anything is enqueued.
+ * Kernel: one 16-wave workgroup per (job, group of 4 sessions); no workgroup waits for another, so the call cannot hang on
+ * residency and needs no workspace.  The recurrent matrix is streamed from L2 every step, the k range of the product split over
+ * the waves and reduced through LDS in a fixed order: the summation order of a pre-activation is a function of H alone - not of the
+ * step's place in the window, of Tw, or of the session's slot - so a session cut into windows differently gives the same bits.
+ * 1 <= H <= MGR_LIVE_MAX_H, 1 <= njobs <= MGR_LIVE_MAX_JOBS, all jobs with the same S and Tw; pointers 16-byte aligned. */
+#define MGR_LIVE_MAX_H 1024
+#define MGR_LIVE_MAX_JOBS 8
+typedef struct mgr_live_job {
+  const float* Z;
+  const float* Up;
+  float* Y;
+  const float* R;
+  float* state;
+  int ldy, ldr, H, reverse;
+} mgr_live_job;
+int mgr_lstm_scan_window(mgr_ctx* ctx, int njobs, const mgr_live_job* jobs, int S, int Tw, const int32_t* n_valid, const int32_t* n_keep,
+                         const int32_t* h_n_valid, const int32_t* h_n_keep);
+/* Greedy CTC decode that carries its open run from call to call: P [S,Tw,C] are the posteriors of a window, of which the first
+ * n_keep[s] rows (device int32 [S], clipped into [0, Tw]) are the session's next frames.  state: device int32 [S, MGR_LIVE_STATE_WORDS]
+ * = {frames consumed so far, the open run's label (-1: none), its first frame, its last frame, its frame count, the float32 sum of
+ * its frame maxima (as bits), 0, 0}; all zero except label = -1 is a fresh session - and so is all zero: a run counts only with a
+ * frame count > 0.  Frames are numbered from the session's start; frames below skip are ignored.  Per frame the best class is the argmax
+ * with the first index on ties; equal neighbouring best classes form a run; a run is FINAL when a frame with another best class
+ * follows it or when flush[s] != 0 (device int32 [S] or NULL: the open run is closed behind this call's frames).  Final runs whose
+ * label is not blank are this call's events, in order: n_events [S] = their TRUE count, also beyond cap, and for e < min(n_events,
+ * cap): lab [S,cap], seg [S,cap,2] = (first, last) frame, conf [S,cap] = the sum of the run's frame maxima, added one at a time in
+ * float32 in frame order, divided by its frame count.  Entries from n_events on are not written.  The confidence filter of the
+ * offline decode counts over a whole recording and is not causal: this is its thr < 0 form.  One wave per session.
+ * 1 <= C, 0 <= blank < C or blank < 0 (no blank), cap >= 0, skip >= 0. */
+#define MGR_LIVE_STATE_WORDS 8
+int mgr_live_greedy(mgr_ctx* ctx, const float* P, int S, int Tw, int C, const int32_t* n_keep, int blank, int skip, int32_t* state,
+                    const int32_t* flush, int cap, int32_t* n_events, int32_t* lab, int32_t* seg, float* conf);
+
 #ifdef __cplusplus
 }
 #endif

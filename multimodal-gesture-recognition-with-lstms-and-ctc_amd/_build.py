@@ -16,7 +16,7 @@ MGR_H = os.path.join(HERE, "..", "include", "mgr.h")
 SOURCES = ["ctx.hip", "elementwise.hip", "ctc.hip", "dense.hip", "gemm.hip", "gemm_split.hip", "lstm_simple.hip", "lstm_mfma.hip",
            "lstm_cluster.hip", "lstm_cluster_bwd.hip", "lstm_cu_bwd.hip", "lstm.hip", "comm.hip", "beam.hip", "skeletal.hip", "conv.hip",
            "mfcc.hip", "roi.hip", "activity.hip", "align.hip", "edit.hip", "lexicon.hip", "rescore.hip", "risk.hip", "sample.hip", "overlap.hip",
-           "joint.hip", "augment.hip", "seqlen.hip"]
+           "joint.hip", "augment.hip", "seqlen.hip", "lstm_live.hip", "live_decode.hip"]
 ARCH = "gfx950"
 
 

@@ -155,6 +155,8 @@ SIGNATURES = {
     "mgr_conv_pool_bwd_weights_ws_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
     "mgr_conv_pool_bwd_weights": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz]),
     "mgr_roi_crop": (i32, [vp, vp, i32, i32, i32, vp, i32, vp]),
+    "mgr_lstm_scan_window": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+    "mgr_live_greedy": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]),
 }
 
 SCAN_GAVE_UP, SCAN_NONFINITE = 1, 8   # enum in include/mgr.h (mgr_scan_status)
@@ -232,6 +234,26 @@ def describe_scan(direction, cu_count, tune, jobs, form=0, ws_bytes=None):
         rc = lib.mgr_lstm_scan_bwd_describe(cu_count, t, TUNE_COUNT, len(jobs), arr, C.byref(opts), C.byref(out))
     check(rc, lib)
     return out
+
+
+class LiveJob(C.Structure):
+    """struct mgr_live_job (K20)"""
+    _fields_ = [("Z", vp), ("Up", vp), ("Y", vp), ("R", vp), ("state", vp), ("ldy", i32), ("ldr", i32), ("H", i32), ("reverse", i32)]
+
+
+LIVE_MAX_H, LIVE_MAX_JOBS, LIVE_STATE_WORDS = 1024, 8, 8     # MGR_LIVE_* of include/mgr.h
+
+
+def make_live_jobs(jobs):
+    """jobs: list of dicts with the mgr_live_job fields (DeviceArray or int pointers; R / state may be absent)."""
+    arr = (LiveJob * max(len(jobs), 1))()
+    for a, j in zip(arr, jobs):
+        for k in ("Z", "Up", "Y", "R", "state"):
+            v = j.get(k, 0)
+            setattr(a, k, v.ptr if isinstance(v, DeviceArray) else (v or 0))
+        for k in ("ldy", "ldr", "H", "reverse"):
+            setattr(a, k, int(j.get(k, 0)))
+    return arr
 
 
 class SeqFillJob(C.Structure):

@@ -15,6 +15,14 @@ def decode_batch(pred_out, f_list, out_file="final_ctc_recout.mlf"):
     return ret
 
 
+def decode_live(model, frames_iter, chunk=20, lookahead=20):
+    """decode_segments for a session that is still producing frames (live.decode_live): frames_iter yields {input name:
+    [n, F]} pieces at the network rate; yields (name, first_frame, last_frame, confidence) as gestures are finalised, chunk +
+    lookahead frames behind the signal.  No confidence filter (it counts over a whole recording)."""
+    from ..live import decode_live as _decode_live
+    return _decode_live(model, frames_iter, chunk, lookahead, map_gest)
+
+
 def decode_segments(pred_out, f_list, out_file="final_ctc_recout_timed.mlf"):
     """decode_batch with start and end times: pred_out (N, T, C) softmax - or the per-sample segment lists that
     Model.predict_generator(decode="segments", threshold=THRESHOLD) computed on the device.  The same filter, collapse, class map and

@@ -207,6 +207,8 @@ PLAIN = StepLayout(False, False, _capi.SCAN_FORM_AUTO, _capi.SCAN_FORM_AUTO, Non
 
 
 class Engine:
+    closed = False      # set by close(): what shares this engine's buffers (live.LiveSession) checks it
+
     def __init__(self, spec, B, T, Lmax, device=0, seed=1234, comm=None, world=1, inference_only=False, schedule=None):
         self.spec = spec
         self.B, self.T, self.Lmax = int(B), int(T), int(Lmax)
@@ -1145,6 +1147,13 @@ class Engine:
         self._forward(False, None)
         P = self.P.download()
         return self._end_pass(blk.download(), P)
+
+    def open_live(self, sessions, chunk, lookahead, cap=None):
+        """A live.LiveSession over this engine's device weights: `sessions` slots fed frame by frame (push / end / reset / step),
+        the BiLSTMs in windows of chunk + lookahead frames with the forward states carried.  Works on any engine,
+        inference_only included; the session has its own buffers and touches none of this engine's."""
+        from . import live
+        return live.LiveSession(self, sessions, chunk, lookahead, cap=cap)
 
     def forward_train_phase(self, inputs, rand=None):
         """Softmax output with learning phase 1 (dropout / noise active) - no gradient."""
@@ -2363,6 +2372,7 @@ class Engine:
 
     def close(self):
         """Free this engine's device buffers; destroy the context only if the engine created it."""
+        self.closed = True
         if self.dev.ctx is None:
             return
         self.dev.sync()

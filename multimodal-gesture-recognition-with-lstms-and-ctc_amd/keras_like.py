@@ -566,6 +566,17 @@ class Model:
             return e.forward_train_phase(ins)
         return e.predict(ins)
 
+    def open_live(self, sessions, chunk, lookahead, cap=None):
+        """Engine.open_live on this model's engine (an inference-only one is built when there is none yet): live sessions fed frame
+        by frame, see live.LiveSession.  The session shares the engine's device weights - set_weights is seen by its next window -
+        and lives as long as that engine: a later call with another batch shape rebuilds the engine and ends the session (its next
+        call raises).  push takes the model's graph input names, as predict_on_batch does (early fusion: the two inputs of the
+        concatenated stream)."""
+        e = self._engine
+        if e is None:
+            e = self._ensure_engine(1, int(chunk) + int(lookahead), 1, inference_only=True)
+        return e.open_live(sessions, chunk, lookahead, cap=cap)
+
     def fit_generator(self, generator, steps_per_epoch, epochs=1, verbose=1, callbacks=None, validation_data=None,
                       validation_steps=None, initial_epoch=0, val_score=None, **kwargs):
         """val_score: None - validation logs val_loss (evaluate_generator), as before; True or a dict of score_generator arguments -
